@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mreads/s of the kalign hot path on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -16,10 +16,12 @@ Setup that is NOT timed: genome + reads synthesis on the GPU (torch RNG), suffix
 (k4_build_sa_device), index packing + k-mer table (k4_open_device), workspace reservation.
 Extra objects in the JSON line: "roofline" (algorithmic bytes of SURVEY.md 8(d) with run-time counted lookups and
 candidates / live HIP-event duration of the k4k_align_step launches of a batch; `traffic` = the PMC-measured HBM bytes of
-the same launches, quoted only while profiles/pmc_hbm_<workload>.json was taken on this build's kernel sources),
-"cpu_baseline" (the reference binary on the host cores when it travelled with the snapshot, else the CPU oracle; the
-oracle also serves as a read-for-read parity check at full scale) and "e2e" (FASTQ text in host memory -> SAM text in
-host memory through the overlapped pipeline; PCIe-inclusive, never `value`).
+the same launches, quoted only while profiles/pmc_hbm_<workload>.json was taken on this build's kernel sources) and
+"parity.nar_histogram" (the merged NAR counts).  Only with --full: "parity.truth_property_violations_rank0",
+"cpu_baseline" (the reference binary on the host cores when oracle/_ref/ngskit4b was built, else the CPU oracle; the
+oracle also serves as a read-for-read parity check at full scale, "parity.oracle_sample") and "e2e" (FASTQ text in host
+memory -> SAM text in host memory through the overlapped pipeline; PCIe-inclusive, never `value`); without it these are
+null.  --dump-outputs DIR writes the last timed step's records (a fixed sample) as .npy files, see dump_outputs().
 """
 import argparse
 import ctypes as C
@@ -308,7 +310,7 @@ def parse_args(argv=None):
                          "rep: 50 M x 100 bp SE vs a repeat-rich 1 Gbp genome (40 000 implanted copies, N runs), -s2 -- the "
                          "secondary tracked line for real-genome-like input, bound by the general kernel")
     ap.add_argument("--f2f-reads", type=int, default=50_000_000,
-                    help="reads (SE) / pairs (PE) of the file-to-file leg (k4align, files in tmpfs, index load inside the wall time; N=1, 0 = skip)")
+                    help="reads (SE) / pairs (PE) of the file-to-file leg (k4align, files in tmpfs, index load inside the wall time; N=1, --full, 0 = skip)")
     ap.add_argument("--chroms", type=int, default=None)
     ap.add_argument("--chrom-mbp", type=float, default=None)
     ap.add_argument("--reads", type=int, default=None, help="reads (SE) or pairs (PE) per GPU per step")
@@ -317,15 +319,23 @@ def parse_args(argv=None):
     ap.add_argument("--kmer-k", type=int, default=0)
     ap.add_argument("--repeats", type=int, default=None, help="implant this many repeat copies and N runs (stress; not the BASELINE workload)")
     ap.add_argument("--n-frac", type=float, default=0.0, help="fraction of reads given one N (general-kernel stress; not the BASELINE workload)")
-    ap.add_argument("--cpu-sample", type=int, default=12_000_000, help="upper bound on reads timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the truth-property check, the CPU baselines with "
+                         "their read-for-read parity sample, and the end-to-end and file-to-file legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (a fixed, seeded sample of its records, "
+                         "one float64 .npy per field) and the NAR histogram of all reads to DIR")
+    ap.add_argument("--cpu-sample", type=int, default=12_000_000, help="upper bound on reads timed on the CPU oracle (--full; 0 = skip)")
     ap.add_argument("--ref-sample", type=int, default=8_000_000,
-                    help="reads given to the real reference binary (oracle/_ref/ngskit4b) when it is present (0 = skip)")
+                    help="reads given to the real reference binary (oracle/_ref/ngskit4b) when it is present (--full; 0 = skip)")
     ap.add_argument("--ext", default="",
                     help="optional AlignReads phases (SURVEY 8(f4)), a secondary line on the workload's genome: c<pct> chimeric trimming "
                          "(kalign -c), a<len> microInDels (-a), A<len> splice junctions (-A), comma separated, e.g. c50 or a12,A3000")
     ap.add_argument("--e2e-reads", type=int, default=20_000_000,
-                    help="reads of the end-to-end leg (FASTQ text in host memory -> SAM text in host memory; C2 at N=1 only, 0 = skip)")
+                    help="reads of the end-to-end leg (FASTQ text in host memory -> SAM text in host memory; C2 at N=1 only, --full, 0 = skip)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     wl = WORKLOADS[args.workload]
     args.chroms = wl[0] if args.chroms is None else args.chroms
     args.reads = wl[1] if args.reads is None else args.reads
@@ -406,6 +416,74 @@ def merge_counts(nar_column, dist):
     if dist is not None:
         dist.all_reduce(hist, op=dist.ReduceOp.SUM)
     return hist.tolist()
+
+
+DUMP_SEED = 0x44554D50  # the rows --dump-outputs samples
+DUMP_ROWS = 1 << 18
+DUMP_LIMIT = 64 << 20  # bytes of .npy data at most
+
+
+def dump_outputs(path, out, hits, out_pe, seg2, nar):
+    """--dump-outputs DIR (rank 0): what the timed path handed its caller in the last step, one float64 .npy per record
+    field -- result_* / hit_* (k4_read_result, k4_hit), pe_* (k4_pe_read) for pairs, seg2_* (k4_seg2) with --ext -- over a
+    fixed, seeded sample of DUMP_ROWS rows (all rows when there are fewer), `row` (their row numbers) and `nar_histogram`
+    (the merged NAR counts of every read)"""
+    n = out.shape[0]
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_ROWS, replace=False))
+    sel = torch.from_numpy(rows).to(out.device)
+    arrays = {"row": rows, "nar_histogram": np.asarray(nar)}
+
+    def add(prefix, rec):  # one array per field (nested records: prefix_outer_inner)
+        for f in rec.dtype.names:
+            if rec.dtype[f].names:
+                add(prefix + "_" + f, rec[f])
+            else:
+                arrays[prefix + "_" + f] = rec[f]
+
+    def records(t, dtype):  # [n, k] i32 rows -> the sampled rows as records
+        return t.index_select(0, sel).cpu().numpy().view(dtype).reshape(-1)
+
+    if out_pe is not None:
+        add("pe", records(out_pe, k4.PE_READ_DTYPE))
+    else:
+        add("result", records(out, k4.RESULT_DTYPE))
+        add("hit", records(hits, k4.HIT_DTYPE))
+    if seg2 is not None:
+        add("seg2", records(seg2, k4.SEG2_DTYPE))
+    assert sum(a.size for a in arrays.values()) * 8 <= DUMP_LIMIT
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def truth_violations(args, truth, out, hits, out_pe):
+    """(--full) reads that break the truth property of an i.i.d. genome: AA at the truth locus with Mismatches == nsubs iff
+    nsubs <= MaxTotMM, else NL; None on a genome with implanted repeats"""
+    if args.repeats != 0:  # (the property needs an i.i.d. genome)
+        return None
+    pe, L, n_reads = args.pe, args.read_len, out.shape[0]
+    max_tot_mm = 0 if args.max_subs == 0 else max(1, int(0.5 + L * args.max_subs / 100.0))
+    ok = truth[:, 3] <= max_tot_mm
+    if pe:  # -U2: a pair is reported only when both ends are placed; then both are proper-pair flagged
+        both = ok[0::2] & ok[1::2]
+        ok = torch.repeat_interleave(both, 2)
+    hv = hits.view(torch.uint8).view(n_reads, 16)
+    h_chrom = hits[:, 0].to(torch.int64)
+    h_loci = hits[:, 1].to(torch.int64) & 0xFFFFFFFF
+    h_strand = hv[:, 10].to(torch.int64)
+    h_mm = hv[:, 11].to(torch.int64)
+    if args.ext_kw:  # with the optional phases a read beyond MaxTotMM may still align (trimmed, or in two segments): the weaker form
+        ok_reads = ok & (truth[:, 3] != 99)
+        return int((ok_reads & ~((out[:, 4] == k4.NAR_ACCEPTED) & (h_chrom == truth[:, 0]) & (h_loci == truth[:, 1]))).sum().item())
+    good = torch.where(truth[:, 3] == 99, torch.ones_like(ok), torch.where(
+        ok,
+        (out[:, 4] == k4.NAR_ACCEPTED) & (h_chrom == truth[:, 0]) & (h_loci == truth[:, 1]) & (h_mm == truth[:, 3])
+        & ((h_strand == ord("-")) == (truth[:, 2] == 1)),
+        (out[:, 4] != k4.NAR_ACCEPTED) if pe else (out[:, 4] == k4.NAR_NOHIT),
+    ))
+    if pe:
+        good &= torch.where(ok, out_pe[:, 4] == 1, out_pe[:, 4] == 0)  # FlgPEAligned
+    return int((~good).sum().item())
 
 
 def job_value(reads_per_rank, world, steps, elapsed):
@@ -679,43 +757,24 @@ def run(args, engine):
     elapsed = timed_steps(engine.step, engine.sync, dist, args.steps, args.warmup, dev, before_timing=engine.timing_begin)
     fast_ms, launches, ctr = engine.timing_end()
 
-    # ---- after the timed region: the count/merge collective and the parity checks --------------------------------
+    # ---- after the timed region: the count/merge collective, the outputs, and (--full) the parity checks and other legs ----
     out, hits, out_pe = engine.results()
     nar = merge_counts(out[:, 4], dist)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, hits, out_pe, getattr(engine, "seg2", None), nar)
 
     # (1) truth property on i.i.d. genomes: AA at the truth locus with Mismatches == nsubs iff nsubs <= MaxTotMM, else NL
-    max_tot_mm = 0 if args.max_subs == 0 else max(1, int(0.5 + L * args.max_subs / 100.0))
-    ok = truth[:, 3] <= max_tot_mm
-    if pe:  # -U2: a pair is reported only when both ends are placed; then both are proper-pair flagged
-        both = ok[0::2] & ok[1::2]
-        ok = torch.repeat_interleave(both, 2)
-    hv = hits.view(torch.uint8).view(n_reads, 16)
-    h_chrom = hits[:, 0].to(torch.int64)
-    h_loci = hits[:, 1].to(torch.int64) & 0xFFFFFFFF
-    h_strand = hv[:, 10].to(torch.int64)
-    h_mm = hv[:, 11].to(torch.int64)
-    good = torch.where(truth[:, 3] == 99, torch.ones_like(ok), torch.where(
-        ok,
-        (out[:, 4] == k4.NAR_ACCEPTED) & (h_chrom == truth[:, 0]) & (h_loci == truth[:, 1]) & (h_mm == truth[:, 3])
-        & ((h_strand == ord("-")) == (truth[:, 2] == 1)),
-        (out[:, 4] != k4.NAR_ACCEPTED) if pe else (out[:, 4] == k4.NAR_NOHIT),
-    ))
-    if pe:
-        good &= torch.where(ok, out_pe[:, 4] == 1, out_pe[:, 4] == 0)  # FlgPEAligned
-    truth_viol = int((~good).sum().item()) if args.repeats == 0 else None  # (the property needs an i.i.d. genome)
-    if args.ext_kw:  # with the optional phases a read beyond MaxTotMM may still align (trimmed, or in two segments): the weaker form
-        ok_reads = ok & (truth[:, 3] != 99)
-        truth_viol = int((ok_reads & ~((out[:, 4] == k4.NAR_ACCEPTED) & (h_chrom == truth[:, 0]) & (h_loci == truth[:, 1]))).sum().item()) if args.repeats == 0 else None
+    truth_viol = truth_violations(args, truth, out, hits, out_pe) if args.full else None
 
     # (2) CPU baseline = the oracle on all host cores over a bounded sample, same index, same reads (rank 0, N=1 only)
     cpu = None
     parity_sample = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0 and engine.is_gpu:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0 and engine.is_gpu:
         cpu, parity_sample = cpu_baseline(args, engine, seq, reads, out, hits, out_pe, n, el, n_chrom, chrom_len, L, pe, dev, rank)
 
     # (3) end to end: FASTQ text in host memory -> SAM text in host memory through the overlapped pipeline (never `value`)
     e2e = None
-    if rank == 0 and world == 1 and engine.is_gpu and args.e2e_reads > 0 and not args.ext_kw and hasattr(engine, "e2e"):
+    if args.full and rank == 0 and world == 1 and engine.is_gpu and args.e2e_reads > 0 and not args.ext_kw and hasattr(engine, "e2e"):
         # (pairs: half as many units, the same number of reads -- the leg's buffers sit beside the timed run's 100 M reads)
         e2e = engine.e2e(reads, min(args.e2e_reads // (2 if pe else 1), n_units), L, args.max_subs, lambda *a: log(rank, *a), pe=pe)
         if args.f2f_reads > 0 and hasattr(engine, "file_to_file"):
@@ -766,6 +825,7 @@ def run(args, engine):
             "vs_baseline": None,
             "dtype": "u64",
             "data": "synthetic",
+            "full": args.full,
             "config": {
                 "workload": ("%s: %d x %s%d bp %s per GPU vs %.2f Gbp synthetic genome (%d x %d bp%s), kalign -s%d%s"
                              % (args.workload.upper(), n_units, "2x" if pe else "", L, "pairs" if pe else "SE reads",

@@ -13,7 +13,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--steps", "2", "--warmup", "1", "--workload", "c1", "--chroms", "2", "--chrom-mbp", "0.03",
-        "--reads", "500", "--max-subs", "2"]
+        "--reads", "500", "--max-subs", "2", "--full"]  # (--full: the truth-property check below)
 
 WORKER = textwrap.dedent(
     """

@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 import synth
-from oracle_bindings import (EXT_CHIMERIC, EXT_INDEL, EXT_INSERT, EXT_SPLICE, NAR_ACCEPTED, NAR_MICROINDEL, NAR_SPLICEJCTN,
-                             NAR_TRIM, Oracle, Ref, ext_trims, ref_available)
+from oracle_bindings import (EXT_CHIMERIC, EXT_INDEL, EXT_INSERT, EXT_SPLICE, HIT_DTYPE, NAR_ACCEPTED, NAR_MICROINDEL,
+                             NAR_SPLICEJCTN, NAR_TRIM, Oracle, Ref, ext_trims, ref_available)
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = sorted(os.path.basename(p)[10:-4] for p in glob.glob(os.path.join(GOLDEN, "align_ext_*.npz")))
@@ -157,22 +157,12 @@ def test_post_stages_known_answers(oracle, g3_path, golden_dir):
     oracle.close(h)
 
 
-@pytest.mark.parametrize("window,seed", [(400, 1), (900, 2), (1500, 3), (6000, 4)])
-def test_chimeric_mate_rescue_vs_live_reference(oracle, golden_dir, window, seed):
-    """CSfxArray::AlignPairedRead with MinChimericLen (SfxArray.cpp:8571-8767): both branches -- the linear scan below 1000 loci and
-    the exact-core seeds of IterateExactsRange above -- on mates whose flanks are foreign sequence, placed relative to made-up
-    anchors on the golden genome; oracle vs the live reference (oracle/_ref/libk4ref.so; skipped where it is not built)."""
-    from oracle_bindings import Ref, ref_available
+RESCUE_GOLDEN = "mate_rescue_x_reference.json.xz"  # "<window>_<seed>" -> per call: [sha256 of the arguments, rslt, hit bytes (hex)]
 
-    if not ref_available():
-        pytest.skip("oracle/_ref/libk4ref.so is not built here")
-    names, chroms = synth.golden_genome()
+
+def rescue_calls(chroms, window, seed):
+    """the arguments of the AlignPairedRead calls of one (window, seed) case"""
     rng = np.random.default_rng(900 + seed)
-    R = Ref()
-    path = os.path.join(golden_dir, "g1.sfx")
-    hr = R.open(path)
-    ho = oracle.open(path)
-    n_placed = n_chim = 0
     for t in range(140):
         c = int(rng.integers(0, 3))
         g = chroms[c]
@@ -206,8 +196,42 @@ def test_chimeric_mate_rescue_vs_live_reference(oracle, golden_dir, window, seed
         max_mm = int(rng.choice([2, 3, 5]))
         core_len = max(8, L // (max_mm + 1))
         core_delta = max(L // 10 - 1, core_len)
-        args = (b3, anti, c + 1, a_start, a_end, 50, window + L, max_mm, mate, mcl, core_len, core_delta)
-        r_ref, h_ref = R.align_paired_read_x(hr, *args)
+        yield t, (b3, anti, c + 1, a_start, a_end, 50, window + L, max_mm, mate, mcl, core_len, core_delta)
+
+
+def rescue_args_digest(args):
+    import hashlib
+
+    return hashlib.sha256(repr(args[:8] + args[9:]).encode() + np.ascontiguousarray(args[8], dtype=np.uint8).tobytes()).hexdigest()
+
+
+@pytest.mark.parametrize("window,seed", [(400, 1), (900, 2), (1500, 3), (6000, 4)])
+def test_chimeric_mate_rescue_vs_live_reference(oracle, golden_dir, window, seed):
+    """CSfxArray::AlignPairedRead with MinChimericLen (SfxArray.cpp:8571-8767): both branches -- the linear scan below 1000 loci and
+    the exact-core seeds of IterateExactsRange above -- on mates whose flanks are foreign sequence, placed relative to made-up
+    anchors on the golden genome; oracle vs the live reference (oracle/_ref/libk4ref.so), or where that is not built, vs what the
+    reference returned for the same calls (tests/golden/mate_rescue_x_reference.json.xz, tests/golden/make_golden_mate_rescue.py)."""
+    import json
+    import lzma
+
+    names, chroms = synth.golden_genome()
+    path = os.path.join(golden_dir, "g1.sfx")
+    live = ref_available()
+    if live:
+        R = Ref()
+        hr = R.open(path)
+    else:
+        with lzma.open(os.path.join(golden_dir, RESCUE_GOLDEN), "rt") as f:
+            stored = iter(json.load(f)["%d_%d" % (window, seed)])
+    ho = oracle.open(path)
+    n_placed = n_chim = 0
+    for t, args in rescue_calls(chroms, window, seed):
+        if live:
+            r_ref, h_ref = R.align_paired_read_x(hr, *args)
+        else:
+            digest, r_ref, h_hex = next(stored)
+            assert digest == rescue_args_digest(args), t
+            h_ref = np.frombuffer(bytes.fromhex(h_hex), dtype=HIT_DTYPE)[0]
         r_o, h_o = oracle.align_paired_read_x(ho, *args)
         assert r_ref == r_o, (t, r_ref, r_o, args[:8])
         if r_ref == 1:
@@ -215,5 +239,8 @@ def test_chimeric_mate_rescue_vs_live_reference(oracle, golden_dir, window, seed
             n_placed += 1
             n_chim += int((int(h_o["reserved"]) >> 24) & 1)
     assert n_placed > 60 and n_chim > 15
-    R.close(hr)
+    if live:
+        R.close(hr)
+    else:
+        assert next(stored, None) is None
     oracle.close(ho)

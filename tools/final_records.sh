@@ -12,7 +12,7 @@ for W in "$@"; do
     rep_c50) A="--workload rep --ext c50 --ref-sample 2000000 --cpu-sample 2000000";;
     c1) A="--workload c1 --f2f-reads 0 --e2e-reads 0";;
   esac
-  timeout -k 10 900 python3 bench.py $A > $O/bench_$W.json 2> $O/bench_$W.log || { echo "$W failed"; tail -5 $O/bench_$W.log; }
+  timeout -k 10 900 python3 bench.py --full $A > $O/bench_$W.json 2> $O/bench_$W.log || { echo "$W failed"; tail -5 $O/bench_$W.log; }
   python3 -c "
 import json
 d=json.load(open('$O/bench_$W.json')); r=d['roofline']; c=d.get('cpu_baseline') or {}

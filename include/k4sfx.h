@@ -49,7 +49,8 @@ enum { K4_HR_NONE = 0, K4_HR_HITS = 1, K4_HR_MMDELTA = 2, K4_HR_HITINSTS = 3, K4
 enum { K4_STRAND_BOTH = 0, K4_STRAND_WATSON = 1, K4_STRAND_CRICK = 2 };
 /* eNAR values AlignRead can assign, ngskit4b/KAligner.h:136-158 */
 enum { K4_NAR_UNALIGNED = 0, K4_NAR_ACCEPTED = 1, K4_NAR_NS = 2, K4_NAR_NOHIT = 3, K4_NAR_MMDELTA = 4,
-       K4_NAR_MULTIALIGN = 5, K4_NAR_TRIM = 6, K4_NAR_SPLICEJCTN = 7, K4_NAR_MICROINDEL = 8 };
+       K4_NAR_MULTIALIGN = 5, K4_NAR_TRIM = 6, K4_NAR_SPLICEJCTN = 7, K4_NAR_MICROINDEL = 8,
+       K4_NAR_PCRDUP = 9 /* eNARPCRdup: removed as a potential PCR artefact (k4_reduce_pcr_dups_dev) */ };
 
 typedef struct k4_index k4_index; /* opaque: the HBM-resident index (replaces a loaded CSfxArray) */
 
@@ -271,6 +272,13 @@ int k4_auto_trim_flanks_dev(k4_index* ix, int32_t min_flank_exacts, int pe, int6
                             void* stream);
 int k4_remove_orphan_juncts_dev(k4_index* ix, uint32_t which, int64_t n_reads, int32_t max_ml, void* d_rr, void* d_hits,
                                 const void* d_seg2, int64_t* n_removed, void* stream);
+/* k4_reduce_pcr_dups_dev <- CKAligner::ReducePCRduplicates (KAligner.cpp:2303-2400; `kalign -k <win_len>`, 0..250, SE only):
+ *                           for each accepted read's (chrom, AdjStartLoci, AdjHitLen, strand) stack, ranked by low_mm then load
+ *                           order, the reads behind the stack's limit become K4_NAR_PCRDUP with num_hits = inst = 0.  The limit is
+ *                           1..50 by the distinct same-strand start sites within win_len up- or downstream (NumUpUniques /
+ *                           NumDnUniques), 0 for win_len 0.  Waits for `stream` and returns the count in *n_dups. */
+int k4_reduce_pcr_dups_dev(k4_index* ix, int32_t win_len, int64_t n_reads, int32_t max_ml, void* d_rr, void* d_hits, int64_t* n_dups,
+                           void* stream);
 /* k4_best_matches_batch <- CSfxArray::LocateBestMatches (SfxArray.h:793, SfxArray.cpp:6836-7205; CKAligner's `-N`) for
  * n_reads reads: at most p->max_hits alignments with no more than p->tot_mm mismatches, sorted by mismatches; rslt = the
  * call's return value (0 none, 1..max_hits, max_hits+1 when further matches were sloughed), inst = alignments in the

@@ -31,7 +31,7 @@ SEG2_DTYPE = np.dtype(
     [("chrom_id", "<u4"), ("match_loci", "<u4"), ("match_len", "<u2"), ("read_ofs", "<u2"), ("mismatches", "u1"),
      ("reserved", "u1"), ("score", "<u2")]
 )
-NAR_TRIM, NAR_SPLICEJCTN, NAR_MICROINDEL = 6, 7, 8
+NAR_TRIM, NAR_SPLICEJCTN, NAR_MICROINDEL, NAR_PCRDUP = 6, 7, 8, 9
 
 
 class K4Error(RuntimeError):
@@ -125,7 +125,7 @@ ABI_SYMBOLS = [
     "k4_copy_to_device", "k4_copy_to_host", "k4_upload_pageable", "k4_host_register", "k4_host_unregister", "k4_best_matches_batch", "k4_best_matches_batch_dev",
     "k4_get_sfx_header", "k4_set_description", "k4_select_hits_dev",
     "k4_assign_multi_dev", "k4_align_reads_ext_batch", "k4_align_reads_ext_batch_dev", "k4_kalign_ext_batch",
-    "k4_kalign_ext_batch_dev", "k4_auto_trim_flanks_dev", "k4_remove_orphan_juncts_dev", "k4_format_sam_ext_dev",
+    "k4_kalign_ext_batch_dev", "k4_auto_trim_flanks_dev", "k4_remove_orphan_juncts_dev", "k4_reduce_pcr_dups_dev", "k4_format_sam_ext_dev",
     "k4_pipeline_open", "k4_pipeline_acquire", "k4_pipeline_submit", "k4_pipeline_submit_host", "k4_pipeline_wait_aligned",
     "k4_pipeline_format", "k4_pipeline_next_sam", "k4_pipeline_read_sam", "k4_pipeline_close", "k4_sfx_map", "k4_sfx_unmap",
     "k4_set_raw_header",
@@ -202,6 +202,7 @@ def lib():
     L.k4_kalign_ext_batch_dev.argtypes = [vp, C.POINTER(KalignParams), i64, C.c_int32] + [vp] * 7
     L.k4_auto_trim_flanks_dev.argtypes = [vp, C.c_int32, i32, i64, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(C.c_int64), vp]
     L.k4_remove_orphan_juncts_dev.argtypes = [vp, u32, i64, C.c_int32, vp, vp, vp, C.POINTER(C.c_int64), vp]
+    L.k4_reduce_pcr_dups_dev.argtypes = [vp, C.c_int32, i64, C.c_int32, vp, vp, C.POINTER(C.c_int64), vp]
     L.k4_format_sam_ext_dev.argtypes = [vp, i32, i64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(SamNames), C.POINTER(vp),
                                         C.POINTER(u64), C.POINTER(SamStats), vp, vp]
     L.k4_format_bam_dev.argtypes = [vp, i32, i64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(SamNames), C.c_int32, C.POINTER(vp),
@@ -677,6 +678,14 @@ class SfxIndex:
                                                            d_seg2.data_ptr(), C.byref(c), 0))
                 cnt[key] = c.value
         return (d_rr.cpu().numpy().view(RESULT_DTYPE), d_hits.cpu().numpy().view(HIT_DTYPE).reshape(n, max_ml), cnt)
+
+    def reduce_pcr_dups(self, win_len, n, max_ml, d_rr, d_hits, stream=0):
+        """ReducePCRduplicates (`kalign -k`, KAligner.cpp:2303-2400) in place over device arrays of SE results: d_rr (n k4_read_result
+        records) and d_hits (n * max_ml k4_hit slots), torch tensors or device addresses; returns the number of reads marked NAR_PCRDUP."""
+        c = C.c_int64(0)
+        ptr = lambda a: a if isinstance(a, int) else a.data_ptr()  # noqa: E731
+        self._ck(lib().k4_reduce_pcr_dups_dev(self.h, int(win_len), int(n), int(max_ml), ptr(d_rr), ptr(d_hits), C.byref(c), stream))
+        return c.value
 
     def pipeline_sam(self, texts, kp, pe=None, min_len=50, max_len=500, chunk_bytes=0, ring=False, out=None, min_batch_units=0, all_reads=False, expect=True):
         """host text (bytes-like / pinned tensors: one for SE, two for PE) -> SAM body through the overlapped pipeline.

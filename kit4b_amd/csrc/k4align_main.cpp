@@ -10,7 +10,8 @@
 //   statistics           CKAligner::ReportAlignStats :3600-3830 (NAR histogram, strand counts)
 //   SAM                  CKAligner::WriteBAMReadHits :5718-5914, ReportBAMread :5957-6320, SortHitMatch :10969,
 //                        CSAMfile::AddAlignment libkit4b/SAMfile.cpp:2194-2377 -> k4_format_sam_dev; header :1615,1667-1669,1799
-// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x (plus -g <gpu>, -S <i/N> read slice).
+//   PCR duplicates (-k)  CKAligner::ReducePCRduplicates :2303-2400                -> k4_reduce_pcr_dups_dev
+// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k (plus -g <gpu>, -S <i/N> read slice).
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -48,6 +49,8 @@ struct Opts {
   bool clamp = false, best = false; // -X / -N (KAlignerCL.cpp:278-280)
   int q_method = 3;  // -g (etFQMethod, KAlignerCL.cpp:241,499): 3 = the quality lines are ignored
   int min_chimeric = 0, micro_indel = 0, splice_junct = 0, min_flank_exacts = 0;  // -c / -a / -A / -x (KAlignerCL.cpp:237,245,246,267)
+  int pcr_win = -1;                 // -k <0..250>: PCR artefact reduction window (KAlignerCL.cpp:222,738-743); -1 = off
+  bool pcr_given = false;           // (an explicit -k-1 is turned down like any value outside 0..250)
   double batch_mb = 0;              // -b <MB>: stream the input, this much text per file per batch (0: the whole input at once)
   int shard = 0, n_shards = 1;      // -S i/N: this process aligns the i-th of N contiguous slices of the reads (one process per GPU)
   int gpu = 0;
@@ -527,7 +530,7 @@ const char* kNarAbbr[20] = {"NA", "AA", "EN", "NL", "MH", "ML", "ET", "OJ", "OM"
 void usage() {
   fprintf(stderr,
           "k4align -i reads.f[aq][.gz] [-i more ...] [-u mates ...] -I index.sfx -o out.sam|out.bam [-z bgzf level=6] [-s subs/100bp=5] [-e 1|2] [-m 0..3] [-n maxNs=1]\n"
-          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
+          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
 }
 
 }  // namespace
@@ -672,8 +675,12 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
         k4_free_device(d_choice);
       }
     }
-    // the filters, in CKAligner::Align's order (KAligner.cpp:653-686)
     int64_t cnt = 0;
+    if (!pe && o.pcr_win >= 0) {  // ReducePCRduplicates, behind AssignMultiMatches and before the filters (KAligner.cpp:628-640)
+      CK(k4_reduce_pcr_dups_dev(ix, o.pcr_win, n, max_ml, d_rr, d_hits, &cnt, nullptr));
+      fprintf(stderr, "k4align: %lld potential PCR artefact reads removed\n", (long long)cnt);
+    }
+    // the filters, in CKAligner::Align's order (KAligner.cpp:653-686)
     if (o.min_flank_exacts > 0) {
       CK(k4_auto_trim_flanks_dev(ix, o.min_flank_exacts, pe ? 1 : 0, pe ? 2 * n : n, max_ml, pe ? d_pe : d_rr, d_hits, d_reads, d_offs,
                                  d_lens, &cnt, nullptr));
@@ -1348,6 +1355,7 @@ int main(int argc, char** argv) {
       case 'a': o.micro_indel = atoi(val().c_str()); break;
       case 'A': o.splice_junct = atoi(val().c_str()); break;
       case 'x': o.min_flank_exacts = atoi(val().c_str()); break;
+      case 'k': o.pcr_win = atoi(val().c_str()); o.pcr_given = true; break;
       case 'p': o.min_snp_reads = atoi(val().c_str()); break;
       case 'P': o.qvalue = atof(val().c_str()); break;
       case '1': o.snp_nonref_pcnt = atof(val().c_str()); break;
@@ -1423,6 +1431,18 @@ int main(int argc, char** argv) {
   if (o.min_chimeric != 0 && (o.min_chimeric < 15 || o.min_chimeric > 99)) { fprintf(stderr, "k4align: minimum chimeric length percentage '-c%d' specified outside of range 15..99\n", o.min_chimeric); return 1; }
   if (o.micro_indel < 0 || o.micro_indel > 20) { fprintf(stderr, "k4align: microInDel length maximum '-a%d' specified outside of range 0..20\n", o.micro_indel); return 1; }
   if (o.splice_junct != 0 && (o.splice_junct < 25 || o.splice_junct > 100000)) { fprintf(stderr, "k4align: RNAseq maximum splice junction separation '-A%d' must be either 0 or in the range 25..100000\n", o.splice_junct); return 1; }
+  if (o.pcr_given && (o.pcr_win < 0 || o.pcr_win > 250)) {
+    fprintf(stderr, "k4align: PCR differential amplification artefacts window length '-k%d' specified outside of range 0..250\n", o.pcr_win);
+    return 1;
+  }
+  // ReducePCRduplicates runs for SE only (KAligner.cpp:628); with -u the option is accepted and does nothing
+  if (o.pcr_win >= 0 && !pe) {
+    if (o.batch_mb > 0 || o.n_shards > 1 || !o.gpus.empty()) {
+      fprintf(stderr, "k4align: -k reduces PCR duplicates over all reads of the run; it cannot be combined with -b, -S or -G\n");
+      return 1;
+    }
+    if (o.ml_mode == 5) { fprintf(stderr, "k4align: PCR artefact reduction '-k' with every multiloci alignment reported '-r5' is not built\n"); return 3; }
+  }
   if (o.q_method < 0 || o.q_method > 3) { fprintf(stderr, "k4align: fastq quality '-g%d' specified outside of range 0..3\n", o.q_method); return 1; }
   if (o.min_flank_exacts < 0 || o.min_flank_exacts > 7) { fprintf(stderr, "k4align: max flank trimming '-x%d' specified outside of range 0..7\n", o.min_flank_exacts); return 1; }
   if (pe && (o.micro_indel || o.splice_junct)) { fprintf(stderr, "k4align: microInDel '-a' / splice junction '-A' processing not supported in paired end processing\n"); return 1; }

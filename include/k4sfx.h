@@ -279,6 +279,47 @@ int k4_remove_orphan_juncts_dev(k4_index* ix, uint32_t which, int64_t n_reads, i
  *                           NumDnUniques), 0 for win_len 0.  Waits for `stream` and returns the count in *n_dups. */
 int k4_reduce_pcr_dups_dev(k4_index* ix, int32_t win_len, int64_t n_reads, int32_t max_ml, void* d_rr, void* d_hits, int64_t* n_dups,
                            void* stream);
+/* ---- alignment statistics (`kalign -O <file>`; kit4b_amd/csrc/k4_stats.hip) -------------------------------------------------
+ * k4_align_stats_collect <- m_MultiHitDist (KAligner.cpp:9943) and m_pLenDist (:3251, :3408, :3511): on = 1 zeroes two tallies on the
+ *                           device which every later k4_kalign_*_batch_dev / k4_kalign_pe_batch_dev call (a pipeline's too) adds
+ *                           to: LowHitInstances of the reads AlignRead accepts, and the fragment length of every pair accepted as
+ *                           such or through a rescued mate.  on = 0 drops them; off, the align calls do nothing new.
+ * k4_align_stats_dev     <- CKAligner::WriteSubDist (:6469-6525) and the counting of ReportTargHitCnts (:5458-5712) over the
+ *                           records in HBM as the last global stage left them: n_reads reads (PE: both ends, d_pe; SE: d_rr and
+ *                           hit slot 0 of d_hits); max_read_len bounds lens[] and is the row length of the position tables.  The
+ *                           quality band of a base is read from bits 4..7 of its read byte, where k4_set_fastq_quality's parse put
+ *                           the 4-bit score (all 0, band 0, under -g3).  Fills *out, the run tallies included (zero when they
+ *                           were not collected); waits for `stream`.  Release with k4_free_align_stats.
+ * k4_write_align_stats   <- the text: WriteBasicCountStats (:4159-4300) into `path` (left empty when no read was accepted),
+ *                           ReportTargHitCnts into <path cut at its last '.'>.AlignCntsDist.csv (only when a read was accepted),
+ *                           and with pe != 0 <..>.GlobalPEInsertDist.csv (:3092-3146).  n_loaded: the reads behind the length
+ *                           filter (RPKM); ml_mode / max_multi: kalign -r / -R (the multihit block is written for -r > 0). */
+#define K4_STATS_MULTI 500      /* cMaxMultiHits, KAligner.h:80 */
+#define K4_STATS_PE_LEN 100000  /* cPairMaxLen, KAligner.h:88 */
+typedef struct {
+  uint32_t max_align_len;       /* m_MaxAlignLen: the longest accepted one-segment read */
+  uint32_t len_stride;          /* L: row length of q_insts / q_subs (the call's max_read_len) */
+  uint32_t n_entries;
+  uint32_t reserved;
+  uint64_t n_accepted;          /* accepted reads (ReportTargHitCnts counts these, two-segment reads included) */
+  uint64_t* q_insts;            /* [4][L] m_AlignQSubDist[band][pos].QInsts */
+  uint64_t* q_subs;             /* [4][L] .Subs */
+  uint64_t* m_sub;              /* [L + 1] m_AlignMSubDist */
+  uint64_t* multi_hit;          /* [K4_STATS_MULTI] m_MultiHitDist */
+  uint64_t* pe_len_dist;        /* [K4_STATS_PE_LEN + 1] m_pLenDist */
+  uint32_t* ent_hits;           /* [n_entries] accepted alignments per target, by entry order */
+  uint32_t* ent_uniq_loci;      /* [n_entries] distinct AdjAlignStartLoci */
+  uint32_t* ent_indeterminate;  /* [n_entries] reads whose first three bases hold a non-ACGT */
+  uint32_t* ent_trimer;         /* [n_entries][64] reads by their first three bases (A=0 .. T=3, first base most significant) */
+  void* block;                  /* the one allocation behind the arrays */
+} k4_align_stats;
+int k4_align_stats_collect(k4_index* ix, int on);
+int k4_align_stats_dev(k4_index* ix, int pe, int64_t n_reads, int32_t max_ml, int32_t max_read_len, const void* d_rr,
+                       const void* d_hits, const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens,
+                       k4_align_stats* out, void* stream);
+void k4_free_align_stats(k4_align_stats* s);
+int k4_write_align_stats(k4_index* ix, const k4_align_stats* s, uint64_t n_loaded, int32_t ml_mode, int32_t max_multi, int pe,
+                         const char* path);
 /* k4_best_matches_batch <- CSfxArray::LocateBestMatches (SfxArray.h:793, SfxArray.cpp:6836-7205; CKAligner's `-N`) for
  * n_reads reads: at most p->max_hits alignments with no more than p->tot_mm mismatches, sorted by mismatches; rslt = the
  * call's return value (0 none, 1..max_hits, max_hits+1 when further matches were sloughed), inst = alignments in the
@@ -511,6 +552,8 @@ int k4_pipeline_submit(k4_pipeline* pl, int end, uint64_t bytes, int final_chunk
 /* text in the caller's own memory (pinned for the full PCIe rate); it must stay valid until k4_pipeline_wait_aligned returns */
 int k4_pipeline_submit_host(k4_pipeline* pl, int end, const void* text, uint64_t bytes, int final_chunk);
 int k4_pipeline_wait_aligned(k4_pipeline* pl, k4_pipeline_view* view); /* after the final chunks: every read is aligned */
+/* k4_align_stats_dev over the pipeline's own arrays; call it behind the last global stage and before k4_pipeline_format* */
+int k4_pipeline_align_stats(k4_pipeline* pl, k4_align_stats* out);
 int k4_pipeline_format(k4_pipeline* pl, k4_sam_stats* stats, uint8_t* chrom_hit /* host, n_entries + 1, or NULL */, uint64_t* sam_bytes);
 /* ... as BAM records (k4_format_bam_dev); the pieces come down through k4_pipeline_next_sam / k4_pipeline_read_sam all the same */
 int k4_pipeline_format_bam(k4_pipeline* pl, int32_t sq_all, k4_sam_stats* stats, uint8_t* chrom_hit, uint64_t* bam_bytes);

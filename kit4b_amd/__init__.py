@@ -107,6 +107,17 @@ class PipelineView(C.Structure):
                 ("d_lens", C.c_void_p), ("names", SamNames)]
 
 
+class AlignStats(C.Structure):  # k4_align_stats
+    _fields_ = [("max_align_len", C.c_uint32), ("len_stride", C.c_uint32), ("n_entries", C.c_uint32), ("reserved", C.c_uint32),
+                ("n_accepted", C.c_uint64), ("q_insts", C.POINTER(C.c_uint64)), ("q_subs", C.POINTER(C.c_uint64)),
+                ("m_sub", C.POINTER(C.c_uint64)), ("multi_hit", C.POINTER(C.c_uint64)), ("pe_len_dist", C.POINTER(C.c_uint64)),
+                ("ent_hits", C.POINTER(C.c_uint32)), ("ent_uniq_loci", C.POINTER(C.c_uint32)),
+                ("ent_indeterminate", C.POINTER(C.c_uint32)), ("ent_trimer", C.POINTER(C.c_uint32)), ("block", C.c_void_p)]
+
+
+STATS_MULTI, STATS_PE_LEN = 500, 100000
+
+
 class Counters(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_lookup", C.c_uint64), ("n_probe", C.c_uint64), ("n_cand", C.c_uint64),
                 ("n_slow", C.c_uint64), ("n_bases", C.c_uint64)]
@@ -128,7 +139,8 @@ ABI_SYMBOLS = [
     "k4_kalign_ext_batch_dev", "k4_auto_trim_flanks_dev", "k4_remove_orphan_juncts_dev", "k4_reduce_pcr_dups_dev", "k4_format_sam_ext_dev",
     "k4_pipeline_open", "k4_pipeline_acquire", "k4_pipeline_submit", "k4_pipeline_submit_host", "k4_pipeline_wait_aligned",
     "k4_pipeline_format", "k4_pipeline_next_sam", "k4_pipeline_read_sam", "k4_pipeline_close", "k4_sfx_map", "k4_sfx_unmap",
-    "k4_set_raw_header",
+    "k4_set_raw_header", "k4_align_stats_collect", "k4_align_stats_dev", "k4_free_align_stats", "k4_write_align_stats",
+    "k4_pipeline_align_stats",
 ]
 
 
@@ -203,6 +215,12 @@ def lib():
     L.k4_auto_trim_flanks_dev.argtypes = [vp, C.c_int32, i32, i64, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(C.c_int64), vp]
     L.k4_remove_orphan_juncts_dev.argtypes = [vp, u32, i64, C.c_int32, vp, vp, vp, C.POINTER(C.c_int64), vp]
     L.k4_reduce_pcr_dups_dev.argtypes = [vp, C.c_int32, i64, C.c_int32, vp, vp, C.POINTER(C.c_int64), vp]
+    L.k4_align_stats_collect.argtypes = [vp, i32]
+    L.k4_align_stats_dev.argtypes = [vp, i32, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, C.POINTER(AlignStats), vp]
+    L.k4_free_align_stats.argtypes = [C.POINTER(AlignStats)]
+    L.k4_free_align_stats.restype = None
+    L.k4_write_align_stats.argtypes = [vp, C.POINTER(AlignStats), u64, C.c_int32, C.c_int32, i32, C.c_char_p]
+    L.k4_pipeline_align_stats.argtypes = [vp, C.POINTER(AlignStats)]
     L.k4_format_sam_ext_dev.argtypes = [vp, i32, i64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(SamNames), C.POINTER(vp),
                                         C.POINTER(u64), C.POINTER(SamStats), vp, vp]
     L.k4_format_bam_dev.argtypes = [vp, i32, i64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(SamNames), C.c_int32, C.POINTER(vp),
@@ -686,6 +704,37 @@ class SfxIndex:
         ptr = lambda a: a if isinstance(a, int) else a.data_ptr()  # noqa: E731
         self._ck(lib().k4_reduce_pcr_dups_dev(self.h, int(win_len), int(n), int(max_ml), ptr(d_rr), ptr(d_hits), C.byref(c), stream))
         return c.value
+
+    def align_stats_collect(self, on=True):
+        """Start (zero) or drop the run tallies of `kalign -O` that the align calls add to: the multihit distribution and the PE insert lengths."""
+        self._ck(lib().k4_align_stats_collect(self.h, 1 if on else 0))
+
+    def align_stats(self, n, max_ml, max_read_len, d_reads, d_offs, d_lens, d_rr=None, d_hits=None, d_pe=None, stream=0, write=None):
+        """The counts behind `kalign -O` (WriteSubDist, ReportTargHitCnts; KAligner.cpp:6469-6525, 5458-5712) over n reads in device arrays
+        (torch tensors or addresses): SE d_rr + d_hits (n * max_ml slots), or PE d_pe (n = both ends).  Returns numpy arrays: q_insts /
+        q_subs [4, max_read_len], m_sub [max_read_len + 1], multi_hit [500], pe_len_dist [100001], ent_hits / ent_uniq_loci /
+        ent_indeterminate [n_entries], ent_trimer [n_entries, 64], and max_align_len, n_accepted.  write = (path, n_loaded, ml_mode,
+        max_multi): also print the files."""
+        ptr = lambda a: None if a is None else a if isinstance(a, int) else a.data_ptr()  # noqa: E731
+        st = AlignStats()
+        pe = d_pe is not None
+        self._ck(lib().k4_align_stats_dev(self.h, 1 if pe else 0, int(n), int(max_ml), int(max_read_len), ptr(d_rr), ptr(d_hits), ptr(d_pe),
+                                          ptr(d_reads), ptr(d_offs), ptr(d_lens), C.byref(st), stream))
+        try:
+            if write is not None:
+                path, n_loaded, ml_mode, max_multi = write
+                self._ck(lib().k4_write_align_stats(self.h, C.byref(st), int(n_loaded), int(ml_mode), int(max_multi), 1 if pe else 0,
+                                                    os.fsencode(path)))
+            L, ne = st.len_stride, st.n_entries
+            arr = lambda p, k, dt: np.ctypeslib.as_array(p, shape=(k,)).astype(dt).copy() if k else np.zeros(0, dt)  # noqa: E731
+            return {"max_align_len": int(st.max_align_len), "n_accepted": int(st.n_accepted),
+                    "q_insts": arr(st.q_insts, 4 * L, np.uint64).reshape(4, L), "q_subs": arr(st.q_subs, 4 * L, np.uint64).reshape(4, L),
+                    "m_sub": arr(st.m_sub, L + 1, np.uint64), "multi_hit": arr(st.multi_hit, STATS_MULTI, np.uint64),
+                    "pe_len_dist": arr(st.pe_len_dist, STATS_PE_LEN + 1, np.uint64), "ent_hits": arr(st.ent_hits, ne, np.uint32),
+                    "ent_uniq_loci": arr(st.ent_uniq_loci, ne, np.uint32), "ent_indeterminate": arr(st.ent_indeterminate, ne, np.uint32),
+                    "ent_trimer": arr(st.ent_trimer, ne * 64, np.uint32).reshape(ne, 64)}
+        finally:
+            lib().k4_free_align_stats(C.byref(st))
 
     def pipeline_sam(self, texts, kp, pe=None, min_len=50, max_len=500, chunk_bytes=0, ring=False, out=None, min_batch_units=0, all_reads=False, expect=True):
         """host text (bytes-like / pinned tensors: one for SE, two for PE) -> SAM body through the overlapped pipeline.

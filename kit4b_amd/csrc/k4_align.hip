@@ -906,7 +906,12 @@ static int kalign_dev(k4_index* ix, const k4_kalign_params* p, int64_t n, int32_
   a.rr = (k4_read_result*)d_out; a.hits = (k4_hit*)d_hits; a.max_hits = a.kp.max_ml;
   a.seg2 = (k4_seg2*)d_seg2;
   a.sparse_hits = sparse_hits;
-  return run_dev(ix, a, max_len, stream);
+  rc = run_dev(ix, a, max_len, stream);
+  // m_MultiHitDist (KAligner.cpp:9943), only while the `-O` tallies are on.  (pe_mode 2 is also how `-r2` gets every instance
+  // before one is drawn, so it is tallied; under a real eMLall the reference leaves the switch at :9913-9931 without
+  // tallying -- `k4align -O -r5` is turned down)
+  if (rc == K4_OK && ix->d_run_stats) rc = k4i_stats_tally_multi(ix, d_out, n, stream);
+  return rc;
 }
 
 // ---- host-pointer entry points: stage through the index's own buffers and stream -------------------------------

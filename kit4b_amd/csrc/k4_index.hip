@@ -858,6 +858,7 @@ extern "C" void k4_close(k4_index* ix) {
   for (void* p : ptrs)
     if (p) hipFree(p);
   if (ix->d_qlut) hipFree(ix->d_qlut);
+  if (ix->d_run_stats) hipFree(ix->d_run_stats);
   if (w.d_small) hipFree(w.d_small);
   if (w.h_small) hipHostFree(w.h_small);
   for (void* p : {(void*)ix->pe_rr, (void*)ix->pe_hits, (void*)ix->pe_list, (void*)ix->pe_ctl, ix->rs_tasks, ix->rs_reads, ix->rs_res, ix->rs_hits})

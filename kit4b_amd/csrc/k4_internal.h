@@ -109,6 +109,9 @@ struct k4_index {
   // scaled 4-bit score of every base into bits 4..7 of its read byte (the reference's own in-memory form), the SAM / BAM writers emit it
   int q_method = 3;
   uint8_t* d_qlut = nullptr;    // 256 bytes: quality character -> 4-bit score of the chosen method
+  // `kalign -O` run tallies (k4_align_stats_collect, k4_stats.hip): K4_STATS_MULTI multihit bins, then K4_STATS_PE_LEN + 1 insert lengths;
+  // null = not collected (the align and pairing kernels then do nothing more than before)
+  unsigned long long* d_run_stats = nullptr;
   double deep_bucket_frac = 0;  // share of the suffixes that sit in k-mer buckets deeper than K4_DEEP_BUCKET (k4_index.hip)
   std::vector<k4_entry> entries;
   std::string dataset;
@@ -149,6 +152,9 @@ int k4i_build_device_structures(k4_index* ix, const void* d_seq_bytes, int kmer_
 #define K4_SMALL_READS 4096
 int k4i_kalign_batch_dev(k4_index* ix, const k4_kalign_params* p, int64_t n, int32_t max_len, const void* d_reads,
                          const void* d_offs, const void* d_lens, void* d_out, void* d_hits, void* stream, int sparse_hits);
+// k4_stats.hip: the run tallies of `kalign -O` (no-ops while k4_align_stats_collect is off)
+int k4i_stats_tally_multi(k4_index* ix, const void* d_rr, int64_t n, void* stream);
+unsigned long long* k4i_stats_pe_len_dist(k4_index* ix);
 // k4_sabuild.hip
 int k4i_build_sa(uint64_t n, uint32_t el, const uint8_t* d_seq, uint8_t* d_sa, int device, std::string* err);
 

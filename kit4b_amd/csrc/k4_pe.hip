@@ -419,7 +419,8 @@ K4_DEV void k4d_pe_leftover(const k4_pe_params& pe, k4_pe_read& f, k4_pe_read& r
 // and ProcessPairedEnds (:3207-3318) up to the point where a mate rescue is needed; pairs that need one are listed.
 __global__ void __launch_bounds__(256) k4k_pe_pair(k4_pe_params pe, int64_t n_pairs, int mh, const k4_read_result* __restrict__ rr,
                                                    const k4_hit* __restrict__ hits, k4_pe_read* __restrict__ out,
-                                                   uint32_t* __restrict__ orphans, uint32_t* __restrict__ ctl) {
+                                                   uint32_t* __restrict__ orphans, uint32_t* __restrict__ ctl,
+                                                   unsigned long long* __restrict__ len_dist) {
   // The block's 256 pairs read 12 KB of results and write 20 KB of records, both contiguous: they pass through LDS in 16-byte
   // pieces, a lane per piece (a thread copying its own 48 / 80 bytes touches forty lines per wave instruction: 4.4 ms per 50 M
   // pairs before, half the step time of a paired-end batch's last phase)
@@ -480,8 +481,10 @@ __global__ void __launch_bounds__(256) k4k_pe_pair(k4_pe_params pe, int64_t n_pa
     bool paired = false;
     if (!strict_fail && f.nar == K4_NAR_ACCEPTED && r.nar == K4_NAR_ACCEPTED) {
       const int frag = k4d_accept_prov_pe(pe, f.num_hits, f.hit, r.num_hits, r.hit);
-      if (frag > 0) { f.pe_aligned = r.pe_aligned = 1; paired = true; }
-      else {
+      if (frag > 0) {
+        f.pe_aligned = r.pe_aligned = 1; paired = true;
+        if (len_dist && frag <= K4_STATS_PE_LEN) atomicAdd(&len_dist[frag], 1ull);  // m_pLenDist, KAligner.cpp:3251 (null: `-O` is off)
+      } else {
         switch (frag) {
           case -1: f.nar = r.nar = K4_NAR_PESTRAND; break;
           case -2: f.nar = r.nar = K4_NAR_PECHROM; break;
@@ -521,7 +524,8 @@ __global__ void __launch_bounds__(256) k4k_pe_pair(k4_pe_params pe, int64_t n_pa
 __global__ void __launch_bounds__(64) k4k_pe_orphans(K4DevIndex ix, k4_pe_params pe, int max_subs, const uint8_t* __restrict__ reads,
                                                      const uint64_t* __restrict__ offs, const uint32_t* __restrict__ lens,
                                                      const uint32_t* __restrict__ orphans, k4_pe_read* __restrict__ out,
-                                                     uint32_t* __restrict__ ctl, K4PeChim ch) {
+                                                     uint32_t* __restrict__ ctl, K4PeChim ch,
+                                                     unsigned long long* __restrict__ len_dist) {
   extern __shared__ __attribute__((aligned(8))) uint8_t rs[];
   const int lane = threadIdx.x;
   uint32_t* mk = ch.min_chimeric_len > 0 ? reinterpret_cast<uint32_t*>(rs + K4_RESCUE_LDS) + lane : nullptr;
@@ -571,6 +575,7 @@ __global__ void __launch_bounds__(64) k4k_pe_orphans(K4DevIndex ix, k4_pe_params
       m.hit = h; m.num_hits = 1; m.low_mm = h.mismatches; m.inst = 1; m.rescued = 1;
       f.pe_aligned = r.pe_aligned = 1;
       f.nar = r.nar = K4_NAR_ACCEPTED;
+      if (len_dist && lane == 0 && frag <= K4_STATS_PE_LEN) atomicAdd(&len_dist[frag], 1ull);  // m_pLenDist, KAligner.cpp:3408 / :3511
       done = true;
     }
     if (!done) k4d_pe_leftover(pe, f, r);
@@ -626,7 +631,7 @@ extern "C" int k4_kalign_pe_batch_dev(k4_index* ix, const k4_kalign_params* p, c
   rc = k4i_kalign_batch_dev(ix, &kp, 2 * n_pairs, max_read_len, d_reads, d_offs, d_lens, ix->pe_rr, ix->pe_hits, stream, 1);
   if (rc != K4_OK) return rc;
   hipLaunchKernelGGL(k4k_pe_pair, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, pe, n_pairs, mh, ix->pe_rr,
-                     ix->pe_hits, (k4_pe_read*)d_out, ix->pe_list, ix->pe_ctl);
+                     ix->pe_hits, (k4_pe_read*)d_out, ix->pe_list, ix->pe_ctl, k4i_stats_pe_len_dist(ix));
   if (pe.pe_mode == 1 || pe.pe_mode == 3) {
     K4PeChim ch = {0, 0, 1, p->min_edit_dist};
     if (p->min_chimeric_len > 0) {
@@ -639,7 +644,7 @@ extern "C" int k4_kalign_pe_batch_dev(k4_index* ix, const k4_kalign_params* p, c
     hipLaunchKernelGGL(k4k_pe_orphans, dim3((unsigned)std::min<int64_t>(n_pairs, 256 * 32)), dim3(64),
                        ch.min_chimeric_len > 0 ? K4_RESCUE_LDS_CHIM : K4_RESCUE_LDS, st, ix->d, pe, p->max_subs,
                        (const uint8_t*)d_reads, (const uint64_t*)d_offs, (const uint32_t*)d_lens, ix->pe_list,
-                       (k4_pe_read*)d_out, ix->pe_ctl, ch);
+                       (k4_pe_read*)d_out, ix->pe_ctl, ch, k4i_stats_pe_len_dist(ix));
   }
   K4_HIP(ix, hipGetLastError());
   K4_HIP(ix, hipStreamSynchronize(st));  // (the call's contract, include/k4sfx.h: the stream is waited for)

@@ -11,7 +11,9 @@
 //   SAM                  CKAligner::WriteBAMReadHits :5718-5914, ReportBAMread :5957-6320, SortHitMatch :10969,
 //                        CSAMfile::AddAlignment libkit4b/SAMfile.cpp:2194-2377 -> k4_format_sam_dev; header :1615,1667-1669,1799
 //   PCR duplicates (-k)  CKAligner::ReducePCRduplicates :2303-2400                -> k4_reduce_pcr_dups_dev
-// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k (plus -g <gpu>, -S <i/N> read slice).
+//   statistics files (-O) CKAligner::WriteSubDist :6469-6525, WriteBasicCountStats :4159-4300, ReportTargHitCnts :5458-5712,
+//                        the insert size file of ProcessPairedEnds :3092-3146     -> k4_pipeline_align_stats, k4_write_align_stats
+// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k -O (plus -g <gpu>, -S <i/N> read slice).
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -51,6 +53,7 @@ struct Opts {
   int min_chimeric = 0, micro_indel = 0, splice_junct = 0, min_flank_exacts = 0;  // -c / -a / -A / -x (KAlignerCL.cpp:237,245,246,267)
   int pcr_win = -1;                 // -k <0..250>: PCR artefact reduction window (KAlignerCL.cpp:222,738-743); -1 = off
   bool pcr_given = false;           // (an explicit -k-1 is turned down like any value outside 0..250)
+  std::string stats_file;           // -O <file>: alignment statistics (KAlignerCL.cpp:256) and its two side files
   double batch_mb = 0;              // -b <MB>: stream the input, this much text per file per batch (0: the whole input at once)
   int shard = 0, n_shards = 1;      // -S i/N: this process aligns the i-th of N contiguous slices of the reads (one process per GPU)
   int gpu = 0;
@@ -530,7 +533,7 @@ const char* kNarAbbr[20] = {"NA", "AA", "EN", "NL", "MH", "ML", "ET", "OJ", "OM"
 void usage() {
   fprintf(stderr,
           "k4align -i reads.f[aq][.gz] [-i more ...] [-u mates ...] -I index.sfx -o out.sam|out.bam [-z bgzf level=6] [-s subs/100bp=5] [-e 1|2] [-m 0..3] [-n maxNs=1]\n"
-          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
+          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-O stats.csv] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
 }
 
 }  // namespace
@@ -577,6 +580,16 @@ struct RunGuard {
     }
   }
 };
+
+// <file cut at its last '.'> + suffix (CUtility::AppendFileNameSuffix), as k4_write_align_stats names the side files
+static std::string stats_side_name(const std::string& path, const char* suffix) {
+  std::string stem = path;
+  for (size_t q = stem.size(); q > 0; q--) {
+    if (stem[q - 1] == '.') { stem.resize(q - 1); break; }
+    if (stem[q - 1] == '/' || stem[q - 1] == '\\') break;
+  }
+  return stem + suffix;
+}
 
 // one process, one GPU: the whole run, or rank o.rank of a -G run
 static int run_rank(Opts& o, const bool pe, const int max_ml) {
@@ -822,6 +835,15 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
       for (const std::string& q : e ? o.in2 : o.in1) { plain &= !is_gzip(q); tot_sz += file_size(q) + 1; }
       pp2.expect_text_bytes[e] = plain ? tot_sz : 0;
     }
+    if (!o.stats_file.empty()) {  // created / truncated before the reads are loaded (KAligner.cpp:4705-4730); a failed run leaves none of the three
+      FILE* fp = fopen(o.stats_file.c_str(), "wb");
+      if (!fp) { fprintf(stderr, "k4align: unable to create/truncate output stats file '%s'\n", o.stats_file.c_str()); return 5; }
+      fclose(fp);
+      guard.made.push_back(o.stats_file);
+      guard.made.push_back(stats_side_name(o.stats_file, ".AlignCntsDist.csv"));
+      if (pe) guard.made.push_back(stats_side_name(o.stats_file, ".GlobalPEInsertDist.csv"));
+      CK(k4_align_stats_collect(ix, 1));
+    }
     CK(k4_pipeline_open(ix, &pp2, &pl));
     CK(k4_pipeline_set_trims(pl, o.trim5, o.trim3));
     CK(k4_pipeline_set_sampling(pl, o.sample_nth));
@@ -934,6 +956,22 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
       if (!failed.empty()) { fprintf(stderr, "k4align: unable to write %s\n", failed.c_str()); return 5; }
       if (chatty) fprintf(stderr, "k4align: SNP processing completed with %llu putative SNPs discovered, written to %s in %.2fs\n",
                           (unsigned long long)sf.n_snps, o.snp_file.c_str(), secs(ts, now()));
+    }
+    if (!o.stats_file.empty()) {  // behind every stage that can still drop a read: the counted reads are the reported ones
+      auto ts = now();
+      k4_align_stats as;
+      CK(k4_pipeline_align_stats(pl, &as));
+      const uint64_t loaded = (uint64_t)(pe ? 2 : 1) * ((uint64_t)v.n_units - v.n_under - v.n_over);
+      if (o.splice_junct > 0) {
+        // with -A and SAM output the reference has its splice junction file open (KAligner.cpp:4446), so WriteReadHits runs in front
+        // of WriteBAMReadHits (:745-757) and calls WriteSubDist for every read too (:6835): those counts come out doubled
+        for (uint64_t q = 0; q < 4ull * as.len_stride; q++) { as.q_insts[q] *= 2; as.q_subs[q] *= 2; }
+        for (uint64_t q = 0; q <= as.len_stride; q++) as.m_sub[q] *= 2;
+      }
+      rc = k4_write_align_stats(ix, &as, loaded, o.ml_mode, max_ml, pe ? 1 : 0, o.stats_file.c_str());
+      k4_free_align_stats(&as);
+      if (rc != K4_OK) { fprintf(stderr, "k4align: %s\n", k4_last_error(ix)); return 5; }
+      if (chatty) fprintf(stderr, "k4align: alignment statistics written to %s in %.2fs\n", o.stats_file.c_str(), secs(ts, now()));
     }
     // (a rank of a -G run numbers every sequence: the parent renumbers when it knows which ones any rank has hit)
     const int bam_all_sq = (info.n_entries <= (uint32_t)o.rpt_sq_thres || o.rank_bam) ? 1 : 0;
@@ -1356,6 +1394,7 @@ int main(int argc, char** argv) {
       case 'A': o.splice_junct = atoi(val().c_str()); break;
       case 'x': o.min_flank_exacts = atoi(val().c_str()); break;
       case 'k': o.pcr_win = atoi(val().c_str()); o.pcr_given = true; break;
+      case 'O': o.stats_file = val(); break;
       case 'p': o.min_snp_reads = atoi(val().c_str()); break;
       case 'P': o.qvalue = atof(val().c_str()); break;
       case '1': o.snp_nonref_pcnt = atof(val().c_str()); break;
@@ -1442,6 +1481,14 @@ int main(int argc, char** argv) {
       return 1;
     }
     if (o.ml_mode == 5) { fprintf(stderr, "k4align: PCR artefact reduction '-k' with every multiloci alignment reported '-r5' is not built\n"); return 3; }
+  }
+  // the statistics count over all reads of the run in one place (summing per-rank counters is not built)
+  if (!o.stats_file.empty()) {
+    if (o.batch_mb > 0 || o.n_shards > 1 || !o.gpus.empty() || o.legacy) {
+      fprintf(stderr, "k4align: -O counts over all reads of the run; it cannot be combined with -b, -S, -G or -Z\n");
+      return 1;
+    }
+    if (o.ml_mode == 5) { fprintf(stderr, "k4align: alignment statistics '-O' with every multiloci alignment reported '-r5' are not built\n"); return 3; }
   }
   if (o.q_method < 0 || o.q_method > 3) { fprintf(stderr, "k4align: fastq quality '-g%d' specified outside of range 0..3\n", o.q_method); return 1; }
   if (o.min_flank_exacts < 0 || o.min_flank_exacts > 7) { fprintf(stderr, "k4align: max flank trimming '-x%d' specified outside of range 0..7\n", o.min_flank_exacts); return 1; }

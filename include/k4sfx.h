@@ -279,6 +279,46 @@ int k4_remove_orphan_juncts_dev(k4_index* ix, uint32_t which, int64_t n_reads, i
  *                           NumDnUniques), 0 for win_len 0.  Waits for `stream` and returns the count in *n_dups. */
 int k4_reduce_pcr_dups_dev(k4_index* ix, int32_t win_len, int64_t n_reads, int32_t max_ml, void* d_rr, void* d_hits, int64_t* n_dups,
                            void* stream);
+/* ---- which accepted alignments are kept (`kalign -5 <file>`, `-Z <regex>`, `-z <regex>`; kit4b_amd/csrc/k4_filter.hip) ------------
+ * k4_filter_loci_constraints_dev <- CKAligner::IdentifyConstraintViolations (KAligner.cpp:2716-2765; AcceptLociConstraints :2647-2714,
+ *                           AcceptBaseConstraint :2598-2645), which kalign runs behind ProcessPairedEnds / AssignMultiMatches and in front
+ *                           of ReducePCRduplicates: an accepted read on a constrained sequence one of whose loci -- AdjStartLoci ..
+ *                           AdjEndLoci of Seg[0], and of Seg[1] of a two-segment read (d_seg2, may be NULL) -- lies inside a constraint
+ *                           that the read's base there (reverse complemented for a Crick alignment) does not satisfy becomes
+ *                           K4_NAR_LOCICONSTRAINED with num_hits = inst = 0.  pe: n_units pairs in d_pe (d_rr, d_hits, d_seg2 unused), the
+ *                           mate of such a read is marked with it whatever its own state, and counted; else n_units reads in d_rr and hit
+ *                           slot 0 of d_hits.  constraints: HOST array, any order, at most 6400 over at most 64 sequences
+ *                           (KAligner.h:92-93), 0 <= start <= end < the sequence's length.  Waits for `stream`; *n_removed = reads marked.
+ * k4_filter_chroms_dev   <- CKAligner::FiltByChroms (:4025-4091), which kalign runs behind the flank autotrim and the orphan junction /
+ *                           microInDel filters: an accepted read (slot 0) on a sequence whose byte in d_accept is 0 becomes
+ *                           K4_NAR_CHROMFILT with num_hits = inst = 0.  d_accept: DEVICE array of n_entries + 1 bytes indexed by entry id.
+ *                           pe: d_rr_or_pe holds n_reads k4_pe_read records (read by read, as the reference does), else k4_read_result.
+ * k4_load_loci_constraints <- CKAligner::LoadLociConstraints (:1363-1545): a CSV of `sequence,start,end,bases` (0-based inclusive loci; bases
+ *                           from ACGT, and R = "the target's base"), an optional title line, blank lines and # comments sloughed.  *tbl is
+ *                           malloc'd (k4_free_host) and sorted by (sequence, start, end).  A line the reference turns down gives
+ *                           K4_ERR_PARSE (a file that cannot be read K4_ERR_OPEN_FILE) with the reference's message in k4_last_error and,
+ *                           when errbuf is not NULL, in errbuf (256 bytes).  Host only.
+ * k4_chrom_accept_mask   <- CUtility::CompileREs / MatchExcludeRegExpr / MatchIncludeRegExpr (libkit4b/Utility.cpp:78-287) over every
+ *                           sequence of the index: std::regex (ECMAScript) searched in the name up to its first blank; a sequence is kept
+ *                           (mask[entry id] = 1) when no exclude expression matches and an include expression does, or none was given.
+ *                           At most 20 of either kind (KAligner.h:33-34), each cut to 100 characters, blanks and one pair of quotes around it dropped; an expression
+ *                           that does not compile gives K4_ERR_PARAMS.  mask: host, n_entries + 1 bytes.  Host only. */
+typedef struct {
+  uint32_t chrom_id;   /* tsConstraintLoci.ChromID: 1-based entry id */
+  uint32_t start, end; /* StartLoci, EndLoci: 0-based, inclusive */
+  uint8_t bits;        /* Constraint: 0x01 A, 0x02 C, 0x04 G, 0x08 T, 0x10 R (the read's base equals the target's) */
+  uint8_t reserved[3];
+} k4_loci_constraint;
+int k4_filter_loci_constraints_dev(k4_index* ix, const k4_loci_constraint* constraints, int32_t n_constraints, int pe, int64_t n_units,
+                                   int32_t max_ml, void* d_rr, const void* d_hits, const void* d_seg2, void* d_pe, const void* d_reads,
+                                   const void* d_offs, const void* d_lens, int64_t* n_removed, void* stream);
+int k4_filter_chroms_dev(k4_index* ix, const void* d_accept, int pe, int64_t n_reads, int32_t max_ml, void* d_rr_or_pe, const void* d_hits,
+                         int64_t* n_removed, void* stream);
+/* the reads the two calls above marked on this index so far, by the NAR they carried before (20 slots).  kalign prints its EN line from
+ * a tally made while the reads are aligned (m_NumSloughedNs, KAligner.cpp:3732), so a PE mate that went from EN to LC is still in it. */
+int k4_filter_marked_prior(const k4_index* ix, uint64_t* prior20);
+int k4_load_loci_constraints(k4_index* ix, const char* path, k4_loci_constraint** tbl, int32_t* n, char* errbuf);
+int k4_chrom_accept_mask(k4_index* ix, int32_t n_incl, const char* const* incl, int32_t n_excl, const char* const* excl, uint8_t* mask);
 /* ---- alignment statistics (`kalign -O <file>`; kit4b_amd/csrc/k4_stats.hip) -------------------------------------------------
  * k4_align_stats_collect <- m_MultiHitDist (KAligner.cpp:9943) and m_pLenDist (:3251, :3408, :3511): on = 1 zeroes two tallies on the
  *                           device which every later k4_kalign_*_batch_dev / k4_kalign_pe_batch_dev call (a pipeline's too) adds
@@ -337,7 +377,8 @@ int k4_best_matches_batch_dev(k4_index* ix, const k4_align_params* p, int64_t n_
  *                         with MaxHits 10, multi x multi resolution) + ProcessPairedEnds (:3159-3596: AcceptProvPE,
  *                         PEInsertSize, orphan rescue, NAR reassignment).  out[2i] = PE1 of pair i, out[2i+1] = PE2. */
 enum { K4_NAR_CHROMFILT = 11, K4_NAR_PEINSERTMIN = 13, K4_NAR_PEINSERTMAX = 14, K4_NAR_PENOHIT = 15, K4_NAR_PESTRAND = 16,
-       K4_NAR_PECHROM = 17, K4_NAR_PEUNALIGN = 18 };  /* eNAR, KAligner.h:136-158 */
+       K4_NAR_PECHROM = 17, K4_NAR_PEUNALIGN = 18,
+       K4_NAR_LOCICONSTRAINED = 19 /* eNARLociConstrained: a base of the read violates a loci base constraint (k4_filter_loci_constraints_dev) */ };  /* eNAR, KAligner.h:136-158 */
 typedef struct {
   int32_t pe_mode;      /* etPEproc (KAligner.h:278-282): 1 orphan recovery, 2 unique only, 3 orphanSE, 4 uniqueSE */
   int32_t pair_min_len; /* -d */

@@ -107,6 +107,14 @@ class PipelineView(C.Structure):
                 ("d_lens", C.c_void_p), ("names", SamNames)]
 
 
+class LociConstraint(C.Structure):  # k4_loci_constraint
+    _fields_ = [("chrom_id", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("bits", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+LOCI_CONSTRAINT_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("bits", "u1"), ("reserved", "u1", (3,))])
+NAR_CHROMFILT, NAR_LOCICONSTRAINED = 11, 19
+
+
 class AlignStats(C.Structure):  # k4_align_stats
     _fields_ = [("max_align_len", C.c_uint32), ("len_stride", C.c_uint32), ("n_entries", C.c_uint32), ("reserved", C.c_uint32),
                 ("n_accepted", C.c_uint64), ("q_insts", C.POINTER(C.c_uint64)), ("q_subs", C.POINTER(C.c_uint64)),
@@ -140,7 +148,8 @@ ABI_SYMBOLS = [
     "k4_pipeline_open", "k4_pipeline_acquire", "k4_pipeline_submit", "k4_pipeline_submit_host", "k4_pipeline_wait_aligned",
     "k4_pipeline_format", "k4_pipeline_next_sam", "k4_pipeline_read_sam", "k4_pipeline_close", "k4_sfx_map", "k4_sfx_unmap",
     "k4_set_raw_header", "k4_align_stats_collect", "k4_align_stats_dev", "k4_free_align_stats", "k4_write_align_stats",
-    "k4_pipeline_align_stats",
+    "k4_pipeline_align_stats", "k4_filter_loci_constraints_dev", "k4_filter_chroms_dev", "k4_load_loci_constraints", "k4_chrom_accept_mask",
+    "k4_filter_marked_prior",
 ]
 
 
@@ -221,6 +230,12 @@ def lib():
     L.k4_free_align_stats.restype = None
     L.k4_write_align_stats.argtypes = [vp, C.POINTER(AlignStats), u64, C.c_int32, C.c_int32, i32, C.c_char_p]
     L.k4_pipeline_align_stats.argtypes = [vp, C.POINTER(AlignStats)]
+    L.k4_filter_loci_constraints_dev.argtypes = [vp, C.POINTER(LociConstraint), C.c_int32, i32, i64, C.c_int32, vp, vp, vp, vp, vp, vp, vp,
+                                                 C.POINTER(C.c_int64), vp]
+    L.k4_filter_chroms_dev.argtypes = [vp, vp, i32, i64, C.c_int32, vp, vp, C.POINTER(C.c_int64), vp]
+    L.k4_filter_marked_prior.argtypes = [vp, C.POINTER(u64)]
+    L.k4_load_loci_constraints.argtypes = [vp, C.c_char_p, C.POINTER(C.POINTER(LociConstraint)), C.POINTER(C.c_int32), C.c_char_p]
+    L.k4_chrom_accept_mask.argtypes = [vp, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), vp]
     L.k4_format_sam_ext_dev.argtypes = [vp, i32, i64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(SamNames), C.POINTER(vp),
                                         C.POINTER(u64), C.POINTER(SamStats), vp, vp]
     L.k4_format_bam_dev.argtypes = [vp, i32, i64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(SamNames), C.c_int32, C.POINTER(vp),
@@ -704,6 +719,57 @@ class SfxIndex:
         ptr = lambda a: a if isinstance(a, int) else a.data_ptr()  # noqa: E731
         self._ck(lib().k4_reduce_pcr_dups_dev(self.h, int(win_len), int(n), int(max_ml), ptr(d_rr), ptr(d_hits), C.byref(c), stream))
         return c.value
+
+    def load_loci_constraints(self, path):
+        """LoadLociConstraints (`kalign -5 <file>`, KAligner.cpp:1363-1545): the CSV `sequence,start,end,bases` as a LOCI_CONSTRAINT_DTYPE
+        array sorted by (sequence, start, end); a line the reference turns down raises K4Error (-47) with the reference's message."""
+        tbl, n = C.POINTER(LociConstraint)(), C.c_int32(0)
+        self._ck(lib().k4_load_loci_constraints(self.h, os.fsencode(path), C.byref(tbl), C.byref(n), None))
+        try:
+            if n.value == 0:
+                return np.zeros(0, LOCI_CONSTRAINT_DTYPE)
+            return np.frombuffer(C.string_at(tbl, n.value * C.sizeof(LociConstraint)), LOCI_CONSTRAINT_DTYPE).copy()
+        finally:
+            lib().k4_free_host(C.cast(tbl, C.c_void_p))
+
+    def chrom_accept_mask(self, include=(), exclude=()):
+        """Which sequences `kalign -z <include regex> -Z <exclude regex>` keeps (CUtility::MatchExcludeRegExpr / MatchIncludeRegExpr):
+        uint8[n_entries + 1] indexed by entry id, 1 = keep; an expression that does not compile raises K4Error (-100)."""
+        mask = np.zeros(self.info()["n_entries"] + 1, np.uint8)
+        arr = lambda xs: (C.c_char_p * max(len(xs), 1))(*[x.encode() if isinstance(x, str) else x for x in xs])  # noqa: E731
+        inc, exc = list(include), list(exclude)
+        self._ck(lib().k4_chrom_accept_mask(self.h, len(inc), arr(inc), len(exc), arr(exc), mask.ctypes.data))
+        return mask
+
+    def filter_chroms(self, d_accept, n, max_ml, d_rr=None, d_hits=None, d_pe=None, stream=0):
+        """FiltByChroms (KAligner.cpp:4025-4091) in place over device arrays: accepted reads on a sequence whose byte in d_accept
+        (uint8[n_entries + 1] on the device, see chrom_accept_mask) is 0 become NAR_CHROMFILT; SE d_rr + d_hits or PE d_pe (n records).
+        Returns the number of reads marked."""
+        c = C.c_int64(0)
+        ptr = lambda a: None if a is None else a if isinstance(a, int) else a.data_ptr()  # noqa: E731
+        pe = d_pe is not None
+        self._ck(lib().k4_filter_chroms_dev(self.h, ptr(d_accept), 1 if pe else 0, int(n), int(max_ml), ptr(d_pe if pe else d_rr), ptr(d_hits),
+                                            C.byref(c), stream))
+        return c.value
+
+    def filter_loci_constraints(self, constraints, n_units, max_ml, d_reads, d_offs, d_lens, d_rr=None, d_hits=None, d_seg2=None, d_pe=None,
+                                stream=0):
+        """IdentifyConstraintViolations (`kalign -5`, KAligner.cpp:2716-2765) in place over device arrays: constraints is a host
+        LOCI_CONSTRAINT_DTYPE array (load_loci_constraints); SE n_units reads in d_rr + d_hits (+ d_seg2), PE n_units pairs in d_pe.
+        Reads that violate a constraint (PE: and their mates) become NAR_LOCICONSTRAINED; returns how many."""
+        c = C.c_int64(0)
+        ptr = lambda a: None if a is None else a if isinstance(a, int) else a.data_ptr()  # noqa: E731
+        t = np.ascontiguousarray(constraints, LOCI_CONSTRAINT_DTYPE)
+        self._ck(lib().k4_filter_loci_constraints_dev(self.h, C.cast(t.ctypes.data, C.POINTER(LociConstraint)), len(t), 1 if d_pe is not None else 0,
+                                                      int(n_units), int(max_ml), ptr(d_rr), ptr(d_hits), ptr(d_seg2), ptr(d_pe), ptr(d_reads),
+                                                      ptr(d_offs), ptr(d_lens), C.byref(c), stream))
+        return c.value
+
+    def filter_marked_prior(self):
+        """uint64[20]: the reads filter_chroms / filter_loci_constraints marked on this index so far, by the NAR they carried before"""
+        out = (C.c_uint64 * 20)()
+        self._ck(lib().k4_filter_marked_prior(self.h, out))
+        return np.array(out[:], np.uint64)
 
     def align_stats_collect(self, on=True):
         """Start (zero) or drop the run tallies of `kalign -O` that the align calls add to: the multihit distribution and the PE insert lengths."""

@@ -112,6 +112,7 @@ struct k4_index {
   // `kalign -O` run tallies (k4_align_stats_collect, k4_stats.hip): K4_STATS_MULTI multihit bins, then K4_STATS_PE_LEN + 1 insert lengths;
   // null = not collected (the align and pairing kernels then do nothing more than before)
   unsigned long long* d_run_stats = nullptr;
+  uint64_t filter_prior[20] = {0};  // reads the filter stages (k4_filter.hip) marked so far, by the NAR they carried before
   double deep_bucket_frac = 0;  // share of the suffixes that sit in k-mer buckets deeper than K4_DEEP_BUCKET (k4_index.hip)
   std::vector<k4_entry> entries;
   std::string dataset;

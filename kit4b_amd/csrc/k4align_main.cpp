@@ -13,7 +13,12 @@
 //   PCR duplicates (-k)  CKAligner::ReducePCRduplicates :2303-2400                -> k4_reduce_pcr_dups_dev
 //   statistics files (-O) CKAligner::WriteSubDist :6469-6525, WriteBasicCountStats :4159-4300, ReportTargHitCnts :5458-5712,
 //                        the insert size file of ProcessPairedEnds :3092-3146     -> k4_pipeline_align_stats, k4_write_align_stats
-// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k -O (plus -g <gpu>, -S <i/N> read slice).
+//   loci constraints (-5) CKAligner::LoadLociConstraints :1363-1545, IdentifyConstraintViolations :2716-2765
+//                                                                                  -> k4_load_loci_constraints, k4_filter_loci_constraints_dev
+//   chromosome filters   CKAligner::FiltByChroms :4025-4091 (kalign -Z / -z; here --chromexclude / --chromeinclude)
+//                                                                                  -> k4_chrom_accept_mask, k4_filter_chroms_dev
+// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k -O -5 (plus -g <gpu>, -S <i/N> read slice);
+// kalign's -Z / -z go by their long names --chromexclude / --chromeinclude (the letters mean something else here).
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -30,6 +35,7 @@
 #include <cstring>
 #include <map>
 #include <queue>
+#include <regex>
 #include <memory>
 #include <string>
 #include <vector>
@@ -53,6 +59,8 @@ struct Opts {
   int min_chimeric = 0, micro_indel = 0, splice_junct = 0, min_flank_exacts = 0;  // -c / -a / -A / -x (KAlignerCL.cpp:237,245,246,267)
   int pcr_win = -1;                 // -k <0..250>: PCR artefact reduction window (KAlignerCL.cpp:222,738-743); -1 = off
   bool pcr_given = false;           // (an explicit -k-1 is turned down like any value outside 0..250)
+  std::string loci_file;            // -5 / --lociconstraints <file>: loci base constraints CSV (KAlignerCL.cpp:255)
+  std::vector<std::string> chrom_excl, chrom_incl;  // --chromexclude / --chromeinclude <regex>, each repeatable (kalign -Z / -z, KAlignerCL.cpp:274-275)
   std::string stats_file;           // -O <file>: alignment statistics (KAlignerCL.cpp:256) and its two side files
   double batch_mb = 0;              // -b <MB>: stream the input, this much text per file per batch (0: the whole input at once)
   int shard = 0, n_shards = 1;      // -S i/N: this process aligns the i-th of N contiguous slices of the reads (one process per GPU)
@@ -533,7 +541,7 @@ const char* kNarAbbr[20] = {"NA", "AA", "EN", "NL", "MH", "ML", "ET", "OJ", "OM"
 void usage() {
   fprintf(stderr,
           "k4align -i reads.f[aq][.gz] [-i more ...] [-u mates ...] -I index.sfx -o out.sam|out.bam [-z bgzf level=6] [-s subs/100bp=5] [-e 1|2] [-m 0..3] [-n maxNs=1]\n"
-          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-O stats.csv] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
+          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
 }
 
 }  // namespace
@@ -637,6 +645,32 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
     fprintf(stderr, "k4align: index '%s' %u sequences, %llu bp; minimum core size %dbp%s\n", info.dataset, info.n_entries,
             (unsigned long long)info.tot_seqs_len, mcl, multi ? " (read once, sent to the other GPUs over xGMI)" : "");
   auto t_open = std::chrono::steady_clock::now();
+  // -5: the constraints are checked against the index's sequences before any read is loaded (KAligner.cpp:4619-4628)
+  std::unique_ptr<k4_loci_constraint, void (*)(void*)> loci_tbl(nullptr, k4_free_host);
+  int32_t n_loci = 0;
+  if (!o.loci_file.empty()) {
+    k4_loci_constraint* t = nullptr;
+    if ((rc = k4_load_loci_constraints(ix, o.loci_file.c_str(), &t, &n_loci, nullptr)) != K4_OK) {
+      fprintf(stderr, "k4align: %s (%d)\n", k4_last_error(ix), rc);
+      k4_close(ix);  // (joins the thread that is still loading the index)
+      return rc == K4_ERR_OPEN_FILE ? 2 : 1;
+    }
+    loci_tbl.reset(t);
+    if (chatty) fprintf(stderr, "k4align: %d loci base constraints loaded from '%s'\n", (int)n_loci, o.loci_file.c_str());
+  }
+  // --chromexclude / --chromeinclude: one decision per sequence of the index, made here once
+  std::vector<uint8_t> chrom_accept;
+  if (!o.chrom_excl.empty() || !o.chrom_incl.empty()) {
+    std::vector<const char*> inc, exc;
+    for (const std::string& q : o.chrom_incl) inc.push_back(q.c_str());
+    for (const std::string& q : o.chrom_excl) exc.push_back(q.c_str());
+    chrom_accept.assign((size_t)info.n_entries + 1, 0);
+    if ((rc = k4_chrom_accept_mask(ix, (int32_t)inc.size(), inc.data(), (int32_t)exc.size(), exc.data(), chrom_accept.data())) != K4_OK) {
+      fprintf(stderr, "k4align: %s (%d)\n", k4_last_error(ix), rc);
+      k4_close(ix);
+      return 1;
+    }
+  }
 
   if ((o.ml_mode == 3 || o.ml_mode == 4) && (o.batch_mb > 0 || o.n_shards > 1)) {
     fprintf(stderr, "k4align: -r3 / -r4 cluster over all reads of the run; they cannot be combined with -b or -S\n");
@@ -689,6 +723,11 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
       }
     }
     int64_t cnt = 0;
+    if (n_loci > 0) {  // IdentifyConstraintViolations: behind ProcessPairedEnds / AssignMultiMatches, in front of ReducePCRduplicates (KAligner.cpp:628)
+      CK(k4_filter_loci_constraints_dev(ix, loci_tbl.get(), n_loci, pe ? 1 : 0, n, max_ml, d_rr, d_hits, d_seg2, d_pe, d_reads, d_offs, d_lens, &cnt,
+                                        nullptr));
+      fprintf(stderr, "k4align: %lld loci base constraint violations\n", (long long)cnt);
+    }
     if (!pe && o.pcr_win >= 0) {  // ReducePCRduplicates, behind AssignMultiMatches and before the filters (KAligner.cpp:628-640)
       CK(k4_reduce_pcr_dups_dev(ix, o.pcr_win, n, max_ml, d_rr, d_hits, &cnt, nullptr));
       fprintf(stderr, "k4align: %lld potential PCR artefact reads removed\n", (long long)cnt);
@@ -706,6 +745,15 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
     if (!pe && o.micro_indel > 0) {
       CK(k4_remove_orphan_juncts_dev(ix, K4_EXT_INDEL, n, max_ml, d_rr, d_hits, d_seg2, &cnt, nullptr));
       fprintf(stderr, "k4align: %lld orphan microInDel reads removed\n", (long long)cnt);
+    }
+    if (!chrom_accept.empty()) {  // FiltByChroms: behind the autotrim and the orphan filters, in front of every report (KAligner.cpp:693)
+      void* d_accept = nullptr;
+      CK(k4_alloc_device(ix, chrom_accept.size(), &d_accept));
+      CK(k4_copy_to_device(ix, d_accept, chrom_accept.data(), chrom_accept.size()));
+      rc = k4_filter_chroms_dev(ix, d_accept, pe ? 1 : 0, pe ? 2 * n : n, max_ml, pe ? d_pe : d_rr, d_hits, &cnt, nullptr);
+      k4_free_device(d_accept);
+      CK(rc);
+      fprintf(stderr, "k4align: %lld matches removed by chromosome filtering\n", (long long)cnt);
     }
     return K4_OK;
   };
@@ -1019,6 +1067,11 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
 
   // ---- statistics (ReportAlignStats) ------------------------------------------------------------------------------
   const uint64_t my_lines = tot.n_lines;
+  if (n_loci > 0) {  // the EN line is m_NumSloughedNs, counted while the reads are aligned (KAligner.cpp:3732): a PE mate marked LC since stays in it
+    uint64_t prior[20];
+    CK(k4_filter_marked_prior(ix, prior));
+    tot.nar[K4_NAR_NS] += prior[K4_NAR_NS];
+  }
   if (comm) {  // the final aligned-read count/merge: one all-reduce of the tallies (north_star: the only collective on the path)
     uint64_t t[26];
     for (int k = 0; k < 20; k++) t[k] = tot.nar[k];
@@ -1373,6 +1426,19 @@ int main(int argc, char** argv) {
     if (a.size() < 2 || a[0] != '-') { usage(); return 1; }
     auto val = [&]() -> std::string { return a.size() > 2 ? a.substr(2) : (i + 1 < argc ? std::string(argv[++i]) : std::string()); };
     switch (a[1]) {
+      case '-': {  // kalign's long names, for the options whose letters are taken here: --name value | --name=value
+        std::string name = a.substr(2), v;
+        const size_t eq = name.find('=');
+        if (eq != std::string::npos) { v = name.substr(eq + 1); name.resize(eq); }
+        else if (i + 1 < argc) v = argv[++i];
+        else { usage(); return 1; }
+        if (name == "chromexclude") o.chrom_excl.push_back(v);
+        else if (name == "chromeinclude") o.chrom_incl.push_back(v);
+        else if (name == "lociconstraints") o.loci_file = v;
+        else { usage(); return 1; }
+        break;
+      }
+      case '5': o.loci_file = val(); break;
       case 'i': o.in1.push_back(val()); break;
       case 'u': o.in2.push_back(val()); break;
       case 'I': o.sfx = val(); break;
@@ -1489,6 +1555,26 @@ int main(int argc, char** argv) {
       return 1;
     }
     if (o.ml_mode == 5) { fprintf(stderr, "k4align: alignment statistics '-O' with every multiloci alignment reported '-r5' are not built\n"); return 3; }
+  }
+  // the loci constraints and the chromosome filters look at one read (pair) at a time: they run with -b, -S i/N and -G as well
+  if (!o.chrom_excl.empty() || !o.chrom_incl.empty()) {
+    if (o.chrom_excl.size() > 20 || o.chrom_incl.size() > 20) { fprintf(stderr, "k4align: at most 20 --chromexclude and 20 --chromeinclude expressions\n"); return 1; }  // cMaxExcludeChroms / cMaxIncludeChroms
+    for (int which = 0; which < 2; which++)  // a bad expression is a parameter error (CUtility::CompileREs, libkit4b/Utility.cpp:78-140)
+      for (const std::string& q : which ? o.chrom_excl : o.chrom_incl) {
+        try { std::regex re(q.substr(0, 100)); }
+        catch (const std::regex_error& err) {
+          fprintf(stderr, "k4align: Unable to compile %s regular expression '%s' - '%s'\n", which ? "exclusion" : "inclusion", q.c_str(), err.what());
+          return 1;
+        }
+      }
+    if (pe) { fprintf(stderr, "k4align: --chromexclude / --chromeinclude in paired end processing '-u' (the filter inside ProcessPairedEnds) is not built\n"); return 3; }
+    if (o.ml_mode == 5) { fprintf(stderr, "k4align: --chromexclude / --chromeinclude with every multiloci alignment reported '-r5' is not built\n"); return 3; }
+  }
+  if (!o.loci_file.empty()) {
+    if (o.ml_mode == 5) { fprintf(stderr, "k4align: loci base constraints '-5' with every multiloci alignment reported '-r5' are not built\n"); return 3; }
+    FILE* t = fopen(o.loci_file.c_str(), "rb");
+    if (!t) { fprintf(stderr, "k4align: Unable to open '%s' for processing\n", o.loci_file.c_str()); return 2; }
+    fclose(t);
   }
   if (o.q_method < 0 || o.q_method > 3) { fprintf(stderr, "k4align: fastq quality '-g%d' specified outside of range 0..3\n", o.q_method); return 1; }
   if (o.min_flank_exacts < 0 || o.min_flank_exacts > 7) { fprintf(stderr, "k4align: max flank trimming '-x%d' specified outside of range 0..7\n", o.min_flank_exacts); return 1; }

@@ -22,16 +22,9 @@
 #include <algorithm>
 #include <rocprim/rocprim.hpp>
 #include "k4_device.h"
-#include "k4_internal.h"
+#include "k4_stage.h"
 
 namespace {
-
-struct Buf {
-  void* p = nullptr;
-  ~Buf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  template <typename T> T* as() { return (T*)p; }
-};
 
 constexpr uint32_t kUniq = 0x8000u;  // cUniqueClustFlg and friends, KAligner.h:96-101
 constexpr uint32_t kOverlap = 10, kUScore = 5, kMScore = 1, kScale = 10, kMinScore = 50;
@@ -263,25 +256,17 @@ extern "C" int k4_assign_multi_dev(k4_index* ix, int ml_mode, int32_t max_reads_
   hipStream_t st = (hipStream_t)stream;
   k4_read_result* rr = (k4_read_result*)d_rr;
   k4_hit* hits = (k4_hit*)d_hits;
-  Buf cnt, off, tmp;
+  K4DevBuf cnt, off;
   K4_HIP(ix, cnt.alloc((size_t)(n_reads + 1) * 4));
   K4_HIP(ix, off.alloc((size_t)(n_reads + 1) * 8));
   hipLaunchKernelGGL(k4k_mm_count, dim3(grid_for(n_reads + 1)), dim3(256), 0, st, n_reads, rr, cnt.as<uint32_t>());
-  {
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::exclusive_scan(nullptr, tb, cnt.as<uint32_t>(), off.as<uint64_t>(), (uint64_t)0, (size_t)(n_reads + 1),
-                                       rocprim::plus<uint64_t>(), st));
-    K4_HIP(ix, tmp.alloc(tb));
-    K4_HIP(ix, rocprim::exclusive_scan(tmp.p, tb, cnt.as<uint32_t>(), off.as<uint64_t>(), (uint64_t)0, (size_t)(n_reads + 1),
-                                       rocprim::plus<uint64_t>(), st));
-  }
+  K4_TRY(k4s_exclusive_scan<K4DevBuf>(ix, cnt.as<uint32_t>(), off.as<uint64_t>(), (uint64_t)0, (size_t)(n_reads + 1), rocprim::plus<uint64_t>(), st));
   uint64_t m = 0;
-  K4_HIP(ix, hipMemcpyAsync(&m, off.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
+  K4_TRY(k4s_read_back(ix, &m, off.as<uint64_t>() + n_reads, st));
   if (m == 0) return K4_OK;
   if (m > 0xFFFFFFFFull || n_reads > 0xFFFFFFFFll) return k4_fail(ix, K4_ERR_UNSUPPORTED, "more than 2^32 loci to cluster");
   // SortMultiHits order: stable sort on (len, mismatches, strand, read), then on (chrom, start)
-  Buf va, vb, ka, kb, ent, st0, stc, pend, npend, left, nas;
+  K4DevBuf va, vb, ka, kb, ent, st0, stc, pend, left, nas;
   K4_HIP(ix, va.alloc(m * 8));
   K4_HIP(ix, vb.alloc(m * 8));
   K4_HIP(ix, ka.alloc(m * 8));
@@ -290,16 +275,10 @@ extern "C" int k4_assign_multi_dev(k4_index* ix, int ml_mode, int32_t max_reads_
                      va.as<uint64_t>(), ka.as<uint64_t>());
   rocprim::double_buffer<uint64_t> keys(ka.as<uint64_t>(), kb.as<uint64_t>());
   rocprim::double_buffer<uint64_t> vals(va.as<uint64_t>(), vb.as<uint64_t>());
-  {
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::radix_sort_pairs(nullptr, tb, keys, vals, (size_t)m, 0u, 64u, st));
-    Buf t2;
-    K4_HIP(ix, t2.alloc(tb));
-    K4_HIP(ix, rocprim::radix_sort_pairs(t2.p, tb, keys, vals, (size_t)m, 0u, 64u, st));
-    hipLaunchKernelGGL(k4k_mm_key_major, dim3(grid_for(m)), dim3(256), 0, st, m, hits, vals.current(), keys.current());
-    K4_HIP(ix, rocprim::radix_sort_pairs(t2.p, tb, keys, vals, (size_t)m, 0u, 64u, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
-  }
+  K4_TRY(k4s_sort_pairs<K4DevBuf>(ix, keys, vals, (size_t)m, 0u, 64u, st));
+  hipLaunchKernelGGL(k4k_mm_key_major, dim3(grid_for(m)), dim3(256), 0, st, m, hits, vals.current(), keys.current());
+  K4_TRY(k4s_sort_pairs<K4DevBuf>(ix, keys, vals, (size_t)m, 0u, 64u, st));
+  K4_HIP(ix, hipStreamSynchronize(st));
   const uint64_t* val = vals.current();
   K4_HIP(ix, ent.alloc(m * sizeof(Ent)));
   K4_HIP(ix, st0.alloc(m));
@@ -312,30 +291,17 @@ extern "C" int k4_assign_multi_dev(k4_index* ix, int ml_mode, int32_t max_reads_
                      stc.as<uint8_t>());
   K4_HIP(ix, hipGetLastError());
   // the undecided loci
-  K4_HIP(ix, pend.alloc(m * 4));
-  K4_HIP(ix, npend.alloc(8));
   K4_HIP(ix, left.alloc(4));
   K4_HIP(ix, nas.alloc(8));
   K4_HIP(ix, hipMemsetAsync(nas.p, 0, 8, st));
   uint64_t n_pend = 0;
-  {
-    rocprim::counting_iterator<uint32_t> all(0);
-    IsPending pred{st0.as<uint8_t>()};
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::select(nullptr, tb, all, pend.as<uint32_t>(), npend.as<uint64_t>(), (size_t)m, pred, st));
-    Buf t3;
-    K4_HIP(ix, t3.alloc(tb));
-    K4_HIP(ix, rocprim::select(t3.p, tb, all, pend.as<uint32_t>(), npend.as<uint64_t>(), (size_t)m, pred, st));
-    K4_HIP(ix, hipMemcpyAsync(&n_pend, npend.p, 8, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
-  }
+  K4_TRY(k4s_select_indices(ix, pend, (size_t)m, IsPending{st0.as<uint8_t>()}, st, &n_pend));
   uint32_t n_left = n_pend ? 1 : 0;
   for (uint64_t round = 0; n_left && round <= n_pend; round++) {  // every round decides at least the lowest undecided locus
     K4_HIP(ix, hipMemsetAsync(left.p, 0, 4, st));
     hipLaunchKernelGGL(k4k_mm_orphans, dim3(grid_for(n_pend)), dim3(256), 0, st, n_pend, pend.as<uint32_t>(), m, ent.as<Ent>(),
                        st0.as<uint8_t>(), stc.as<uint8_t>(), left.as<uint32_t>());
-    K4_HIP(ix, hipMemcpyAsync(&n_left, left.p, 4, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
+    K4_TRY(k4s_read_back(ix, &n_left, left.p, st));
   }
   if (n_left) return k4_fail(ix, K4_ERR_INTERNAL, "orphan walk did not settle");
   hipLaunchKernelGGL(k4k_mm_assign, dim3(grid_for(m)), dim3(256), 0, st, m, max_ml, ent.as<Ent>(), val, stc.as<uint8_t>(), rr, hits,
@@ -343,8 +309,7 @@ extern "C" int k4_assign_multi_dev(k4_index* ix, int ml_mode, int32_t max_reads_
   hipLaunchKernelGGL(k4k_mm_finish, dim3(grid_for(n_reads)), dim3(256), 0, st, n_reads, max_ml, cnt.as<uint32_t>(), hits);
   K4_HIP(ix, hipGetLastError());
   unsigned long long na = 0;
-  K4_HIP(ix, hipMemcpyAsync(&na, nas.p, 8, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
+  K4_TRY(k4s_read_back(ix, &na, nas.p, st));
   if (n_assigned) *n_assigned = (int64_t)na;
   return K4_OK;
 }

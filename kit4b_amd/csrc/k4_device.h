@@ -4,6 +4,15 @@
 
 #define K4_DEV __device__ __forceinline__
 
+// CKAligner::AdjStartLoci / AdjHitLen / AdjEndLoci (KAligner.cpp:1633-1655) on a flat record: the span of Seg[0] that is left
+// inside its trimmed flanks, on the target.  The end is inclusive.  32-bit unsigned arithmetic: a caller that has to tell an
+// over-trimmed record (length <= 0) casts the length to int32_t.
+K4_DEV uint32_t k4d_adj_start(const k4_hit& h) { return h.match_loci + (h.strand == '+' ? K4_HIT_TRIM_LEFT(h) : K4_HIT_TRIM_RIGHT(h)); }
+K4_DEV uint32_t k4d_adj_len(const k4_hit& h) { return (uint32_t)h.match_len - K4_HIT_TRIM_LEFT(h) - K4_HIT_TRIM_RIGHT(h); }
+K4_DEV uint32_t k4d_adj_end(const k4_hit& h) {
+  return h.match_loci + ((uint32_t)h.match_len - (h.strand == '+' ? K4_HIT_TRIM_RIGHT(h) : K4_HIT_TRIM_LEFT(h)) - 1);
+}
+
 // gfx950 global loads of 2/3/4 dwords only need dword alignment: these types make hipcc emit one wide load where the
 // address is merely 4-byte aligned (a divergent wave pays per lane-request in the vector L1, not per byte).
 typedef uint32_t k4_u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));

@@ -29,8 +29,7 @@
 #include <string>
 #include <vector>
 #include "k4_device.h"
-#include "k4_internal.h"
-#include "k4_pool.h"
+#include "k4_stage.h"
 
 #define K4_MAX_CONSTRAINED_CHROMS 64                                 /* cMaxConstrainedChroms, KAligner.h:92 */
 #define K4_MAX_CONSTRAINED_LOCI (K4_MAX_CONSTRAINED_CHROMS * 100)    /* cMaxConstrainedLoci, KAligner.h:93 */
@@ -39,13 +38,6 @@
 #define K4_FILTER_THREADS 1024                                       /* one block per CU holds the table once for 16 waves */
 
 namespace {
-
-struct Buf {
-  void* p = nullptr;
-  ~Buf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t bytes) { return k4_malloc_retry(&p, bytes ? bytes : 1); }
-  template <typename T> T* as() { return (T*)p; }
-};
 
 // first k in [lo, hi) with a[k] > v (upper) / a[k] >= v (lower); a ascending
 K4_DEV uint32_t k4d_first_gt(const uint32_t* a, uint32_t lo, uint32_t hi, uint32_t v) {
@@ -100,13 +92,11 @@ k4k_filter_loci(K4DevIndex ix, const uint32_t* __restrict__ g_tab, uint32_t n_c,
         }
         if (lo < n_ch && c_chrom[3 * lo] == h.chrom_id && h.chrom_id >= 1 && h.chrom_id <= ix.n_entries) {
           const uint32_t t_lo = c_chrom[3 * lo + 1], t_hi = c_chrom[3 * lo + 2];
-          const uint32_t tl = h.ext & 0xFFFu, tr = (h.ext >> 12) & 0xFFFu;
-          const bool minus = h.strand == '-';
           // Seg[0]: AdjStartLoci .. AdjEndLoci; the walk of the read starts at ReadOfs (0) + TrimLeft on either strand
-          if ((uint32_t)h.match_len > tl + tr) {
-            seg_s[0] = h.match_loci + (minus ? tr : tl);
-            seg_e[0] = seg_s[0] + ((uint32_t)h.match_len - tl - tr) - 1u;
-            seg_q[0] = tl;
+          if ((int32_t)k4d_adj_len(h) > 0) {
+            seg_s[0] = k4d_adj_start(h);
+            seg_e[0] = k4d_adj_end(h);
+            seg_q[0] = K4_HIT_TRIM_LEFT(h);
             seg_k1[0] = k4d_first_gt(c_start, t_lo, t_hi, seg_e[0]);
             seg_k0[0] = k4d_first_ge(c_pmax, t_lo, seg_k1[0], seg_s[0]);
           }
@@ -228,7 +218,7 @@ extern "C" int k4_filter_chroms_dev(k4_index* ix, const void* d_accept, int pe, 
   if (!d_accept || !d_rr_or_pe || (!pe && (!d_hits || max_ml < 1))) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
-  Buf cnt;
+  K4DevBuf cnt;
   K4_HIP(ix, cnt.alloc(8));
   K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 8, st));
   const int64_t blocks = std::min<int64_t>((n_reads + 255) / 256, grid_for(ix->device, 8));
@@ -237,8 +227,7 @@ extern "C" int k4_filter_chroms_dev(k4_index* ix, const void* d_accept, int pe, 
                      cnt.as<unsigned long long>());
   K4_HIP(ix, hipGetLastError());
   unsigned long long c = 0;
-  K4_HIP(ix, hipMemcpyAsync(&c, cnt.p, 8, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
+  K4_TRY(k4s_read_back(ix, &c, cnt.p, st));
   if (n_removed) *n_removed = (int64_t)c;
   ix->filter_prior[K4_NAR_ACCEPTED] += c;
   return K4_OK;
@@ -290,7 +279,7 @@ extern "C" int k4_filter_loci_constraints_dev(k4_index* ix, const k4_loci_constr
   std::copy(chrom.begin(), chrom.end(), tab.begin() + 3 * n);
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
-  Buf d_tab, cnt;  // cnt: [0] reads marked, [1 + k] those of them that carried NAR k and were not accepted
+  K4DevBuf d_tab, cnt;  // cnt: [0] reads marked, [1 + k] those of them that carried NAR k and were not accepted
   K4_HIP(ix, d_tab.alloc((size_t)words * 4));
   K4_HIP(ix, cnt.alloc(8 * 21));
   K4_HIP(ix, hipMemcpyAsync(d_tab.p, tab.data(), (size_t)words * 4, hipMemcpyHostToDevice, st));
@@ -305,8 +294,7 @@ extern "C" int k4_filter_loci_constraints_dev(k4_index* ix, const k4_loci_constr
                      cnt.as<unsigned long long>());
   K4_HIP(ix, hipGetLastError());
   unsigned long long c[21];
-  K4_HIP(ix, hipMemcpyAsync(c, cnt.p, 8 * 21, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));  // (the host copy of the table is read by the upload until here)
+  K4_TRY(k4s_read_back(ix, &c, cnt.p, st));  // (the host copy of the table is read by the upload until here)
   if (n_removed) *n_removed = (int64_t)c[0];
   unsigned long long others = 0;
   for (int k = 0; k < 20; k++) { ix->filter_prior[k] += c[1 + k]; others += c[1 + k]; }

@@ -14,7 +14,7 @@
 #include <vector>
 #include <rocprim/rocprim.hpp>
 #include "k4_device.h"
-#include "k4_pool.h"
+#include "k4_stage.h"
 #include "k4_stages.h"
 
 namespace {
@@ -274,29 +274,20 @@ extern "C" int k4_parse_fastx_dev(k4_index* ix, const void* d_text_v, uint64_t t
   const uint8_t* text = (const uint8_t*)d_text_v;
   if (format == 0) {  // first byte decides, as CFasta does
     uint8_t c = 0;
-    K4_HIP(ix, hipMemcpyAsync(&c, text, 1, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
+    K4_TRY(k4s_read_back(ix, &c, text, st));
     format = c == '@' ? K4_FASTQ : c == '>' ? K4_FASTA : 0;
     if (!format) return k4_fail(ix, K4_ERR_NOT_FASTA, "input is neither FASTA ('>') nor FASTQ ('@')");
   }
   const bool fastq = format == K4_FASTQ;
-  Buf tot, nlb, hdrb, tmp, cnt, so, ss, tcnt, toff;
+  Buf tot, nlb, hdrb, so, ss, tcnt, toff;
   K4_HIP(ix, tot.alloc(32));
-  K4_HIP(ix, cnt.alloc(8));
   K4_HIP(ix, hipMemsetAsync(tot.p, 0, 32, st));
   const uint64_t n_tiles = (text_bytes + K4_NL_TILE - 1) / K4_NL_TILE;
   K4_HIP(ix, tcnt.alloc((n_tiles + 1) * 4));
   K4_HIP(ix, toff.alloc((n_tiles + 1) * 4));
   K4_HIP(ix, hipMemsetAsync(tcnt.as<uint32_t>() + n_tiles, 0, 4, st));
   hipLaunchKernelGGL(k4k_nl_tiles, dim3((unsigned)n_tiles), dim3(256), 0, st, text, text_bytes, tcnt.as<uint32_t>());
-  {
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::exclusive_scan(nullptr, tb, tcnt.as<uint32_t>(), toff.as<uint32_t>(), 0u, (size_t)(n_tiles + 1),
-                                       rocprim::plus<uint32_t>(), st));
-    K4_HIP(ix, tmp.alloc(tb));
-    K4_HIP(ix, rocprim::exclusive_scan(tmp.p, tb, tcnt.as<uint32_t>(), toff.as<uint32_t>(), 0u, (size_t)(n_tiles + 1),
-                                       rocprim::plus<uint32_t>(), st));
-  }
+  K4_TRY(k4s_exclusive_scan<Buf>(ix, tcnt.as<uint32_t>(), toff.as<uint32_t>(), 0u, (size_t)(n_tiles + 1), rocprim::plus<uint32_t>(), st));
   uint32_t n_nl32 = 0;
   uint8_t last = 0;
   K4_HIP(ix, hipMemcpyAsync(&n_nl32, toff.as<uint32_t>() + n_tiles, 4, hipMemcpyDeviceToHost, st));
@@ -321,21 +312,11 @@ extern "C" int k4_parse_fastx_dev(k4_index* ix, const void* d_text_v, uint64_t t
     n_rec = (int64_t)std::min<uint64_t>(n_lines / 4, (uint64_t)max_records);
     if (n_rec == 0) return K4_OK;
     uint32_t e = 0;
-    K4_HIP(ix, hipMemcpyAsync(&e, nlb.as<uint32_t>() + (4 * n_rec - 1), 4, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
+    K4_TRY(k4s_read_back(ix, &e, nlb.as<uint32_t>() + (4 * n_rec - 1), st));
     consumed = std::min<uint64_t>((uint64_t)e + 1, text_bytes);
     if (final_chunk && (uint64_t)n_rec == n_lines / 4 && (uint64_t)n_rec < (uint64_t)max_records) consumed = text_bytes;
   } else {
-    K4_HIP(ix, hdrb.alloc((n_lines + 1) * 4));
-    rocprim::counting_iterator<uint32_t> lines(0);
-    IsHeaderLine pred{text, nlb.as<uint32_t>()};
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::select(nullptr, tb, lines, hdrb.as<uint32_t>(), cnt.as<uint64_t>(), (size_t)n_lines, pred, st));
-    Buf tmp2;
-    K4_HIP(ix, tmp2.alloc(tb));
-    K4_HIP(ix, rocprim::select(tmp2.p, tb, lines, hdrb.as<uint32_t>(), cnt.as<uint64_t>(), (size_t)n_lines, pred, st));
-    K4_HIP(ix, hipMemcpyAsync(&n_hdr, cnt.p, 8, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
+    K4_TRY(k4s_select_indices(ix, hdrb, (size_t)n_lines, IsHeaderLine{text, nlb.as<uint32_t>()}, st, &n_hdr));
     if (n_hdr == 0) return K4_OK;
     // a non-final chunk keeps its last record for the next call (more of its sequence may follow)
     uint64_t avail = final_chunk ? n_hdr : n_hdr - 1;
@@ -343,11 +324,9 @@ extern "C" int k4_parse_fastx_dev(k4_index* ix, const void* d_text_v, uint64_t t
     if (n_rec == 0) return K4_OK;
     if ((uint64_t)n_rec < n_hdr) {  // ends where the next header line starts
       uint32_t hl = 0, e = 0;
-      K4_HIP(ix, hipMemcpyAsync(&hl, hdrb.as<uint32_t>() + n_rec, 4, hipMemcpyDeviceToHost, st));
-      K4_HIP(ix, hipStreamSynchronize(st));
+      K4_TRY(k4s_read_back(ix, &hl, hdrb.as<uint32_t>() + n_rec, st));
       if (hl > 0) {
-        K4_HIP(ix, hipMemcpyAsync(&e, nlb.as<uint32_t>() + (hl - 1), 4, hipMemcpyDeviceToHost, st));
-        K4_HIP(ix, hipStreamSynchronize(st));
+        K4_TRY(k4s_read_back(ix, &e, nlb.as<uint32_t>() + (hl - 1), st));
         consumed = (uint64_t)e + 1;
       }
     } else
@@ -370,18 +349,12 @@ extern "C" int k4_parse_fastx_dev(k4_index* ix, const void* d_text_v, uint64_t t
     else
       hipLaunchKernelGGL(k4k_fastq_lens, dim3((unsigned)std::min<int64_t>((n_rec + 255) / 256, 4096)), dim3(256), 0, st, text,
                          so.as<uint32_t>(), ss.as<uint32_t>(), n_rec, (uint32_t*)d_lens, tot.as<unsigned long long>());
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::exclusive_scan(nullptr, tb, (const uint32_t*)d_lens, (uint64_t*)d_offs, reads_base, (size_t)n_rec,
-                                       rocprim::plus<uint64_t>(), st));
-    Buf tmp3;
-    K4_HIP(ix, tmp3.alloc(tb));
-    K4_HIP(ix, rocprim::exclusive_scan(tmp3.p, tb, (const uint32_t*)d_lens, (uint64_t*)d_offs, reads_base, (size_t)n_rec,
-                                       rocprim::plus<uint64_t>(), st));
+    K4_TRY(k4s_exclusive_scan<Buf>(ix, (const uint32_t*)d_lens, (uint64_t*)d_offs, reads_base, (size_t)n_rec, rocprim::plus<uint64_t>(), st));
     hipLaunchKernelGGL(k4k_fastx_encode, dim3((unsigned)std::min<int64_t>((n_rec + 3) / 4, 1 << 16)), dim3(64), 0, st, text, so.as<uint32_t>(),
                        ss.as<uint32_t>(), (const uint64_t*)d_offs, n_rec, (uint8_t*)d_reads,
                        exact ? (const uint32_t*)nullptr : (const uint32_t*)d_lens, reinterpret_cast<uint32_t*>(tot.as<unsigned long long>() + 3));
     K4_HIP(ix, hipGetLastError());
-    K4_HIP(ix, hipStreamSynchronize(st));  // tmp3 is released here
+    K4_HIP(ix, hipStreamSynchronize(st));
     if (exact) break;
     uint32_t mis = 0;
     K4_HIP(ix, hipMemcpy(&mis, tot.as<unsigned long long>() + 3, 4, hipMemcpyDeviceToHost));
@@ -395,8 +368,7 @@ extern "C" int k4_parse_fastx_dev(k4_index* ix, const void* d_text_v, uint64_t t
                        (const uint64_t*)d_offs, (const uint32_t*)d_lens, n_rec, (uint8_t*)d_reads, (const uint8_t*)ix->d_qlut,
                        reinterpret_cast<uint32_t*>(tot.as<unsigned long long>() + 3));
     uint32_t mis = 0;
-    K4_HIP(ix, hipMemcpyAsync(&mis, tot.as<unsigned long long>() + 3, 4, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
+    K4_TRY(k4s_read_back(ix, &mis, tot.as<unsigned long long>() + 3, st));
     if (mis) return k4_fail(ix, K4_ERR_PARSE, "%u FASTQ records whose quality line is not as long as the read", mis);
   }
   unsigned long long t[3] = {0, 0, 0};
@@ -564,9 +536,6 @@ struct K4SamFields {
   uint32_t op_len[7];  // CIGAR, at most S M S  gap  S M S (ReportBAMread, KAligner.cpp:6148-6225)
   char op[7];
 };
-// CKAligner::AdjAlignStartLoci / AdjAlignHitLen / AdjStartLoci / AdjHitLen (KAligner.cpp:1633-1693) on the flat records
-K4_DEV uint32_t k4d_adj_start(const k4_hit& h) { return h.match_loci + (h.strand == '+' ? K4_HIT_TRIM_LEFT(h) : K4_HIT_TRIM_RIGHT(h)); }
-K4_DEV uint32_t k4d_adj_len0(const k4_hit& h) { return (uint32_t)h.match_len - K4_HIT_TRIM_LEFT(h) - K4_HIT_TRIM_RIGHT(h); }
 K4_DEV bool k4d_two_segs(const k4_hit& h) { return (h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE)) != 0; }
 K4_DEV k4_seg2 k4d_sam_seg2(const K4SamArgs& a, int64_t i, const k4_hit& h) {
   k4_seg2 z = {0, 0, 0, 0, 0, 0, 0};
@@ -581,7 +550,7 @@ K4_DEV K4SamFields k4d_sam_fields(const K4SamArgs& a, int64_t v, const k4_hit& h
   const bool two = !a.pe && a.seg2 && k4d_two_segs(h);
   const k4_seg2 s2 = k4d_sam_seg2(a, i, h);
   const uint32_t tl = K4_HIT_TRIM_LEFT(h), tr = K4_HIT_TRIM_RIGHT(h);
-  const uint32_t len0 = k4d_adj_len0(h), len1 = two ? s2.match_len : 0u;
+  const uint32_t len0 = k4d_adj_len(h), len1 = two ? s2.match_len : 0u;
   f.pos = k4d_adj_start(h) + 1;
   f.aligned = len0 + len1;
   f.n_ops = 0;
@@ -617,7 +586,7 @@ K4_DEV K4SamFields k4d_sam_fields(const K4SamArgs& a, int64_t v, const k4_hit& h
     f.mate_eq = true;
     f.pnext = k4d_adj_start(mt.hit) + 1;
     const int64_t s = k4d_adj_start(h), e = k4d_adj_start(mt.hit);
-    f.tlen = (int32_t)(s <= e ? (e - s) + k4d_adj_len0(mt.hit) : (s - e) + len0);
+    f.tlen = (int32_t)(s <= e ? (e - s) + k4d_adj_len(mt.hit) : (s - e) + len0);
   } else
     f.flag |= 0x8u;
   return f;
@@ -648,7 +617,7 @@ __global__ void __launch_bounds__(256) k4k_sam_key_minor(K4SamArgs a, const uint
   // AdjHitLen(Seg[0]), Strand, then the READ's LowMMCnt (both segments' mismatches for a two-segment hit)
   const int64_t i = k4d_sam_read(a, v);
   const uint32_t mm = a.pe ? h.mismatches : (k4d_two_segs(h) ? (uint32_t)a.rr[i].low_mm & 0xFFu : h.mismatches);
-  key[j] = (k4d_adj_len0(h) << 16) | ((uint32_t)h.strand << 8) | mm;
+  key[j] = (k4d_adj_len(h) << 16) | ((uint32_t)h.strand << 8) | mm;
 }
 __global__ void __launch_bounds__(256) k4k_sam_key_major(K4SamArgs a, const uint32_t* __restrict__ idx, uint64_t m, uint64_t* __restrict__ key) {
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1090,17 +1059,14 @@ extern "C" int k4_unaligned_fasta_dev(k4_index* ix, int pe, int64_t n_units, con
     a.text[w] = (const uint8_t*)names->d_text[w]; a.name_off[w] = (const uint64_t*)names->d_name_off[w];
     a.name_len[w] = (const uint32_t*)names->d_name_len[w];
   }
-  Buf ids, idx, cnt, tmp, ll, lo, outb;
+  Buf ids, idx, cnt, ll, lo, outb;
   K4_HIP(ix, ids.alloc((size_t)(n_reads + 1) * 4));
   K4_HIP(ix, idx.alloc((size_t)n_reads * 4));
   K4_HIP(ix, cnt.alloc(8));
   {  // ReadID - 1: the loaded reads before this one
     rocprim::counting_iterator<uint32_t> all(0);
     auto loaded = rocprim::make_transform_iterator(all, IsLoaded{a.lens});
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::exclusive_scan(nullptr, tb, loaded, ids.as<uint32_t>(), 0u, (size_t)n_reads, rocprim::plus<uint32_t>(), st));
-    K4_HIP(ix, tmp.alloc(tb));
-    K4_HIP(ix, rocprim::exclusive_scan(tmp.p, tb, loaded, ids.as<uint32_t>(), 0u, (size_t)n_reads, rocprim::plus<uint32_t>(), st));
+    K4_TRY(k4s_exclusive_scan<Buf>(ix, loaded, ids.as<uint32_t>(), 0u, (size_t)n_reads, rocprim::plus<uint32_t>(), st));
   }
   uint64_t m = 0;
   const int nars[2][2] = {{K4_NAR_NS, K4_NAR_NOHIT}, {K4_NAR_MULTIALIGN, -1}};
@@ -1108,14 +1074,9 @@ extern "C" int k4_unaligned_fasta_dev(k4_index* ix, int pe, int64_t n_units, con
     if (nars[which][g] < 0) continue;
     rocprim::counting_iterator<uint32_t> all(0);
     NarIs pred{a, nars[which][g]};
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::select(nullptr, tb, all, idx.as<uint32_t>() + m, cnt.as<uint64_t>(), (size_t)n_reads, pred, st));
-    Buf t2;
-    K4_HIP(ix, t2.alloc(tb));
-    K4_HIP(ix, rocprim::select(t2.p, tb, all, idx.as<uint32_t>() + m, cnt.as<uint64_t>(), (size_t)n_reads, pred, st));
+    K4_TRY(k4s_select<Buf>(ix, all, idx.as<uint32_t>() + m, cnt.as<uint64_t>(), (size_t)n_reads, pred, st));
     uint64_t got = 0;
-    K4_HIP(ix, hipMemcpyAsync(&got, cnt.p, 8, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
+    K4_TRY(k4s_read_back(ix, &got, cnt.p, st));
     m += got;
   }
   if (n_listed) *n_listed = m;
@@ -1125,16 +1086,9 @@ extern "C" int k4_unaligned_fasta_dev(k4_index* ix, int pe, int64_t n_units, con
   K4_HIP(ix, hipMemsetAsync(ll.as<uint32_t>() + m, 0, 4, st));
   const unsigned mb = (unsigned)((m + 255) / 256);
   hipLaunchKernelGGL(k4k_fasta_lens, dim3(mb), dim3(256), 0, st, a, idx.as<uint32_t>(), ids.as<uint32_t>(), m, ll.as<uint32_t>());
-  {
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::exclusive_scan(nullptr, tb, ll.as<uint32_t>(), lo.as<uint64_t>(), (uint64_t)0, (size_t)(m + 1), rocprim::plus<uint64_t>(), st));
-    Buf t3;
-    K4_HIP(ix, t3.alloc(tb));
-    K4_HIP(ix, rocprim::exclusive_scan(t3.p, tb, ll.as<uint32_t>(), lo.as<uint64_t>(), (uint64_t)0, (size_t)(m + 1), rocprim::plus<uint64_t>(), st));
-  }
+  K4_TRY(k4s_exclusive_scan<Buf>(ix, ll.as<uint32_t>(), lo.as<uint64_t>(), (uint64_t)0, (size_t)(m + 1), rocprim::plus<uint64_t>(), st));
   uint64_t total = 0;
-  K4_HIP(ix, hipMemcpyAsync(&total, lo.as<uint64_t>() + m, 8, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
+  K4_TRY(k4s_read_back(ix, &total, lo.as<uint64_t>() + m, st));
   K4_HIP(ix, outb.alloc(total + 16));
   hipLaunchKernelGGL(k4k_fasta_write, dim3(mb), dim3(256), 0, st, a, idx.as<uint32_t>(), ids.as<uint32_t>(), m, lo.as<uint64_t>(), (int)which, outb.as<char>());
   char* h = (char*)malloc(total + 1);
@@ -1249,26 +1203,14 @@ int k4i_format_records(k4_index* ix, int bam, int sq_all, int pe, int64_t n_unit
   a.all_reads = all_reads ? 1 : 0;
   a.quals = ix->q_method != 3 ? 1 : 0;
 
-  Buf stb, chb, cnt, idx0, idx1, k32a, k32b, k64a, k64b, tmp, ll, lo;
+  Buf stb, chb, idx0, idx1, k32a, k32b, k64a, k64b, ll, lo;
   K4_HIP(ix, stb.alloc(22 * 8));
   K4_HIP(ix, chb.alloc(ne + 1));
-  K4_HIP(ix, cnt.alloc(8));
   K4_HIP(ix, hipMemsetAsync(stb.p, 0, 22 * 8, st));
   K4_HIP(ix, hipMemsetAsync(chb.p, 0, ne + 1, st));
   hipLaunchKernelGGL(k4k_sam_stats, dim3(2048), dim3(256), 0, st, a, stb.as<unsigned long long>(), chb.as<uint8_t>());
-  // accepted reads, in load order
-  K4_HIP(ix, idx0.alloc((size_t)n_virt * 4));
-  {
-    rocprim::counting_iterator<uint32_t> all(0);
-    IsAccepted pred{a};
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::select(nullptr, tb, all, idx0.as<uint32_t>(), cnt.as<uint64_t>(), (size_t)n_virt, pred, st));
-    K4_HIP(ix, tmp.alloc(tb));
-    K4_HIP(ix, rocprim::select(tmp.p, tb, all, idx0.as<uint32_t>(), cnt.as<uint64_t>(), (size_t)n_virt, pred, st));
-  }
-  uint64_t m = 0;
-  K4_HIP(ix, hipMemcpyAsync(&m, cnt.p, 8, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
+  uint64_t m = 0;  // accepted reads, in load order
+  K4_TRY(k4s_select_indices(ix, idx0, (size_t)n_virt, IsAccepted{a}, st, &m));
   unsigned long long hs[22];
   K4_HIP(ix, hipMemcpy(hs, stb.p, sizeof(hs), hipMemcpyDeviceToHost));
   if (stats) {
@@ -1304,20 +1246,12 @@ int k4i_format_records(k4_index* ix, int bam, int sq_all, int pe, int64_t n_unit
   {
     rocprim::double_buffer<uint32_t> kb(k32a.as<uint32_t>(), k32b.as<uint32_t>());
     rocprim::double_buffer<uint32_t> vb(idx0.as<uint32_t>(), idx1.as<uint32_t>());
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::radix_sort_pairs(nullptr, tb, kb, vb, (size_t)m, 0u, 32u, st));
-    Buf t2;
-    K4_HIP(ix, t2.alloc(tb));
-    K4_HIP(ix, rocprim::radix_sort_pairs(t2.p, tb, kb, vb, (size_t)m, 0u, 32u, st));
+    K4_TRY(k4s_sort_pairs<Buf>(ix, kb, vb, (size_t)m, 0u, 32u, st));
     hipLaunchKernelGGL(k4k_sam_key_major, dim3(mb), dim3(256), 0, st, a, vb.current(), m, k64a.as<uint64_t>());
     rocprim::double_buffer<uint64_t> kb2(k64a.as<uint64_t>(), k64b.as<uint64_t>());
-    size_t tb2 = 0;
     unsigned top = 33;  // key = chrom << 32 | start: only the bits chromosome ids can reach are sorted on
     while (top < 64 && ((a.n_entries + (all_reads ? 33u : 0u)) >> (top - 32)) != 0) top++;
-    K4_HIP(ix, rocprim::radix_sort_pairs(nullptr, tb2, kb2, vb, (size_t)m, 0u, top, st));
-    Buf t3;
-    K4_HIP(ix, t3.alloc(tb2));
-    K4_HIP(ix, rocprim::radix_sort_pairs(t3.p, tb2, kb2, vb, (size_t)m, 0u, top, st));
+    K4_TRY(k4s_sort_pairs<Buf>(ix, kb2, vb, (size_t)m, 0u, top, st));
     K4_HIP(ix, hipStreamSynchronize(st));
     order = vb.current();
   }
@@ -1327,16 +1261,8 @@ int k4i_format_records(k4_index* ix, int bam, int sq_all, int pe, int64_t n_unit
   K4_HIP(ix, hipMemsetAsync(ll.as<uint32_t>() + m, 0, 4, st));
   if (bam) hipLaunchKernelGGL(k4k_sam_line_lens<true>, dim3(mb), dim3(256), 0, st, a, order, m, ll.as<uint32_t>());
   else hipLaunchKernelGGL(k4k_sam_line_lens<false>, dim3(mb), dim3(256), 0, st, a, order, m, ll.as<uint32_t>());
-  {
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::exclusive_scan(nullptr, tb, ll.as<uint32_t>(), lo.as<uint64_t>(), (uint64_t)0, (size_t)(m + 1),
-                                       rocprim::plus<uint64_t>(), st));
-    Buf t4;
-    K4_HIP(ix, t4.alloc(tb));
-    K4_HIP(ix, rocprim::exclusive_scan(t4.p, tb, ll.as<uint32_t>(), lo.as<uint64_t>(), (uint64_t)0, (size_t)(m + 1),
-                                       rocprim::plus<uint64_t>(), st));
-    K4_HIP(ix, hipStreamSynchronize(st));
-  }
+  K4_TRY(k4s_exclusive_scan<Buf>(ix, ll.as<uint32_t>(), lo.as<uint64_t>(), (uint64_t)0, (size_t)(m + 1), rocprim::plus<uint64_t>(), st));
+  K4_HIP(ix, hipStreamSynchronize(st));
   // slices of consecutive lines (one when the caller waits for the whole body anyway): their byte bounds come down with the total
   const int n_sl = slices ? (int)std::min<uint64_t>(16, std::max<uint64_t>(m >> 16, 1)) : 1;
   std::vector<uint64_t> line_end((size_t)n_sl), byte_end((size_t)n_sl);

@@ -21,34 +21,19 @@
 #include <string.h>
 #include <algorithm>
 #include <rocprim/rocprim.hpp>
-#include "k4_internal.h"
-#include "k4_pool.h"
+#include "k4_device.h"
+#include "k4_stage.h"
 
 namespace {
-
-struct Buf {
-  void* p = nullptr;
-  ~Buf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t bytes) { return k4_malloc_retry(&p, bytes ? bytes : 1); }
-  template <typename T> T* as() { return (T*)p; }
-};
 
 struct IsUniqueAccepted {  // the reads the walk looks at: accepted, one hit (SE: every accepted read before -x / -r5)
   const k4_read_result* rr;
   __device__ bool operator()(uint32_t i) const { return rr[i].nar == K4_NAR_ACCEPTED && rr[i].num_hits == 1; }
 };
 
-// AdjStartLoci / AdjHitLen (KAligner.cpp:1634-1655): the trimmed span of Seg[0]
-__device__ __forceinline__ uint32_t adj_start(const k4_hit& h) {
-  const uint32_t tl = h.ext & 0xFFFu, tr = (h.ext >> 12) & 0xFFFu;
-  return h.match_loci + (h.strand == '+' ? tl : tr);
-}
-__device__ __forceinline__ uint32_t adj_len(const k4_hit& h) {
-  return (uint32_t)h.match_len - (h.ext & 0xFFFu) - ((h.ext >> 12) & 0xFFFu);
-}
 // major key: chrom (bits 33..), strand (bit 32: '-' after '+'), AdjStartLoci (bits 0..31)
 __device__ __forceinline__ uint64_t site_key(const k4_hit& h) {
-  return ((uint64_t)h.chrom_id << 33) | ((uint64_t)(h.strand == '-') << 32) | adj_start(h);
+  return ((uint64_t)h.chrom_id << 33) | ((uint64_t)(h.strand == '-') << 32) | k4d_adj_start(h);
 }
 
 __global__ void __launch_bounds__(256) k4k_pcr_minor_keys(uint32_t m, const uint32_t* __restrict__ idx, const k4_read_result* __restrict__ rr,
@@ -57,7 +42,7 @@ __global__ void __launch_bounds__(256) k4k_pcr_minor_keys(uint32_t m, const uint
   if (j >= m) return;
   const uint32_t i = idx[j];
   const int32_t mm = rr[i].low_mm;
-  minor[j] = (adj_len(hits[(int64_t)i * max_ml]) << 16) | (uint32_t)min(max(mm, 0), 0xFFFF);
+  minor[j] = (k4d_adj_len(hits[(int64_t)i * max_ml]) << 16) | (uint32_t)min(max(mm, 0), 0xFFFF);
 }
 
 __global__ void __launch_bounds__(256) k4k_pcr_major_keys(uint32_t m, const uint32_t* __restrict__ idx, const k4_hit* __restrict__ hits, int max_ml,
@@ -82,7 +67,7 @@ __global__ void __launch_bounds__(256) k4k_pcr_heads(uint32_t m, const uint32_t*
   bool site = j == 0, run = j == 0;
   if (j) {
     site = major[j] != major[j - 1];
-    run = site || adj_len(hits[(int64_t)order[j] * max_ml]) != adj_len(hits[(int64_t)order[j - 1] * max_ml]);
+    run = site || k4d_adj_len(hits[(int64_t)order[j] * max_ml]) != k4d_adj_len(hits[(int64_t)order[j - 1] * max_ml]);
   }
   out[j] = {site ? 1u : 0u, run ? j : 0u};
 }
@@ -157,25 +142,15 @@ extern "C" int k4_reduce_pcr_dups_dev(k4_index* ix, int32_t win_len, int64_t n_r
   hipStream_t st = (hipStream_t)stream;
   const k4_read_result* rr = (const k4_read_result*)d_rr;
   const k4_hit* hits = (const k4_hit*)d_hits;
-  Buf idx0, idx1, cnt, tmp;
-  K4_HIP(ix, idx0.alloc((size_t)n_reads * 4));
-  K4_HIP(ix, cnt.alloc(16));
-  K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 16, st));
-  {  // the accepted reads, in load order
-    rocprim::counting_iterator<uint32_t> all(0);
-    size_t tb = 0;
-    IsUniqueAccepted pred{rr};
-    K4_HIP(ix, rocprim::select(nullptr, tb, all, idx0.as<uint32_t>(), cnt.as<uint64_t>(), (size_t)n_reads, pred, st));
-    K4_HIP(ix, tmp.alloc(tb));
-    K4_HIP(ix, rocprim::select(tmp.p, tb, all, idx0.as<uint32_t>(), cnt.as<uint64_t>(), (size_t)n_reads, pred, st));
-  }
-  uint64_t m64 = 0;
-  K4_HIP(ix, hipMemcpyAsync(&m64, cnt.p, 8, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
+  K4DevBuf idx0, idx1, cnt;
+  K4_HIP(ix, cnt.alloc(8));
+  K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 8, st));
+  uint64_t m64 = 0;  // the accepted reads, in load order
+  K4_TRY(k4s_select_indices(ix, idx0, (size_t)n_reads, IsUniqueAccepted{rr}, st, &m64));
   if (m64 < 2) return K4_OK;  // a lone read is the head of its run
   const uint32_t m = (uint32_t)m64;
   const unsigned nb = (m + 255u) / 256u;
-  Buf mk0, mk1, kk0, kk1, sr, srs, sites, lim;
+  K4DevBuf mk0, mk1, kk0, kk1, sr, srs, sites, lim;
   K4_HIP(ix, idx1.alloc((size_t)m * 4));
   K4_HIP(ix, mk0.alloc((size_t)m * 4));
   K4_HIP(ix, mk1.alloc((size_t)m * 4));
@@ -186,24 +161,11 @@ extern "C" int k4_reduce_pcr_dups_dev(k4_index* ix, int32_t win_len, int64_t n_r
   K4_HIP(ix, hipGetLastError());
   rocprim::double_buffer<uint32_t> mk(mk0.as<uint32_t>(), mk1.as<uint32_t>());
   rocprim::double_buffer<uint32_t> vb(idx0.as<uint32_t>(), idx1.as<uint32_t>());
-  {
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::radix_sort_pairs(nullptr, tb, mk, vb, (size_t)m, 0u, 32u, st));
-    Buf t2;
-    K4_HIP(ix, t2.alloc(tb));
-    K4_HIP(ix, rocprim::radix_sort_pairs(t2.p, tb, mk, vb, (size_t)m, 0u, 32u, st));
-  }
+  K4_TRY(k4s_sort_pairs<K4DevBuf>(ix, mk, vb, (size_t)m, 0u, 32u, st));
   hipLaunchKernelGGL(k4k_pcr_major_keys, dim3(nb), dim3(256), 0, st, m, vb.current(), hits, (int)max_ml, kk0.as<uint64_t>());
   K4_HIP(ix, hipGetLastError());
   rocprim::double_buffer<uint64_t> kk(kk0.as<uint64_t>(), kk1.as<uint64_t>());
-  {
-    const unsigned end_bit = 64u;  // (chrom ids are the index's EntryIDs: any 32-bit value)
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::radix_sort_pairs(nullptr, tb, kk, vb, (size_t)m, 0u, end_bit, st));
-    Buf t3;
-    K4_HIP(ix, t3.alloc(tb));
-    K4_HIP(ix, rocprim::radix_sort_pairs(t3.p, tb, kk, vb, (size_t)m, 0u, end_bit, st));
-  }
+  K4_TRY(k4s_sort_pairs<K4DevBuf>(ix, kk, vb, (size_t)m, 0u, 64u, st));  // (chrom ids are the index's EntryIDs: any 32-bit value)
   const uint32_t* order = vb.current();
   const uint64_t* major = kk.current();
   // 2. site numbers and run heads
@@ -211,13 +173,7 @@ extern "C" int k4_reduce_pcr_dups_dev(k4_index* ix, int32_t win_len, int64_t n_r
   K4_HIP(ix, srs.alloc((size_t)m * sizeof(SiteRun)));
   hipLaunchKernelGGL(k4k_pcr_heads, dim3(nb), dim3(256), 0, st, m, order, major, hits, (int)max_ml, sr.as<SiteRun>());
   K4_HIP(ix, hipGetLastError());
-  {
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::inclusive_scan(nullptr, tb, sr.as<SiteRun>(), srs.as<SiteRun>(), (size_t)m, SiteRunOp(), st));
-    Buf t4;
-    K4_HIP(ix, t4.alloc(tb));
-    K4_HIP(ix, rocprim::inclusive_scan(t4.p, tb, sr.as<SiteRun>(), srs.as<SiteRun>(), (size_t)m, SiteRunOp(), st));
-  }
+  K4_TRY(k4s_inclusive_scan<K4DevBuf>(ix, sr.as<SiteRun>(), srs.as<SiteRun>(), (size_t)m, SiteRunOp(), st));
   // 3. LimitDups per site (WinLen 0: LimitDups 0 everywhere)
   const int32_t* d_lim = nullptr;
   if (win_len > 0) {
@@ -231,11 +187,10 @@ extern "C" int k4_reduce_pcr_dups_dev(k4_index* ix, int32_t win_len, int64_t n_r
   }
   // 4. the reads ranked behind their run's limit
   hipLaunchKernelGGL(k4k_pcr_mark, dim3(nb), dim3(256), 0, st, m, order, srs.as<SiteRun>(), d_lim, (k4_read_result*)d_rr,
-                     cnt.as<unsigned long long>() + 1);
+                     cnt.as<unsigned long long>());
   K4_HIP(ix, hipGetLastError());
   unsigned long long c = 0;
-  K4_HIP(ix, hipMemcpyAsync(&c, cnt.as<unsigned long long>() + 1, 8, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
+  K4_TRY(k4s_read_back(ix, &c, cnt.p, st));
   if (n_dups) *n_dups = (int64_t)c;
   return K4_OK;
 }

@@ -388,15 +388,11 @@ K4_DEV int k4d_pe_insert_size(const k4_pe_params& pe, uint8_t s1, uint32_t st1, 
   if (frag > pe.pair_max_len) return -7;
   return frag;
 }
-// AdjStartLoci / AdjEndLoci (KAligner.cpp:1633-1650): a chimeric hit counts from / to its trimmed ends
-K4_DEV uint32_t k4d_pe_adj_start(const k4_hit& h) { return h.match_loci + (h.strand == '+' ? K4_HIT_TRIM_LEFT(h) : K4_HIT_TRIM_RIGHT(h)); }
-K4_DEV uint32_t k4d_pe_adj_end(const k4_hit& h) {
-  return h.match_loci + ((uint32_t)h.match_len - (h.strand == '+' ? K4_HIT_TRIM_RIGHT(h) : K4_HIT_TRIM_LEFT(h)) - 1);
-}
+// (k4d_adj_start / k4d_adj_end: a chimeric hit counts from / to its trimmed ends)
 K4_DEV int k4d_accept_prov_pe(const k4_pe_params& pe, int nh1, const k4_hit& h1, int nh2, const k4_hit& h2) {  // :2799-2861
   if (!(nh1 == 1 && nh2 == 1)) return 0;
   if (h1.chrom_id != h2.chrom_id) return -2;
-  return k4d_pe_insert_size(pe, h1.strand, k4d_pe_adj_start(h1), k4d_pe_adj_end(h1), h2.strand, k4d_pe_adj_start(h2), k4d_pe_adj_end(h2));
+  return k4d_pe_insert_size(pe, h1.strand, k4d_adj_start(h1), k4d_adj_end(h1), h2.strand, k4d_adj_start(h2), k4d_adj_end(h2));
 }
 struct K4PeChim { int min_chimeric_len, min_core_len, slides_per100, min_edit_dist; };  // AlignPairedRead's chimeric mode (0: off)
 K4_DEV bool k4d_pe_unaligned(int nar) { return nar == K4_NAR_NS || nar == K4_NAR_NOHIT || nar == K4_NAR_UNALIGNED; }
@@ -547,8 +543,8 @@ __global__ void __launch_bounds__(64) k4k_pe_orphans(K4DevIndex ix, k4_pe_params
         if (pe.pair_strand) { tk.b3prime_extend = !tk.b3prime_extend; tk.antisense = !tk.antisense; }
       }
       tk.chrom_id = anchor.hit.chrom_id;
-      tk.start_loci = k4d_pe_adj_start(anchor.hit);  // OrphStartLoci / OrphEndLoci (:3354-3355)
-      tk.end_loci = k4d_pe_adj_end(anchor.hit);
+      tk.start_loci = k4d_adj_start(anchor.hit);  // OrphStartLoci / OrphEndLoci (:3354-3355)
+      tk.end_loci = k4d_adj_end(anchor.hit);
       const int64_t mate = round == 0 ? 2 * i + 1 : 2 * i;
       tk.read_len = lens[mate];
       tk.read_off = offs[mate];
@@ -566,7 +562,7 @@ __global__ void __launch_bounds__(64) k4k_pe_orphans(K4DevIndex ix, k4_pe_params
       k4_hit h;
       const int res = k4d_mate_rescue(ix, tk, reads, lane, rs, h, mk);
       if (res != 1) continue;
-      const uint32_t hs = k4d_pe_adj_start(h), he = k4d_pe_adj_end(h);  // (:3390, :3492)
+      const uint32_t hs = k4d_adj_start(h), he = k4d_adj_end(h);  // (:3390, :3492)
       const uint32_t as = tk.start_loci, ae = tk.end_loci;
       const int frag = round == 0 ? k4d_pe_insert_size(pe, anchor.hit.strand, as, ae, h.strand, hs, he)
                                   : k4d_pe_insert_size(pe, h.strand, hs, he, anchor.hit.strand, as, ae);

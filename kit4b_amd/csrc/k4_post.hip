@@ -10,16 +10,9 @@
 #include <rocprim/rocprim.hpp>
 #include "k4_device.h"
 #include "k4_internal.h"
-#include "k4_pool.h"
+#include "k4_stage.h"
 
 namespace {
-
-struct Buf {
-  void* p = nullptr;
-  ~Buf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t bytes) { return k4_malloc_retry(&p, bytes ? bytes : 1); }
-  template <typename T> T* as() { return (T*)p; }
-};
 
 // read symbol j of the alignment in READ orientation: the target is reverse-complemented for a '-' hit (:1802-1805)
 K4_DEV uint32_t k4d_targ_in_read_sense(const K4DevIndex& ix, uint64_t base, uint32_t len, bool minus, uint32_t j) {
@@ -136,7 +129,7 @@ extern "C" int k4_auto_trim_flanks_dev(k4_index* ix, int32_t min_flank_exacts, i
   if (!d_rr || (!pe && (!d_hits || max_ml < 1)) || !d_reads || !d_offs || !d_lens) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
-  Buf cnt;
+  K4DevBuf cnt;
   K4_HIP(ix, cnt.alloc(8));
   K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 8, st));
   // PE: d_rr holds k4_pe_read records (hit inside); SE: k4_read_result + the hit slots
@@ -146,8 +139,7 @@ extern "C" int k4_auto_trim_flanks_dev(k4_index* ix, int32_t min_flank_exacts, i
                      cnt.as<unsigned long long>());
   K4_HIP(ix, hipGetLastError());
   unsigned long long c = 0;
-  K4_HIP(ix, hipMemcpyAsync(&c, cnt.p, 8, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
+  K4_TRY(k4s_read_back(ix, &c, cnt.p, st));
   if (n_eliminated) *n_eliminated = (int64_t)c;
   return K4_OK;
 }
@@ -162,72 +154,44 @@ extern "C" int k4_remove_orphan_juncts_dev(k4_index* ix, uint32_t which, int64_t
   if (n_reads >= 0xFFFFFF00ll) return k4_fail(ix, K4_ERR_PARAMS, "at most 2^32-256 reads per call");
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
-  Buf idx0, idx1, cnt, tmp, ka, kb, ma, mb2;
-  K4_HIP(ix, idx0.alloc((size_t)n_reads * 4));
-  K4_HIP(ix, cnt.alloc(16));
-  K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 16, st));
-  {
-    rocprim::counting_iterator<uint32_t> all(0);
-    IsJunct pred{(const k4_read_result*)d_rr, (const k4_hit*)d_hits, (int)max_ml, which};
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::select(nullptr, tb, all, idx0.as<uint32_t>(), cnt.as<uint64_t>(), (size_t)n_reads, pred, st));
-    K4_HIP(ix, tmp.alloc(tb));
-    K4_HIP(ix, rocprim::select(tmp.p, tb, all, idx0.as<uint32_t>(), cnt.as<uint64_t>(), (size_t)n_reads, pred, st));
-  }
+  K4DevBuf idx0, idx1, cnt, ka, kb, ma, mb2;
+  K4_HIP(ix, cnt.alloc(8));
+  K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 8, st));
   uint64_t m = 0;
-  K4_HIP(ix, hipMemcpyAsync(&m, cnt.p, 8, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
+  K4_TRY(k4s_select_indices(ix, idx0, (size_t)n_reads, IsJunct{(const k4_read_result*)d_rr, (const k4_hit*)d_hits, (int)max_ml, which}, st, &m));
   if (m == 0) return K4_OK;
-  K4_HIP(ix, idx1.alloc(m * 4));
-  K4_HIP(ix, ka.alloc(m * 8));
-  K4_HIP(ix, kb.alloc(m * 8));
-  K4_HIP(ix, ma.alloc(m * 4));
-  K4_HIP(ix, mb2.alloc(m * 4));
   const unsigned nb = (unsigned)((m + 255) / 256);
   const uint32_t* order = idx0.as<uint32_t>();
-  if (m > 1) {
+  if (m > 1) {  // (a lone junction is an orphan, :2482-2489: nothing to sort, no neighbour to test)
+    K4_HIP(ix, idx1.alloc(m * 4));
+    K4_HIP(ix, ka.alloc(m * 8));
+    K4_HIP(ix, kb.alloc(m * 8));
+    K4_HIP(ix, ma.alloc(m * 4));
+    K4_HIP(ix, mb2.alloc(m * 4));
     // SortSegJuncts (KAligner.cpp:11104): chrom, start, end -- two stable radix sorts, the minor key first; the keys travel
     // with the values so that they are in sorted order for the neighbour test
     hipLaunchKernelGGL(k4k_junct_keys, dim3(nb), dim3(256), 0, st, m, idx0.as<uint32_t>(), (const k4_hit*)d_hits, (int)max_ml,
                        (const k4_seg2*)d_seg2, ka.as<uint64_t>(), ma.as<uint32_t>());
     rocprim::double_buffer<uint32_t> mk(ma.as<uint32_t>(), mb2.as<uint32_t>());
     rocprim::double_buffer<uint32_t> vb(idx0.as<uint32_t>(), idx1.as<uint32_t>());
-    size_t tb = 0;
-    K4_HIP(ix, rocprim::radix_sort_pairs(nullptr, tb, mk, vb, (size_t)m, 0u, 32u, st));
-    Buf t2;
-    K4_HIP(ix, t2.alloc(tb));
-    K4_HIP(ix, rocprim::radix_sort_pairs(t2.p, tb, mk, vb, (size_t)m, 0u, 32u, st));
+    K4_TRY(k4s_sort_pairs<K4DevBuf>(ix, mk, vb, (size_t)m, 0u, 32u, st));
     // keys of the values in their new order
     hipLaunchKernelGGL(k4k_junct_keys, dim3(nb), dim3(256), 0, st, m, vb.current(), (const k4_hit*)d_hits, (int)max_ml,
                        (const k4_seg2*)d_seg2, ka.as<uint64_t>(), mk.alternate());
     rocprim::double_buffer<uint64_t> kk(ka.as<uint64_t>(), kb.as<uint64_t>());
-    size_t tb2 = 0;
-    K4_HIP(ix, rocprim::radix_sort_pairs(nullptr, tb2, kk, vb, (size_t)m, 0u, 64u, st));
-    Buf t3;
-    K4_HIP(ix, t3.alloc(tb2));
-    K4_HIP(ix, rocprim::radix_sort_pairs(t3.p, tb2, kk, vb, (size_t)m, 0u, 64u, st));
+    K4_TRY(k4s_sort_pairs<K4DevBuf>(ix, kk, vb, (size_t)m, 0u, 64u, st));
     order = vb.current();
     uint32_t* minor_sorted = mk.alternate();
     hipLaunchKernelGGL(k4k_junct_keys, dim3(nb), dim3(256), 0, st, m, order, (const k4_hit*)d_hits, (int)max_ml, (const k4_seg2*)d_seg2,
                        kk.alternate(), minor_sorted);
     hipLaunchKernelGGL(k4k_junct_mark, dim3(nb), dim3(256), 0, st, m, order, (const uint64_t*)kk.alternate(), (const uint32_t*)minor_sorted,
                        (k4_hit*)d_hits, (int)max_ml);
-    hipLaunchKernelGGL(k4k_junct_drop, dim3(nb), dim3(256), 0, st, m, order, (const k4_hit*)d_hits, (int)max_ml, (k4_read_result*)d_rr,
-                       which == K4_EXT_SPLICE ? K4_NAR_SPLICEJCTN : K4_NAR_MICROINDEL, cnt.as<unsigned long long>() + 1);
-    K4_HIP(ix, hipGetLastError());
-    unsigned long long c = 0;
-    K4_HIP(ix, hipMemcpyAsync(&c, cnt.as<unsigned long long>() + 1, 8, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
-    if (n_removed) *n_removed = (int64_t)c;
-    return K4_OK;
   }
-  // a lone junction is an orphan (:2482-2489)
   hipLaunchKernelGGL(k4k_junct_drop, dim3(nb), dim3(256), 0, st, m, order, (const k4_hit*)d_hits, (int)max_ml, (k4_read_result*)d_rr,
-                     which == K4_EXT_SPLICE ? K4_NAR_SPLICEJCTN : K4_NAR_MICROINDEL, cnt.as<unsigned long long>() + 1);
+                     which == K4_EXT_SPLICE ? K4_NAR_SPLICEJCTN : K4_NAR_MICROINDEL, cnt.as<unsigned long long>());
   K4_HIP(ix, hipGetLastError());
   unsigned long long c = 0;
-  K4_HIP(ix, hipMemcpyAsync(&c, cnt.as<unsigned long long>() + 1, 8, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
+  K4_TRY(k4s_read_back(ix, &c, cnt.p, st));
   if (n_removed) *n_removed = (int64_t)c;
   return K4_OK;
 }

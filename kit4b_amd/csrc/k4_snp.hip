@@ -25,7 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 #include "k4_device.h"
-#include "k4_pool.h"
+#include "k4_stage.h"
 
 namespace {
 
@@ -58,9 +58,9 @@ __global__ void __launch_bounds__(256) k4k_snp_pileup(SnpArgs a) {
     if (nar != K4_NAR_ACCEPTED) continue;
     const k4_hit h = a.pe ? a.pr[i].hit : a.hits[i * a.max_ml];
     if (h.chrom_id != a.chrom_id || (h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE))) continue;
-    const uint32_t tl = K4_HIT_TRIM_LEFT(h), tr = K4_HIT_TRIM_RIGHT(h);
-    uint32_t match_len = (uint32_t)h.match_len - tl - tr;                 // AdjHitLen
-    const uint32_t loci0 = h.match_loci + (h.strand == '+' ? tl : tr);   // AdjStartLoci
+    const uint32_t tl = K4_HIT_TRIM_LEFT(h);
+    uint32_t match_len = k4d_adj_len(h);
+    const uint32_t loci0 = k4d_adj_start(h);
     if ((uint64_t)loci0 + match_len > a.clen) continue;                  // (GetSeq comes back short: the read is skipped, :8420)
     const uint8_t* src = a.reads + a.offs[i] + tl;
     if (lane == 0) { nr++; nb += match_len; }
@@ -166,9 +166,8 @@ __global__ void __launch_bounds__(256) k4k_snp_haplotypes(SnpArgs a, HapArgs hp)
     if (nar != K4_NAR_ACCEPTED) continue;
     const k4_hit h = a.pe ? a.pr[i].hit : a.hits[i * a.max_ml];
     if (h.chrom_id != a.chrom_id || (h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE))) continue;
-    const uint32_t tl = K4_HIT_TRIM_LEFT(h), tr = K4_HIT_TRIM_RIGHT(h);
-    const uint32_t match_len = (uint32_t)h.match_len - tl - tr;
-    const uint32_t start = h.match_loci + (h.strand == '+' ? tl : tr);  // AdjStartLoci .. AdjEndLoci
+    const uint32_t match_len = k4d_adj_len(h);
+    const uint32_t start = k4d_adj_start(h);  // AdjStartLoci .. AdjEndLoci
     if (match_len == 0 || (uint64_t)start + match_len > a.clen) continue;
     const uint32_t end = start + match_len - 1;
     uint32_t lo = 0, hi = hp.n_loci;
@@ -317,13 +316,6 @@ static WigOut wig_chromosome(std::unique_ptr<uint8_t[]> cov, int width, uint32_t
   return wig_walk<uint32_t>((const uint32_t*)cov.get(), clen, name);
 }
 
-struct Buf {
-  void* p = nullptr;
-  ~Buf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t bytes) { return k4_malloc_retry(&p, bytes ? bytes : 1); }
-  template <typename T> T* as() { return (T*)p; }
-};
-
 // ---- CStats (libkit4b/Stats.cpp:489-564), operation for operation ------------------------------------------------------------
 double calc_nck(uint32_t n, uint32_t k) {
   if (k > n) return 0.0;
@@ -418,7 +410,7 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
   if (wig) { *wig = nullptr; *wig_bytes = 0; }
   struct WigJob { std::future<WigOut> f; bool close_tail; };
   std::vector<WigJob> wig_jobs;  // one per chromosome with alignments, in chromosome order
-  Buf covb, covmax;
+  K4DevBuf covb, covmax;
   if (n_snps) *n_snps = 0;
   if (n_units < 0 || min_snp_reads < 1 || qvalue < 0.0 || snp_nonref_pcnt < 0.0) return k4_fail(ix, K4_ERR_PARAMS, "SNP parameters out of range");
   if (n_units > 0 && ((pe && !d_pe) || (!pe && (!d_rr || !d_hits || max_ml < 1)) || !d_reads || !d_offs || !d_lens))
@@ -440,7 +432,8 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
   uint32_t max_len = 0;
   for (const k4_entry& e : ix->entries) max_len = std::max(max_len, e.seq_len);
   const size_t S = (size_t)max_len + 16;
-  Buf cnt, tot, pref, pnon, cands, ncand, tmp;
+  K4DevBuf cnt, tot, pref, pnon, cands, ncand;
+  K4Scratch<K4DevBuf> tmp;  // of the prefix sums: sized for the longest sequence, once
   const uint32_t cap = 1u << 22;  // candidate loci per chromosome kept on the device (more: the call fails loudly)
   K4_HIP(ix, cnt.alloc(7 * S * 4));
   K4_HIP(ix, tot.alloc(4 * 8));
@@ -448,9 +441,7 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
   K4_HIP(ix, pnon.alloc((S + 1) * 8));
   K4_HIP(ix, cands.alloc((size_t)cap * sizeof(Cand)));
   K4_HIP(ix, ncand.alloc(4));
-  size_t tb = 0;
-  K4_HIP(ix, rocprim::exclusive_scan(nullptr, tb, cnt.as<uint32_t>(), pref.as<uint64_t>(), (uint64_t)0, S + 1, rocprim::plus<uint64_t>(), st));
-  K4_HIP(ix, tmp.alloc(tb));
+  K4_TRY(k4s_exclusive_scan(ix, cnt.as<uint32_t>(), pref.as<uint64_t>(), (uint64_t)0, S + 1, rocprim::plus<uint64_t>(), st, &tmp, true));
   uint64_t tot_snps = 0;
   const double nonref_frac = snp_nonref_pcnt / 100.0;  // m_SNPNonRefPcnt, KAligner.cpp:256
   std::vector<Cand> hc;
@@ -459,7 +450,7 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
   std::vector<uint8_t> chrom_hit((size_t)ix->d.n_entries + 1, 0);
   std::vector<uint64_t> ent_start_h((size_t)ix->d.n_entries, 0);
   if (a.n_reads > 0 && ix->d.n_entries) {
-    Buf flags;
+    K4DevBuf flags;
     K4_HIP(ix, flags.alloc(chrom_hit.size()));
     K4_HIP(ix, hipMemsetAsync(flags.p, 0, chrom_hit.size(), st));
     hipLaunchKernelGGL(k4k_snp_mark, dim3((unsigned)std::min<int64_t>((a.n_reads + 255) / 256, 2048)), dim3(256), 0, st, a, flags.as<uint8_t>(), ix->d.n_entries);
@@ -478,8 +469,7 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
     K4_HIP(ix, hipMemsetAsync(ncand.p, 0, 4, st));
     hipLaunchKernelGGL(k4k_snp_pileup, dim3(2048), dim3(256), 0, st, a);
     unsigned long long t3[4] = {0, 0, 0, 0};
-    K4_HIP(ix, hipMemcpyAsync(t3, tot.p, 32, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
+    K4_TRY(k4s_read_back(ix, &t3, tot.p, st));
     if (t3[2] == 0) continue;  // no alignment on this chromosome
     size_t wig_slot = 0;
     if (wig) {  // coverage down to the host, its walk on a thread of its own (at most twelve chromosomes in flight)
@@ -487,8 +477,7 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
       K4_HIP(ix, hipMemsetAsync(covmax.p, 0, 4, st));
       hipLaunchKernelGGL(k4k_snp_coverage_max, dim3(1024), dim3(256), 0, st, a.cnt, a.cnt + K4_SNP_STRIDE(a), a.clen, covmax.as<uint32_t>());
       uint32_t mx = 0;
-      K4_HIP(ix, hipMemcpyAsync(&mx, covmax.p, 4, hipMemcpyDeviceToHost, st));
-      K4_HIP(ix, hipStreamSynchronize(st));
+      K4_TRY(k4s_read_back(ix, &mx, covmax.p, st));
       const int width = mx < 256 ? 1 : mx < 65536 ? 2 : 4;
       const dim3 cg((a.clen + 255) / 256);
       if (width == 1) hipLaunchKernelGGL(k4k_snp_coverage<uint8_t>, cg, dim3(256), 0, st, a.cnt, a.cnt + K4_SNP_STRIDE(a), a.clen, covb.as<uint8_t>());
@@ -502,13 +491,12 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
       wig_jobs.push_back({std::async(std::launch::async, wig_chromosome, std::move(cov), width, a.clen, std::string(e.name)), false});
     }
     // prefix sums over [0, clen]: element l = sum of the loci below l (the arrays are zero behind clen)
-    K4_HIP(ix, rocprim::exclusive_scan(tmp.p, tb, a.cnt, pref.as<uint64_t>(), (uint64_t)0, (size_t)a.clen + 1, rocprim::plus<uint64_t>(), st));
-    K4_HIP(ix, rocprim::exclusive_scan(tmp.p, tb, a.cnt + Sc, pnon.as<uint64_t>(), (uint64_t)0, (size_t)a.clen + 1, rocprim::plus<uint64_t>(), st));
+    K4_TRY(k4s_exclusive_scan(ix, a.cnt, pref.as<uint64_t>(), (uint64_t)0, (size_t)a.clen + 1, rocprim::plus<uint64_t>(), st, &tmp));
+    K4_TRY(k4s_exclusive_scan(ix, a.cnt + Sc, pnon.as<uint64_t>(), (uint64_t)0, (size_t)a.clen + 1, rocprim::plus<uint64_t>(), st, &tmp));
     hipLaunchKernelGGL(k4k_snp_candidates, dim3((a.clen + 255) / 256), dim3(256), 0, st, a, pref.as<uint64_t>(), pnon.as<uint64_t>(), (int)min_snp_reads,
                        nonref_frac, cands.as<Cand>(), cap, ncand.as<uint32_t>());
     uint32_t nc = 0;
-    K4_HIP(ix, hipMemcpyAsync(&nc, ncand.p, 4, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
+    K4_TRY(k4s_read_back(ix, &nc, ncand.p, st));
     if (nc > cap) return k4_fail(ix, K4_ERR_MEM, "more than %u candidate SNP loci on %s", cap, e.name);
     hc.resize(nc);
     if (nc) K4_HIP(ix, hipMemcpy(hc.data(), cands.p, (size_t)nc * sizeof(Cand), hipMemcpyDeviceToHost));
@@ -561,7 +549,7 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
         if (k >= 2 && pv[k - 1].loci > 0 && cur > 0 && cur - (int)pv[k - 2].loci <= max_sep) slot[n_acc + k] = (int32_t)n_tri++;
       }
       if (n_di) {  // (a triple holds two pairs: no pair, no triple)
-        Buf dl, ds, dd, dt;
+        K4DevBuf dl, ds, dd, dt;
         K4_HIP(ix, dl.alloc(n_acc * 4));
         K4_HIP(ix, ds.alloc(2 * n_acc * 4));
         K4_HIP(ix, dd.alloc((size_t)n_di * 17 * 4));

@@ -1,0 +1,109 @@
+// kit4b_amd/csrc/k4_stage.h -- what a device stage needs on the host side: its scratch buffers, the rocPRIM calls with their
+// temporary, the list of the reads a predicate accepts, a counter brought down.  A new stage starts from here.
+//
+// The helpers are templates over the buffer type B: K4DevBuf below, or the pool-backed Buf of k4_io.hip (k4_pool.h says why the
+// ingest / emit stages free nothing).  B needs `p`, `hipError_t alloc(size_t)` (which lets go of what it held) and `as<T>()`;
+// a helper's temporary is a B as well, so a stage never mixes the two kinds.  All of them return a K4_* code.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <type_traits>
+#include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
+#include "k4_internal.h"
+#include "k4_pool.h"
+
+#define K4_TRY(call)                 \
+  do {                               \
+    int _try = (call);               \
+    if (_try != K4_OK) return _try;  \
+  } while (0)
+
+// RAII device block of one stage call: hipMalloc (the pool's cache is given back first when memory is short), hipFree
+struct K4DevBuf {
+  void* p = nullptr;
+  K4DevBuf() = default;
+  K4DevBuf(const K4DevBuf&) = delete;
+  K4DevBuf& operator=(const K4DevBuf&) = delete;
+  ~K4DevBuf() { if (p) hipFree(p); }
+  hipError_t alloc(size_t bytes) {
+    if (p) { (void)hipFree(p); p = nullptr; }
+    return k4_malloc_retry(&p, bytes ? bytes : 1);
+  }
+  template <typename T> T* as() { return (T*)p; }
+};
+
+// one trivially copyable value (a counter, a small array of them) from the device, waited for
+template <typename T>
+int k4s_read_back(k4_index* ix, T* host, const void* dev, hipStream_t st) {
+  static_assert(std::is_trivially_copyable<T>::value, "k4s_read_back copies bytes");
+  K4_HIP(ix, hipMemcpyAsync(host, dev, sizeof(T), hipMemcpyDeviceToHost, st));
+  K4_HIP(ix, hipStreamSynchronize(st));
+  return K4_OK;
+}
+
+// The temporary of a rocPRIM call.  Every wrapper below makes one and lets go of it when it returns; a caller that repeats a
+// call in a loop hands in one that it keeps instead (k4s_exclusive_scan).
+template <typename B>
+struct K4Scratch {
+  B buf;
+  size_t bytes = 0;
+};
+
+// rocPRIM's two calls: `call(tmp, bytes)` is the rocPRIM function with the rest of its arguments bound; a null tmp asks for the size
+template <typename B, typename F>
+int k4s_two_calls(k4_index* ix, const char* what, F call, K4Scratch<B>* keep = nullptr, bool size_only = false) {
+  K4Scratch<B> own;
+  K4Scratch<B>& s = keep ? *keep : own;
+  size_t tb = 0;
+  K4_TRY(k4_check_hip(ix, call((void*)nullptr, tb), what));
+  if (!s.buf.p || tb > s.bytes) {
+    K4_TRY(k4_check_hip(ix, s.buf.alloc(tb), what));
+    s.bytes = tb;
+  }
+  return size_only ? K4_OK : k4_check_hip(ix, call(s.buf.p, tb), what);
+}
+
+// out[0 .. *d_count) = the items of in[0 .. n) that pred accepts, in order; *d_count is a 64-bit device word
+template <typename B, typename In, typename Out, typename Pred>
+int k4s_select(k4_index* ix, In in, Out out, uint64_t* d_count, size_t n, Pred pred, hipStream_t st) {
+  return k4s_two_calls<B>(ix, "rocprim::select", [&](void* t, size_t& tb) { return rocprim::select(t, tb, in, out, d_count, n, pred, st); });
+}
+
+// stable LSD sorts on the key bits [begin_bit, end_bit); the sorted side is current() afterwards
+template <typename B, typename K, typename V>
+int k4s_sort_pairs(k4_index* ix, rocprim::double_buffer<K>& keys, rocprim::double_buffer<V>& vals, size_t n, unsigned begin_bit,
+                   unsigned end_bit, hipStream_t st) {
+  return k4s_two_calls<B>(ix, "rocprim::radix_sort_pairs",
+                          [&](void* t, size_t& tb) { return rocprim::radix_sort_pairs(t, tb, keys, vals, n, begin_bit, end_bit, st); });
+}
+template <typename B, typename K>
+int k4s_sort_keys(k4_index* ix, rocprim::double_buffer<K>& keys, size_t n, unsigned begin_bit, unsigned end_bit, hipStream_t st) {
+  return k4s_two_calls<B>(ix, "rocprim::radix_sort_keys",
+                          [&](void* t, size_t& tb) { return rocprim::radix_sort_keys(t, tb, keys, n, begin_bit, end_bit, st); });
+}
+
+// keep: the caller's temporary, which grows to what a call asks for and stays with the caller; size_only: it is made ready for
+// this call and nothing runs (k4_snp.hip sizes it for its longest sequence once and scans every sequence with it)
+template <typename B, typename In, typename Out, typename Init, typename Op>
+int k4s_exclusive_scan(k4_index* ix, In in, Out out, Init init, size_t n, Op op, hipStream_t st, K4Scratch<B>* keep = nullptr,
+                       bool size_only = false) {
+  return k4s_two_calls<B>(
+      ix, "rocprim::exclusive_scan", [&](void* t, size_t& tb) { return rocprim::exclusive_scan(t, tb, in, out, init, n, op, st); }, keep,
+      size_only);
+}
+template <typename B, typename In, typename Out, typename Op>
+int k4s_inclusive_scan(k4_index* ix, In in, Out out, size_t n, Op op, hipStream_t st) {
+  return k4s_two_calls<B>(ix, "rocprim::inclusive_scan", [&](void* t, size_t& tb) { return rocprim::inclusive_scan(t, tb, in, out, n, op, st); });
+}
+
+// The opener of a stage: idx = the i in [0, n) that pred accepts, ascending, *m = how many (on the host: the stream is waited
+// for).  idx gets n * 4 bytes for the list and, behind them, the word rocPRIM counts in.
+template <typename B, typename Pred>
+int k4s_select_indices(k4_index* ix, B& idx, size_t n, Pred pred, hipStream_t st, uint64_t* m) {
+  const size_t list = (n * 4 + 7) & ~(size_t)7;
+  K4_HIP(ix, idx.alloc(list + 8));
+  uint64_t* d_m = reinterpret_cast<uint64_t*>(idx.template as<char>() + list);
+  K4_TRY(k4s_select<B>(ix, rocprim::counting_iterator<uint32_t>(0), idx.template as<uint32_t>(), d_m, n, pred, st));
+  return k4s_read_back(ix, m, d_m, st);
+}

@@ -29,8 +29,7 @@
 #include <vector>
 #include <rocprim/rocprim.hpp>
 #include "k4_device.h"
-#include "k4_internal.h"
-#include "k4_pool.h"
+#include "k4_stage.h"
 
 #define K4_STATS_LDS_LEN 1024   // read positions of the block's LDS table (32 KB of counters: four blocks per CU)
 #define K4_STATS_LDS_MSUB 256   // mismatches-per-read bins kept in LDS
@@ -38,13 +37,6 @@
 #define K4_STATS_ENT_W 65       // per target: [0] reads whose leading trimer holds a non-ACGT, [1 + t] reads that start with trimer t
 
 namespace {
-
-struct Buf {
-  void* p = nullptr;
-  ~Buf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t bytes) { return k4_malloc_retry(&p, bytes ? bytes : 1); }
-  template <typename T> T* as() { return (T*)p; }
-};
 
 // where the reported alignment of read i lives: SE results + hit slot 0, or the PE records
 struct StatSrc {
@@ -89,11 +81,11 @@ __global__ void __launch_bounds__(256) k4k_sub_dist(K4DevIndex ix, StatSrc s, in
     if (h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE)) continue;  // FlagSegs: a two-segment read is sloughed (:6480)
     if (h.chrom_id == 0 || h.chrom_id > ix.n_entries) continue;
     const uint32_t len = lens[i];
-    const uint32_t tl = h.ext & 0xFFFu, tr = (h.ext >> 12) & 0xFFFu;
+    const uint32_t tl = K4_HIT_TRIM_LEFT(h), tr = K4_HIT_TRIM_RIGHT(h);
     wmax = max(wmax, len);
     const bool minus = h.strand == '-';
-    const uint32_t adj_start = h.match_loci + (minus ? tr : tl);
-    const int32_t adj_len = (int32_t)h.match_len - (int32_t)tl - (int32_t)tr;
+    const uint32_t adj_start = k4d_adj_start(h);
+    const int32_t adj_len = (int32_t)k4d_adj_len(h);
     const uint32_t start = tl;
     // (a one-segment hit spans the whole read, so the walk is AdjHitLen long; the bounds keep an odd record inside the tables)
     uint32_t end = len > tr ? len - tr : 0u;
@@ -186,8 +178,7 @@ __global__ void __launch_bounds__(256) k4k_targ_counts(uint32_t n_entries, StatS
     k4_hit h;
     const bool acc = k4d_stat_accepted(s, i, h) && h.chrom_id >= 1 && h.chrom_id <= n_entries;
     if (!acc) { keys[i] = ~0ull; continue; }
-    const uint32_t tl = h.ext & 0xFFFu, tr = (h.ext >> 12) & 0xFFFu;
-    keys[i] = ((uint64_t)h.chrom_id << 32) | (uint32_t)(h.match_loci + (h.strand == '+' ? tl : tr));
+    keys[i] = ((uint64_t)h.chrom_id << 32) | k4d_adj_start(h);
     mine++;
     uint32_t slot = 0, tri = 0;
     if (lens[i] >= 3) {  // (no read is that short behind the length filter; one that were counts as indeterminate)
@@ -318,7 +309,7 @@ extern "C" int k4_align_stats_dev(k4_index* ix, int pe, int64_t n_reads, int32_t
   // device block: the position tables and m_sub (u64), accepted count (u64), max length, the per-target table and the distinct loci (u32)
   const size_t d64 = (size_t)8 * L + (L + 1) + 1;
   const size_t d32 = 2 + (size_t)ne * (K4_STATS_ENT_W + 1);
-  Buf dev, k0, k1, tmp;
+  K4DevBuf dev, k0, k1;
   if ((rc = k4_check_hip(ix, dev.alloc(d64 * 8 + d32 * 4), "hipMalloc(stats)")) != K4_OK) return fail(rc);
   if ((rc = k4_check_hip(ix, hipMemsetAsync(dev.p, 0, d64 * 8 + d32 * 4, st), "hipMemset(stats)")) != K4_OK) return fail(rc);
   unsigned long long* g_insts = dev.as<unsigned long long>();
@@ -341,12 +332,7 @@ extern "C" int k4_align_stats_dev(k4_index* ix, int pe, int64_t n_reads, int32_t
                      n_reads, (const uint8_t*)d_reads, (const uint64_t*)d_offs, (const uint32_t*)d_lens, use_lds, k0.as<uint64_t>(), g_ent, g_nacc);
   if ((rc = k4_check_hip(ix, hipGetLastError(), "k4k_targ_counts")) != K4_OK) return fail(rc);
   rocprim::double_buffer<uint64_t> kk(k0.as<uint64_t>(), k1.as<uint64_t>());
-  {
-    size_t tb = 0;
-    if ((rc = k4_check_hip(ix, rocprim::radix_sort_keys(nullptr, tb, kk, (size_t)n_reads, 0u, 64u, st), "sort")) != K4_OK) return fail(rc);
-    if ((rc = k4_check_hip(ix, tmp.alloc(tb), "hipMalloc(sort)")) != K4_OK) return fail(rc);
-    if ((rc = k4_check_hip(ix, rocprim::radix_sort_keys(tmp.p, tb, kk, (size_t)n_reads, 0u, 64u, st), "sort")) != K4_OK) return fail(rc);
-  }
+  if ((rc = k4s_sort_keys<K4DevBuf>(ix, kk, (size_t)n_reads, 0u, 64u, st)) != K4_OK) return fail(rc);
   hipLaunchKernelGGL(k4k_uniq_heads, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, st, (uint64_t)n_reads, kk.current(), ne, g_uniq);
   if ((rc = k4_check_hip(ix, hipGetLastError(), "k4k_uniq_heads")) != K4_OK) return fail(rc);
   // down: the u64 tables are laid out as in the host block; the per-target table is unpacked

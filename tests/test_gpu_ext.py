@@ -124,3 +124,79 @@ def test_fresh_inputs_vs_oracle_kalign_level_and_post_stages(oracle, tmp_path):
         assert np.array_equal(g_out, o_out) and np.array_equal(g_hits, o_hits)
     ix.close()
     oracle.close(h)
+
+
+# ---- the orphan-junction stage at small selected counts ---------------------------------------------------------------------------
+def _junction_results(m, flag, seed):
+    """(out, hits, seg2) of SE results with exactly m accepted reads that carry `flag`, on two sequences: single junctions, groups
+    of two or three reads whose seg-0 ends and seg-1 starts chain within 3 bp, pairs that agree at one end only; between them
+    accepted reads without a junction, accepted reads with the other junction kind, and reads that carry `flag` but were not
+    accepted.  The last junction of sequence 1 and the first of sequence 2 lie 1 bp apart in both coordinates."""
+    rng = np.random.default_rng(seed)
+    other = EXT_INDEL if flag == EXT_SPLICE else EXT_SPLICE
+    sites = {0: [], 1: [1], 2: [2], 3: [1, 2]}.get(m)  # reads per site; -2: a pair that is close at the seg-0 end only
+    if sites is None:
+        sites, left = [], m
+        while left:
+            k = int(rng.choice([1, 1, 2, 3, -2]))
+            sites.append(k if abs(k) <= left else 1)
+            left -= abs(sites[-1])
+    half = len(sites) // 2  # sites of sequence 1; the two next to the boundary get one read each, the others go to the end
+    if m > 3:
+        for q in (half - 1, half):
+            sites += [1] * (abs(sites[q]) - 1)
+            sites[q] = 1
+    assert sum(abs(k) for k in sites) == m
+    junct = []  # (chrom, seg-0 end, seg-1 start)
+    for q, k in enumerate(sites):
+        chrom = 1 if q < half or len(sites) < 2 else 2
+        e0, s1 = 5000 + 1000 * q, 9000 + 1000 * q
+        if q == half and m > 3:
+            e0, s1 = 5000 + 1000 * (q - 1) + 1, 9000 + 1000 * (q - 1) + 1
+        for _ in range(abs(k)):
+            junct.append((chrom, e0, s1))
+            e0 += int(rng.integers(-3, 4))
+            s1 += int(rng.integers(-3, 4)) if k > 0 else 4 + int(rng.integers(0, 50))
+    n_plain, n_other, n_rejected = m // 2 + 5, m // 4 + 3, m // 4 + 3
+    n = m + n_plain + n_other + n_rejected
+    out = np.zeros(n, k4.RESULT_DTYPE)
+    hits = np.zeros((n, 1), k4.HIT_DTYPE)
+    seg2 = np.zeros(n, k4.SEG2_DTYPE)
+    out["hit_rslt"], out["inst"], out["nar"], out["num_hits"] = 1, 1, 1, 1
+    hits["chrom_id"][:, 0] = rng.integers(1, 3, n)
+    hits["match_loci"][:, 0] = rng.integers(5000, 300000, n)
+    hits["match_len"][:, 0] = 40
+    hits["strand"][:, 0] = np.where(rng.random(n) < 0.5, ord("+"), ord("-"))
+    for k, (chrom, e0, s1) in enumerate(junct):
+        hits["chrom_id"][k, 0], hits["match_loci"][k, 0] = chrom, e0 - 39
+        seg2["chrom_id"][k], seg2["match_loci"][k], seg2["match_len"][k], seg2["read_ofs"][k] = chrom, s1, 60, 40
+    hits["reserved"][:m, 0] = flag
+    a = m + n_plain
+    hits["reserved"][a:a + n_other, 0] = other
+    seg2["match_loci"][a:], seg2["match_len"][a:] = hits["match_loci"][a:, 0] + 500, 60
+    hits["reserved"][a + n_other:, 0] = flag  # junction reads at the loci of accepted ones that something earlier turned down
+    out["nar"][a + n_other:] = rng.choice([0, 3, 6], n_rejected)
+    out["num_hits"][a + n_other:] = 0
+    for k in range(min(m, n_rejected)):
+        hits["chrom_id"][a + n_other + k, 0], hits["match_loci"][a + n_other + k, 0] = hits["chrom_id"][k, 0], hits["match_loci"][k, 0]
+        seg2["match_loci"][a + n_other + k] = seg2["match_loci"][k]
+    order = rng.permutation(n)
+    return out[order], hits[order], seg2[order]
+
+
+@pytest.mark.parametrize("m,flag", [(m, EXT_SPLICE) for m in (0, 1, 2, 3, 255, 256, 257)] + [(1, EXT_INDEL), (257, EXT_INDEL)])
+def test_orphan_juncts_small_counts_vs_oracle(oracle, g3, m, flag):
+    """k4_remove_orphan_juncts_dev where its control flow branches: nothing selected, a lone junction (no sort, no neighbour
+    test), two and three, and one block of 256 threads more or less."""
+    out, hits, seg2 = _junction_results(m, flag, 1000 + m)
+    assert int(((out["nar"] == 1) & ((hits["reserved"][:, 0] & flag) != 0)).sum()) == m
+    o_out, o_hits = out.copy(), hits.copy()
+    want = oracle.remove_orphan_juncts(flag, o_out, o_hits, seg2)
+    if m > 3:  # the input has both outcomes
+        assert m // 4 < want < m - m // 4
+    reads = [np.zeros(4, np.uint8)] * len(out)
+    splice = flag == EXT_SPLICE
+    g_out, g_hits, cnt = g3.post_stages(reads, out, hits, seg2, min_flank_exacts=0, orphan_splice=splice, orphan_indel=not splice)
+    print("m %d selected, %d removed (oracle %d)" % (m, list(cnt.values())[0], want))
+    assert cnt == {"splice" if splice else "indel": want}
+    assert np.array_equal(g_out, o_out) and np.array_equal(g_hits, o_hits)

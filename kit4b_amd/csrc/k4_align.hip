@@ -639,15 +639,8 @@ extern "C" int k4_reserve(k4_index* ix, int64_t max_reads, int32_t max_read_len,
     int len = std::max(fast_len, w.cap_len);
     int nch = nch_for(len);
     touched = true;
-    // the capacities say what the pointers below can hold: zero while they are being replaced, so that a failed
-    // allocation leaves a workspace every *_dev call refuses (K4_ERR_PARAMS) instead of one with null buffers
-    w.cap_reads = 0;
+    w.cap_reads = 0;  // (zero until the whole group has grown: K4DevBuf::reserve, k4_pool.h; every *_dev call then refuses the workspace)
     w.cap_len = 0;
-    for (void* q : {(void*)w.ids[0], (void*)w.ids[1], (void*)w.rows[0], (void*)w.rows[1], (void*)w.slow_list, (void*)w.slow_step,
-                    (void*)w.huge_list, (void*)w.huge_step})
-      if (q) hipFree(q);
-    w.ids[0] = w.ids[1] = nullptr; w.rows[0] = w.rows[1] = nullptr; w.slow_list = nullptr; w.slow_step = nullptr;
-    w.huge_list = nullptr; w.huge_step = nullptr;
     // Survivors of step t (ids + packed rows) ping-pong between two buffers.  Slots are handed out K4_CHUNK at a time
     // per wave; a wave abandons the tail of its chunk (at most 63 slots) when the next ballot does not fit, and leaves
     // one partly used chunk behind when it ends.  Step t+1 walks over step t's slots, holes included, but places only
@@ -655,35 +648,32 @@ extern "C" int k4_reserve(k4_index* ix, int64_t max_reads, int32_t max_read_len,
     // uses at most n * K4_CHUNK / (K4_CHUNK - 63) slots plus one chunk per wave of the (at most 2048-block) grid.
     const size_t slots = k4_survivor_slots((size_t)cap);
     for (int b = 0; b < 2; b++) {
-      K4_HIP(ix, hipMalloc(&w.ids[b], slots * 4));
-      K4_HIP(ix, hipMalloc(&w.rows[b], slots * K4_ROW_WORDS(nch) * 8));
+      K4_HIP(ix, w.ids[b].reserve(slots * 4));
+      K4_HIP(ix, w.rows[b].reserve(slots * K4_ROW_WORDS(nch) * 8));
     }
-    K4_HIP(ix, hipMalloc(&w.slow_list, (size_t)cap * 4));
-    K4_HIP(ix, hipMalloc(&w.slow_step, (size_t)cap));
-    K4_HIP(ix, hipMalloc(&w.huge_list, (size_t)cap * 4));
-    K4_HIP(ix, hipMalloc(&w.huge_step, (size_t)cap));
+    K4_HIP(ix, w.slow_list.reserve((size_t)cap * 4));
+    K4_HIP(ix, w.slow_step.reserve((size_t)cap));
+    K4_HIP(ix, w.huge_list.reserve((size_t)cap * 4));
+    K4_HIP(ix, w.huge_step.reserve((size_t)cap));
     w.cap_reads = cap;
     w.cap_len = len;
   }
-  if (!w.ctl) {
+  if (!w.ctl.p) {
     touched = true;
-    K4_HIP(ix, hipMalloc(&w.ctl, K4_CTL_WORDS * 4));
-    K4_HIP(ix, hipMemset(w.ctl, 0, K4_CTL_WORDS * 4));
+    K4_HIP(ix, w.ctl.reserve(K4_CTL_WORDS * 4));
+    K4_HIP(ix, hipMemset(w.ctl.p, 0, K4_CTL_WORDS * 4));
   }
   // general-kernel scratch.  Pass 0: K4_SLOW_WAVES waves with small dedupe tables; pass 1: K4_HUGE_WAVES waves whose
   // tables hold one strand pass at the reference's own limits (<= MaxIter per core, <= 1,024,000 nodes, SfxArray.h:15)
   uint64_t nodes = ix->d.max_iter ? std::min<uint64_t>((uint64_t)ix->d.max_iter * 48, K4_MAX_IDENT_NODES) : K4_MAX_IDENT_NODES;
   uint32_t hcap = next_pow2(std::max<uint64_t>(2 * nodes + 2, 1024));
-  if (!w.slow_hash || hcap > w.slow_hash_cap) {
+  if (!w.slow_hash.p || hcap > w.slow_hash_cap) {
     touched = true;
-    if (w.slow_hash) hipFree(w.slow_hash);
-    w.slow_hash = nullptr;
     const size_t words = (size_t)K4_SLOW_WAVES * K4_SMALL_HASH + (size_t)K4_HUGE_WAVES * hcap;
     const size_t bytes = words * 8 + (size_t)(K4_SLOW_WAVES + K4_HUGE_WAVES) * 4;
-    K4_HIP(ix, hipMalloc(&w.slow_hash, bytes));
-    K4_HIP(ix, hipMemset(w.slow_hash, 0, bytes));
+    K4_HIP(ix, w.slow_hash.reserve(bytes));
+    K4_HIP(ix, hipMemset(w.slow_hash.p, 0, bytes));
     w.slow_hash_cap = hcap;
-    w.slow_lanes = K4_SLOW_WAVES;
   }
   w.cap_hits = std::max(w.cap_hits, max_hits);
   // (the fills above ran on the null stream: callers launch on streams of their own, possibly non-blocking ones)
@@ -694,6 +684,9 @@ extern "C" int k4_reserve(k4_index* ix, int64_t max_reads, int32_t max_read_len,
 template <int EL, int NCH, typename KT>
 static int launch_steps(k4_index* ix, K4AlignArgs& a, int n_steps, hipStream_t st) {
   K4Workspace& w = ix->ws;
+  uint32_t* const ids[2] = {w.ids[0].as<uint32_t>(), w.ids[1].as<uint32_t>()};
+  uint64_t* const rows[2] = {w.rows[0].as<uint64_t>(), w.rows[1].as<uint64_t>()};
+  uint32_t* const ctl = w.ctl.as<uint32_t>();
   const size_t lds = (size_t)2 * (NCH + 1) * K4_BS(NCH) * 8 + (size_t)K4_DEDUP_CAP * K4_BS(NCH) * 4 + (size_t)2 * K4_BS(NCH) * 8 + (size_t)2 * K4_LDS_ENTRIES * 8 +
                      (size_t)K4_SUP_WORDS * 4 + 16;
   if (lds > 48 * 1024) {
@@ -724,20 +717,20 @@ static int launch_steps(k4_index* ix, K4AlignArgs& a, int n_steps, hipStream_t s
   static const int deep_mode = getenv("K4_DEEP_TO_GENERAL") ? atoi(getenv("K4_DEEP_TO_GENERAL")) : 0;  // (experiment)
   a.deep_general = (deep_mode && ix->deep_bucket_frac >= K4_DEFER_MIN_FRAC) ? deep_mode : 0;  // 1: from the first phase on, 2: from the second
   if (ix->deep_bucket_frac >= K4_DEFER_MIN_FRAC && a.deep_general != 1) {
-    a.defer_ids = w.ids[1];
+    a.defer_ids = ids[1];
     hipLaunchKernelGGL((k4k_align_step<EL, NCH, true, KT, true>), dim3(grid0), dim3(K4_BS(NCH)), lds, st, a, 0, (const uint32_t*)nullptr,
-                       (const uint64_t*)nullptr, (const uint32_t*)nullptr, w.ids[0], w.rows[0], w.ctl + 2);
-    hipLaunchKernelGGL((k4k_align_step<EL, NCH, true, KT, true>), dim3(grid0), dim3(K4_BS(NCH)), lds, st, a, 0, (const uint32_t*)w.ids[1],
-                       (const uint64_t*)nullptr, (const uint32_t*)(w.ctl + K4_CTL_DEFER), w.ids[0], w.rows[0], w.ctl + 2);
+                       (const uint64_t*)nullptr, (const uint32_t*)nullptr, ids[0], rows[0], ctl + 2);
+    hipLaunchKernelGGL((k4k_align_step<EL, NCH, true, KT, true>), dim3(grid0), dim3(K4_BS(NCH)), lds, st, a, 0, (const uint32_t*)ids[1],
+                       (const uint64_t*)nullptr, (const uint32_t*)(ctl + K4_CTL_DEFER), ids[0], rows[0], ctl + 2);
   } else {
     a.defer_ids = nullptr;
     hipLaunchKernelGGL((k4k_align_step<EL, NCH, true, KT, false>), dim3(grid0), dim3(K4_BS(NCH)), lds, st, a, 0, (const uint32_t*)nullptr,
-                       (const uint64_t*)nullptr, (const uint32_t*)nullptr, w.ids[0], w.rows[0], w.ctl + 2);
+                       (const uint64_t*)nullptr, (const uint32_t*)nullptr, ids[0], rows[0], ctl + 2);
   }
   for (int t = 1; t < n_steps; t++) {
     const int in = (t - 1) & 1, out = t & 1;
-    hipLaunchKernelGGL((k4k_align_step<EL, NCH, false, KT>), dim3(grid0), dim3(K4_BS(NCH)), lds, st, a, t, w.ids[in], w.rows[in],
-                       w.ctl + 2 + (t - 1), w.ids[out], w.rows[out], w.ctl + 2 + t);
+    hipLaunchKernelGGL((k4k_align_step<EL, NCH, false, KT>), dim3(grid0), dim3(K4_BS(NCH)), lds, st, a, t, ids[in], rows[in],
+                       ctl + 2 + (t - 1), ids[out], rows[out], ctl + 2 + t);
   }
   if (timed) K4_HIP(ix, hipEventRecord(ix->ev1[ix->ev_used], st));  // (launch_all records ev2 behind the general kernel and counts the set)
   return K4_OK;
@@ -749,19 +742,18 @@ static int launch_all(k4_index* ix, K4AlignArgs& a, int max_len, int n_steps, hi
   const int nch = nch_for(std::min(max_len, K4_MAX_FAST_READ_LEN));
   if (nch > nch_for(w.cap_len)) return k4_fail(ix, K4_ERR_INTERNAL, "workspace not reserved for read length %d", max_len);
   if (n_steps < 1 || n_steps > K4_CTL_WORDS - 4) return k4_fail(ix, K4_ERR_INTERNAL, "bad phase count %d", n_steps);
-  a.slow_list = w.slow_list;
-  a.slow_step = w.slow_step;
-  a.ctl = w.ctl;
-  a.counters = (unsigned long long*)ix->counters;
-  a.huge_list = w.huge_list;
-  a.huge_step = w.huge_step;
-  a.slow_probe = nullptr;
-  a.slow_hash = w.slow_hash;
+  a.slow_list = w.slow_list.as<uint32_t>();
+  a.slow_step = w.slow_step.as<uint8_t>();
+  a.ctl = w.ctl.as<uint32_t>();
+  a.counters = ix->counters.as<unsigned long long>();
+  a.huge_list = w.huge_list.as<uint32_t>();
+  a.huge_step = w.huge_step.as<uint8_t>();
+  a.slow_hash = w.slow_hash.as<uint64_t>();
   a.slow_hash_cap = w.slow_hash_cap;
-  a.slow_gen = reinterpret_cast<uint32_t*>(w.slow_hash + (size_t)K4_SLOW_WAVES * K4_SMALL_HASH + (size_t)K4_HUGE_WAVES * w.slow_hash_cap);
+  a.slow_gen = reinterpret_cast<uint32_t*>(a.slow_hash + (size_t)K4_SLOW_WAVES * K4_SMALL_HASH + (size_t)K4_HUGE_WAVES * w.slow_hash_cap);
   a.nw = nch + 1;
   if (a.n_reads == 0) return K4_OK;
-  K4_HIP(ix, hipMemsetAsync(w.ctl, 0, K4_CTL_WORDS * 4, st));
+  K4_HIP(ix, hipMemsetAsync(w.ctl.p, 0, K4_CTL_WORDS * 4, st));
   int rc;
   switch (nch) {
     case 4: rc = launch_steps<EL, 4, KT>(ix, a, n_steps, st); break;
@@ -783,7 +775,7 @@ static int launch_all(k4_index* ix, K4AlignArgs& a, int max_len, int n_steps, hi
 static int run_dev(k4_index* ix, K4AlignArgs& a, int max_len, void* stream) {
   K4Workspace& w = ix->ws;
   if (a.n_reads > w.cap_reads || std::min(max_len, K4_MAX_FAST_READ_LEN) > w.cap_len || a.max_hits > w.cap_hits ||
-      !w.slow_hash || !w.ids[0] || !w.ids[1] || !w.rows[0] || !w.rows[1] || !w.slow_list || !w.huge_list || !w.ctl)
+      !w.slow_hash.p || !w.ids[0].p || !w.ids[1].p || !w.rows[0].p || !w.rows[1].p || !w.slow_list.p || !w.huge_list.p || !w.ctl.p)
     return k4_fail(ix, K4_ERR_PARAMS, "k4_reserve(%lld, %d, %d) must precede the *_dev call", (long long)a.n_reads,
                    max_len, a.max_hits);
   a.ix = ix->d;
@@ -910,13 +902,13 @@ static int kalign_dev(k4_index* ix, const k4_kalign_params* p, int64_t n, int32_
   // m_MultiHitDist (KAligner.cpp:9943), only while the `-O` tallies are on.  (pe_mode 2 is also how `-r2` gets every instance
   // before one is drawn, so it is tallied; under a real eMLall the reference leaves the switch at :9913-9931 without
   // tallying -- `k4align -O -r5` is turned down)
-  if (rc == K4_OK && ix->d_run_stats) rc = k4i_stats_tally_multi(ix, d_out, n, stream);
+  if (rc == K4_OK && ix->d_run_stats.p) rc = k4i_stats_tally_multi(ix, d_out, n, stream);
   return rc;
 }
 
 // ---- host-pointer entry points: stage through the index's own buffers and stream -------------------------------
 static int stage_in(k4_index* ix, int64_t n, const uint8_t* reads, const uint64_t* offs, const uint32_t* lens,
-                    int max_hits, int* max_len_out, size_t out_bytes_per_read) {
+                    int max_hits, int* max_len_out) {
   K4Workspace& w = ix->ws;
   uint64_t tot = 0;
   int max_len = 1;
@@ -929,79 +921,77 @@ static int stage_in(k4_index* ix, int64_t n, const uint8_t* reads, const uint64_
   int rc = k4_reserve(ix, n, max_len, max_hits);
   if (rc != K4_OK) return rc;
   // small batch: everything through one pinned block (one copy up, one down instead of three and two from pageable memory)
-  const size_t in_bytes = (((size_t)n * 12 + 15) & ~(size_t)15) + tot + 64;
+  const size_t reads_off = ((size_t)n * 12 + 15) & ~(size_t)15;
+  const size_t in_bytes = reads_off + tot + 64;
   const size_t hits_off = ((size_t)n * 24 + 15) & ~(size_t)15;
   const size_t out_bytes = hits_off + (size_t)n * max_hits * sizeof(k4_hit);
   w.c_small = n <= K4_SMALL_READS && in_bytes <= K4_SMALL_STAGE / 2 && out_bytes <= K4_SMALL_STAGE / 2;
   if (w.c_small) {
-    if (!w.h_small) {
-      K4_HIP(ix, hipHostMalloc((void**)&w.h_small, K4_SMALL_STAGE, hipHostMallocDefault));
-      K4_HIP(ix, hipMalloc((void**)&w.d_small, K4_SMALL_STAGE));
-    }
-    const size_t reads_off = ((size_t)n * 12 + 15) & ~(size_t)15;
+    if (!w.h_small) K4_HIP(ix, hipHostMalloc((void**)&w.h_small, K4_SMALL_STAGE, hipHostMallocDefault));
+    K4_HIP(ix, w.d_small.reserve(K4_SMALL_STAGE));
+    uint8_t* const d = w.d_small.as<uint8_t>();
     memcpy(w.h_small, offs, (size_t)n * 8);
     memcpy(w.h_small + (size_t)n * 8, lens, (size_t)n * 4);
     memcpy(w.h_small + reads_off, reads, tot);
-    K4_HIP(ix, hipMemcpyAsync(w.d_small, w.h_small, reads_off + tot, hipMemcpyHostToDevice, ix->stream));
-    w.c_offs = (const uint64_t*)w.d_small;
-    w.c_lens = (const uint32_t*)(w.d_small + (size_t)n * 8);
-    w.c_reads = w.d_small + reads_off;
-    w.c_out = (int32_t*)(w.d_small + K4_SMALL_STAGE / 2);
-    w.c_hits = (k4_hit*)(w.d_small + K4_SMALL_STAGE / 2 + hits_off);
+    K4_HIP(ix, hipMemcpyAsync(d, w.h_small, reads_off + tot, hipMemcpyHostToDevice, ix->stream));
+    w.c_offs = (const uint64_t*)d;
+    w.c_lens = (const uint32_t*)(d + (size_t)n * 8);
+    w.c_reads = d + reads_off;
+    w.c_out = (int32_t*)(d + K4_SMALL_STAGE / 2);
+    w.c_hits = (k4_hit*)(d + K4_SMALL_STAGE / 2 + hits_off);
     return K4_OK;
   }
-  if (tot + 64 > w.d_reads_cap) {
-    if (w.d_reads) hipFree(w.d_reads);
-    w.d_reads = nullptr;
-    K4_HIP(ix, hipMalloc(&w.d_reads, tot + 64));
-    w.d_reads_cap = tot + 64;
-  }
+  K4_HIP(ix, w.d_reads.reserve(tot + 64));
   if (n > w.stage_reads || max_hits > w.stage_hits) {
-    int64_t cap = std::max(n, w.stage_reads);
-    int mh = std::max(max_hits, w.stage_hits);
-    for (void* p : {(void*)w.d_offs, (void*)w.d_lens, (void*)w.d_out4, (void*)w.d_hits})
-      if (p) hipFree(p);
-    w.d_offs = nullptr; w.d_lens = nullptr; w.d_out4 = nullptr; w.d_hits = nullptr;
-    K4_HIP(ix, hipMalloc(&w.d_offs, (size_t)(cap + 1) * 8));
-    K4_HIP(ix, hipMalloc(&w.d_lens, (size_t)(cap + 1) * 4));
-    K4_HIP(ix, hipMalloc(&w.d_out4, (size_t)(cap + 1) * 24));
-    K4_HIP(ix, hipMalloc(&w.d_hits, (size_t)(cap + 1) * mh * sizeof(k4_hit)));
+    const int64_t cap = std::max(n, w.stage_reads);
+    const int mh = std::max(max_hits, w.stage_hits);
+    w.stage_reads = 0;
+    w.stage_hits = 0;
+    K4_HIP(ix, w.d_offs.reserve((size_t)(cap + 1) * 8));
+    K4_HIP(ix, w.d_lens.reserve((size_t)(cap + 1) * 4));
+    K4_HIP(ix, w.d_out4.reserve((size_t)(cap + 1) * 24));
+    K4_HIP(ix, w.d_hits.reserve((size_t)(cap + 1) * mh * sizeof(k4_hit)));
     w.stage_reads = cap;
     w.stage_hits = mh;
   }
-  (void)out_bytes_per_read;
-  w.c_reads = w.d_reads; w.c_offs = w.d_offs; w.c_lens = w.d_lens; w.c_out = w.d_out4; w.c_hits = w.d_hits;
+  w.c_reads = w.d_reads.as<uint8_t>(); w.c_offs = w.d_offs.as<uint64_t>(); w.c_lens = w.d_lens.as<uint32_t>();
+  w.c_out = w.d_out4.as<int32_t>(); w.c_hits = w.d_hits.as<k4_hit>();
   if (n) {
-    K4_HIP(ix, hipMemcpyAsync(w.d_reads, reads, tot, hipMemcpyHostToDevice, ix->stream));
-    K4_HIP(ix, hipMemcpyAsync(w.d_offs, offs, (size_t)n * 8, hipMemcpyHostToDevice, ix->stream));
-    K4_HIP(ix, hipMemcpyAsync(w.d_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, ix->stream));
+    K4_HIP(ix, hipMemcpyAsync(w.d_reads.p, reads, tot, hipMemcpyHostToDevice, ix->stream));
+    K4_HIP(ix, hipMemcpyAsync(w.d_offs.p, offs, (size_t)n * 8, hipMemcpyHostToDevice, ix->stream));
+    K4_HIP(ix, hipMemcpyAsync(w.d_lens.p, lens, (size_t)n * 4, hipMemcpyHostToDevice, ix->stream));
   }
   return K4_OK;
 }
 
-// small batch: results and hits come down in one copy into the pinned block; returns where they are
-static int fetch_small(k4_index* ix, int64_t n, int max_hits, const int32_t** out, const k4_hit** hits) {
+// The tail of a host-pointer batch: the result arrays that lie one behind the other in c_out (n elements of `elem` bytes each:
+// rslt / inst / low / nxt words, or the one array of k4_read_result) and the hit slots come down, and the stream is waited for.
+// A small batch comes down in one copy into the pinned block and is handed out from there.
+static int stage_out(k4_index* ix, int64_t n, int max_hits, std::initializer_list<void*> dst, size_t elem, k4_hit* hits) {
   K4Workspace& w = ix->ws;
-  const size_t hits_off = ((size_t)n * 24 + 15) & ~(size_t)15;
-  const size_t bytes = hits_off + (size_t)n * max_hits * sizeof(k4_hit);
-  K4_HIP(ix, hipMemcpyAsync(w.h_small + K4_SMALL_STAGE / 2, w.d_small + K4_SMALL_STAGE / 2, bytes, hipMemcpyDeviceToHost, ix->stream));
+  const size_t part = (size_t)n * elem, hit_bytes = (size_t)n * max_hits * sizeof(k4_hit);
+  if (w.c_small) {
+    const size_t hits_off = ((size_t)n * 24 + 15) & ~(size_t)15;
+    const uint8_t* h = w.h_small + K4_SMALL_STAGE / 2;
+    K4_HIP(ix, hipMemcpyAsync(w.h_small + K4_SMALL_STAGE / 2, w.c_out, hits_off + hit_bytes, hipMemcpyDeviceToHost, ix->stream));
+    K4_HIP(ix, hipStreamSynchronize(ix->stream));
+    memcpy(hits, h + hits_off, hit_bytes);
+    for (void* d : dst) { memcpy(d, h, part); h += part; }
+    return K4_OK;
+  }
+  const uint8_t* o = (const uint8_t*)w.c_out;
+  for (void* d : dst) { K4_HIP(ix, hipMemcpyAsync(d, o, part, hipMemcpyDeviceToHost, ix->stream)); o += part; }
+  K4_HIP(ix, hipMemcpyAsync(hits, w.c_hits, hit_bytes, hipMemcpyDeviceToHost, ix->stream));
   K4_HIP(ix, hipStreamSynchronize(ix->stream));
-  *out = (const int32_t*)(w.h_small + K4_SMALL_STAGE / 2);
-  *hits = (const k4_hit*)(w.h_small + K4_SMALL_STAGE / 2 + hits_off);
   return K4_OK;
 }
 
 // second segments of a host-pointer batch: a temporary device array, copied down after the stream has drained
-struct Seg2Stage {
-  void* d = nullptr;
-  ~Seg2Stage() { if (d) hipFree(d); }
-  int alloc(k4_index* ix, int64_t n) { K4_HIP(ix, hipMalloc(&d, (size_t)std::max<int64_t>(n, 1) * sizeof(k4_seg2))); return K4_OK; }
-  int fetch(k4_index* ix, k4_seg2* out, int64_t n) {
-    K4_HIP(ix, hipMemcpyAsync(out, d, (size_t)n * sizeof(k4_seg2), hipMemcpyDeviceToHost, ix->stream));
-    K4_HIP(ix, hipStreamSynchronize(ix->stream));
-    return K4_OK;
-  }
-};
+static int seg2_fetch(k4_index* ix, k4_seg2* out, const K4DevBuf& d, int64_t n) {
+  K4_HIP(ix, hipMemcpyAsync(out, d.p, (size_t)n * sizeof(k4_seg2), hipMemcpyDeviceToHost, ix->stream));
+  K4_HIP(ix, hipStreamSynchronize(ix->stream));
+  return K4_OK;
+}
 
 extern "C" int k4_align_reads_batch(k4_index* ix, const k4_align_params* p, int64_t n, const uint8_t* reads,
                                     const uint64_t* offs, const uint32_t* lens, int32_t* rslt, int32_t* inst,
@@ -1019,33 +1009,17 @@ extern "C" int k4_align_reads_ext_batch(k4_index* ix, const k4_align_params* p, 
   if (n == 0) return K4_OK;
   K4_HIP(ix, hipSetDevice(ix->device));
   int max_len = 1;
-  rc = stage_in(ix, n, reads, offs, lens, p->max_hits, &max_len, 16);
+  rc = stage_in(ix, n, reads, offs, lens, p->max_hits, &max_len);
   if (rc != K4_OK) return rc;
   K4Workspace& w = ix->ws;
   int32_t* o = w.c_out;
-  Seg2Stage s2;
-  if (seg2 && (rc = s2.alloc(ix, n)) != K4_OK) return rc;
+  K4DevBuf s2;
+  if (seg2) K4_HIP(ix, s2.alloc((size_t)n * sizeof(k4_seg2)));
   rc = k4_align_reads_ext_batch_dev(ix, p, n, max_len, w.c_reads, w.c_offs, w.c_lens, o, o + n, o + 2 * n, o + 3 * n,
-                                    w.c_hits, s2.d, ix->stream);
+                                    w.c_hits, s2.p, ix->stream);
   if (rc != K4_OK) return rc;
-  if (seg2 && (rc = s2.fetch(ix, seg2, n)) != K4_OK) return rc;
-  if (w.c_small) {
-    const int32_t* r;
-    const k4_hit* h;
-    rc = fetch_small(ix, n, p->max_hits, &r, &h);
-    if (rc != K4_OK) return rc;
-    memcpy(rslt, r, (size_t)n * 4); memcpy(inst, r + n, (size_t)n * 4);
-    memcpy(low, r + 2 * n, (size_t)n * 4); memcpy(nxt, r + 3 * n, (size_t)n * 4);
-    memcpy(hits, h, (size_t)n * p->max_hits * sizeof(k4_hit));
-    return K4_OK;
-  }
-  K4_HIP(ix, hipMemcpyAsync(rslt, o, (size_t)n * 4, hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipMemcpyAsync(inst, o + n, (size_t)n * 4, hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipMemcpyAsync(low, o + 2 * n, (size_t)n * 4, hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipMemcpyAsync(nxt, o + 3 * n, (size_t)n * 4, hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipMemcpyAsync(hits, w.c_hits, (size_t)n * p->max_hits * sizeof(k4_hit), hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipStreamSynchronize(ix->stream));
-  return K4_OK;
+  if (seg2 && (rc = seg2_fetch(ix, seg2, s2, n)) != K4_OK) return rc;
+  return stage_out(ix, n, p->max_hits, {rslt, inst, low, nxt}, 4, hits);
 }
 
 extern "C" int k4_best_matches_batch(k4_index* ix, const k4_align_params* p, int64_t n, const uint8_t* reads, const uint64_t* offs,
@@ -1057,26 +1031,13 @@ extern "C" int k4_best_matches_batch(k4_index* ix, const k4_align_params* p, int
   if (n == 0) return K4_OK;
   K4_HIP(ix, hipSetDevice(ix->device));
   int max_len = 1;
-  rc = stage_in(ix, n, reads, offs, lens, p->max_hits, &max_len, 16);
+  rc = stage_in(ix, n, reads, offs, lens, p->max_hits, &max_len);
   if (rc != K4_OK) return rc;
   K4Workspace& w = ix->ws;
   int32_t* o = w.c_out;
   rc = k4_best_matches_batch_dev(ix, p, n, max_len, w.c_reads, w.c_offs, w.c_lens, o, o + n, w.c_hits, ix->stream);
   if (rc != K4_OK) return rc;
-  if (w.c_small) {
-    const int32_t* r;
-    const k4_hit* h;
-    rc = fetch_small(ix, n, p->max_hits, &r, &h);
-    if (rc != K4_OK) return rc;
-    memcpy(rslt, r, (size_t)n * 4); memcpy(inst, r + n, (size_t)n * 4);
-    memcpy(hits, h, (size_t)n * p->max_hits * sizeof(k4_hit));
-    return K4_OK;
-  }
-  K4_HIP(ix, hipMemcpyAsync(rslt, o, (size_t)n * 4, hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipMemcpyAsync(inst, o + n, (size_t)n * 4, hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipMemcpyAsync(hits, w.c_hits, (size_t)n * p->max_hits * sizeof(k4_hit), hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipStreamSynchronize(ix->stream));
-  return K4_OK;
+  return stage_out(ix, n, p->max_hits, {rslt, inst}, 4, hits);
 }
 
 extern "C" int k4_kalign_batch(k4_index* ix, const k4_kalign_params* p, int64_t n, const uint8_t* reads,
@@ -1091,27 +1052,15 @@ extern "C" int k4_kalign_ext_batch(k4_index* ix, const k4_kalign_params* p, int6
   if (n == 0) return K4_OK;
   K4_HIP(ix, hipSetDevice(ix->device));
   int max_len = 1;
-  int rc = stage_in(ix, n, reads, offs, lens, p->max_ml, &max_len, 24);
+  int rc = stage_in(ix, n, reads, offs, lens, p->max_ml, &max_len);
   if (rc != K4_OK) return rc;
   K4Workspace& w = ix->ws;
-  Seg2Stage s2;
-  if (seg2 && (rc = s2.alloc(ix, n)) != K4_OK) return rc;
-  rc = k4_kalign_ext_batch_dev(ix, p, n, max_len, w.c_reads, w.c_offs, w.c_lens, w.c_out, w.c_hits, s2.d, ix->stream);
+  K4DevBuf s2;
+  if (seg2) K4_HIP(ix, s2.alloc((size_t)n * sizeof(k4_seg2)));
+  rc = k4_kalign_ext_batch_dev(ix, p, n, max_len, w.c_reads, w.c_offs, w.c_lens, w.c_out, w.c_hits, s2.p, ix->stream);
   if (rc != K4_OK) return rc;
-  if (seg2 && (rc = s2.fetch(ix, seg2, n)) != K4_OK) return rc;
-  if (w.c_small) {
-    const int32_t* r;
-    const k4_hit* h;
-    rc = fetch_small(ix, n, p->max_ml, &r, &h);
-    if (rc != K4_OK) return rc;
-    memcpy(out, r, (size_t)n * sizeof(k4_read_result));
-    memcpy(hits, h, (size_t)n * p->max_ml * sizeof(k4_hit));
-    return K4_OK;
-  }
-  K4_HIP(ix, hipMemcpyAsync(out, w.c_out, (size_t)n * sizeof(k4_read_result), hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipMemcpyAsync(hits, w.c_hits, (size_t)n * p->max_ml * sizeof(k4_hit), hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipStreamSynchronize(ix->stream));
-  return K4_OK;
+  if (seg2 && (rc = seg2_fetch(ix, seg2, s2, n)) != K4_OK) return rc;
+  return stage_out(ix, n, p->max_ml, {out}, sizeof(k4_read_result), hits);
 }
 
 extern "C" int k4_enable_kernel_timing(k4_index* ix, int on) {
@@ -1147,7 +1096,7 @@ extern "C" int k4_get_counters(k4_index* ix, k4_counters* out) {
   if (!ix || !out) return K4_ERR_PARAMS;
   K4_HIP(ix, hipSetDevice(ix->device));
   K4_HIP(ix, hipDeviceSynchronize());
-  K4_HIP(ix, hipMemcpy(out, ix->counters, sizeof(k4_counters), hipMemcpyDeviceToHost));
+  K4_HIP(ix, hipMemcpy(out, ix->counters.p, sizeof(k4_counters), hipMemcpyDeviceToHost));
   return K4_OK;
 }
 
@@ -1156,8 +1105,8 @@ extern "C" int k4i_debug_prof(k4_index* ix, uint64_t* out) {
   if (!ix || !out) return K4_ERR_PARAMS;
   K4_HIP(ix, hipSetDevice(ix->device));
   K4_HIP(ix, hipDeviceSynchronize());
-  K4_HIP(ix, hipMemcpy(out, (char*)ix->counters + sizeof(k4_counters), K4_PROF_SLOTS * 8, hipMemcpyDeviceToHost));
-  K4_HIP(ix, hipMemset((char*)ix->counters + sizeof(k4_counters), 0, K4_PROF_SLOTS * 8));
+  K4_HIP(ix, hipMemcpy(out, ix->counters.as<char>() + sizeof(k4_counters), K4_PROF_SLOTS * 8, hipMemcpyDeviceToHost));
+  K4_HIP(ix, hipMemset(ix->counters.as<char>() + sizeof(k4_counters), 0, K4_PROF_SLOTS * 8));
   return K4_OK;
 }
 
@@ -1165,6 +1114,6 @@ extern "C" int k4_reset_counters(k4_index* ix) {
   if (!ix) return K4_ERR_PARAMS;
   K4_HIP(ix, hipSetDevice(ix->device));
   K4_HIP(ix, hipDeviceSynchronize());
-  K4_HIP(ix, hipMemset(ix->counters, 0, sizeof(k4_counters)));
+  K4_HIP(ix, hipMemset(ix->counters.p, 0, sizeof(k4_counters)));
   return K4_OK;
 }

@@ -92,7 +92,6 @@ struct K4AlignArgs {
   uint32_t* defer_ids;  // first launch: list of the reads set aside (chunked like the survivor lists, ctl[K4_CTL_DEFER])
   uint32_t* ctl;
   unsigned long long* counters;
-  uint8_t* slow_probe;
   uint64_t* slow_hash;
   uint32_t* slow_gen;
   uint32_t slow_hash_cap;

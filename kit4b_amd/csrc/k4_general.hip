@@ -1354,8 +1354,8 @@ __global__ void __launch_bounds__(64 * K4_SLOW_WPB) __attribute__((amdgpu_waves_
 template <int EL>
 static int launch_general(k4_index* ix, K4AlignArgs& a, int max_len, hipStream_t st) {
   K4Workspace& w = ix->ws;
-  uint64_t* small_base = w.slow_hash;
-  uint64_t* big_base = w.slow_hash + (size_t)K4_SLOW_WAVES * K4_SMALL_HASH;
+  uint64_t* small_base = w.slow_hash.as<uint64_t>();
+  uint64_t* big_base = small_base + (size_t)K4_SLOW_WAVES * K4_SMALL_HASH;
   uint32_t* gen_small = reinterpret_cast<uint32_t*>(big_base + (size_t)K4_HUGE_WAVES * w.slow_hash_cap);
   uint32_t* gen_big = gen_small + K4_SLOW_WAVES;
   const int slow_len = std::min(std::max(max_len, 1), K4_MAX_READ_LEN);

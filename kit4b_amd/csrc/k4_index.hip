@@ -289,10 +289,9 @@ __global__ void __launch_bounds__(256) k4k_ktab_deep(const T* __restrict__ tab, 
 template <int EL, typename T>
 static int build_ktab(k4_index* ix) {
   uint64_t nent = (1ull << (2 * ix->d.k)) + 1;
-  T* tab = nullptr;
   const int ST = sizeof(T) == 4 ? K4_KTAB_STRIDE32 : K4_KTAB_STRIDE64;
-  K4_HIP(ix, hipMalloc(&tab, nent * ST * sizeof(T) + 32));
-  ix->ktab = tab;
+  K4_HIP(ix, ix->ktab.alloc(nent * ST * sizeof(T) + 32));
+  T* tab = ix->ktab.as<T>();
   ix->device_bytes += nent * ST * sizeof(T) + 32;
   K4_HIP(ix, hipMemset(tab, 0xFF, nent * ST * sizeof(T) + 32));
   T last = (T)ix->d.n;
@@ -302,22 +301,22 @@ static int build_ktab(k4_index* ix) {
   hipLaunchKernelGGL((k4k_ktab_mark<EL, T>), dim3((unsigned)nb), dim3(256), 0, 0, ix->d, tab);
   K4_HIP(ix, hipGetLastError());
   uint64_t sb = (nent + 2047) / 2048;
-  T* agg = nullptr;
-  K4_HIP(ix, hipMalloc(&agg, sb * sizeof(T)));
-  hipLaunchKernelGGL((k4k_scan_block_min<T>), dim3((unsigned)sb), dim3(256), 0, 0, tab, nent, agg);
-  hipLaunchKernelGGL((k4k_scan_agg<T>), dim3(1), dim3(1024), 0, 0, agg, sb);
-  hipLaunchKernelGGL((k4k_scan_apply<T>), dim3((unsigned)sb), dim3(256), 0, 0, tab, nent, agg);
-  K4_HIP(ix, hipGetLastError());
-  K4_HIP(ix, hipDeviceSynchronize());
-  K4_HIP(ix, hipFree(agg));
   {
-    unsigned long long* d_deep = nullptr;
+    K4DevBuf agg;
+    K4_HIP(ix, agg.alloc(sb * sizeof(T)));
+    hipLaunchKernelGGL((k4k_scan_block_min<T>), dim3((unsigned)sb), dim3(256), 0, 0, tab, nent, agg.as<T>());
+    hipLaunchKernelGGL((k4k_scan_agg<T>), dim3(1), dim3(1024), 0, 0, agg.as<T>(), sb);
+    hipLaunchKernelGGL((k4k_scan_apply<T>), dim3((unsigned)sb), dim3(256), 0, 0, tab, nent, agg.as<T>());
+    K4_HIP(ix, hipGetLastError());
+    K4_HIP(ix, hipDeviceSynchronize());
+  }
+  {
+    K4DevBuf d_deep;
     unsigned long long deep = 0;
-    K4_HIP(ix, hipMalloc(&d_deep, 8));
-    K4_HIP(ix, hipMemset(d_deep, 0, 8));
-    hipLaunchKernelGGL((k4k_ktab_deep<T>), dim3(8192), dim3(256), 0, 0, (const T*)tab, nent - 1, d_deep);
-    K4_HIP(ix, hipMemcpy(&deep, d_deep, 8, hipMemcpyDeviceToHost));
-    K4_HIP(ix, hipFree(d_deep));
+    K4_HIP(ix, d_deep.alloc(8));
+    K4_HIP(ix, hipMemset(d_deep.p, 0, 8));
+    hipLaunchKernelGGL((k4k_ktab_deep<T>), dim3(8192), dim3(256), 0, 0, (const T*)tab, nent - 1, d_deep.as<unsigned long long>());
+    K4_HIP(ix, hipMemcpy(&deep, d_deep.p, 8, hipMemcpyDeviceToHost));
     ix->deep_bucket_frac = ix->d.n ? (double)deep / (double)ix->d.n : 0.0;
   }
   if (sizeof(T) == 8) {
@@ -330,25 +329,25 @@ static int build_ktab(k4_index* ix) {
   return K4_OK;
 }
 
-// d_seq: concat_len bytes (1 byte/base) in HBM; ix->sa, entries and ix->d.{n,el} must already be set.
+// d_seq: concat_len bytes (1 byte/base) in HBM; ix->d.{sa,n,el} and the entries must already be set.
 int k4i_build_device_structures(k4_index* ix, const void* d_seq, int kmer_k) {
   const uint64_t n = ix->d.n;
   const uint64_t n_blocks = (n + 63) / 64;        // 64-base packing units
   const uint64_t words = n_blocks * 4;
   const uint64_t n_eblocks = (n + K4_EXC_BLOCK - 1) >> K4_EXC_SHIFT;
   const uint64_t bm_words = ((n_blocks + 255) / 256) * 2 + 8;  // the pack kernel writes 16 bits per wave; +pad for the 8-byte fetch
-  K4_HIP(ix, hipMalloc(&ix->ref2_alloc, (words + 2 * K4_PAD_WORDS) * 4));
-  K4_HIP(ix, hipMemset(ix->ref2_alloc, 0, (words + 2 * K4_PAD_WORDS) * 4));
-  K4_HIP(ix, hipMalloc(&ix->excbm, bm_words * 4));
-  K4_HIP(ix, hipMemset(ix->excbm, 0, bm_words * 4));
+  K4_HIP(ix, ix->ref2.alloc((words + 2 * K4_PAD_WORDS) * 4));
+  K4_HIP(ix, hipMemset(ix->ref2.p, 0, (words + 2 * K4_PAD_WORDS) * 4));
+  K4_HIP(ix, ix->excbm.alloc(bm_words * 4));
+  K4_HIP(ix, hipMemset(ix->excbm.p, 0, bm_words * 4));
   ix->device_bytes += (words + 2 * K4_PAD_WORDS) * 4 + bm_words * 4;
-  uint32_t* ref2 = ix->ref2_alloc + K4_PAD_WORDS;
+  uint32_t* ref2 = ix->ref2.as<uint32_t>() + K4_PAD_WORDS;
   hipLaunchKernelGGL(k4k_pack_ref, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, 0,
-                     (const uint8_t*)d_seq, n, ref2, (uint16_t*)ix->excbm, n_blocks);
+                     (const uint8_t*)d_seq, n, ref2, ix->excbm.as<uint16_t>(), n_blocks);
   K4_HIP(ix, hipGetLastError());
   // flagged-block list on the host (bitmap is n/512 bytes)
   std::vector<uint32_t> bm(bm_words);
-  K4_HIP(ix, hipMemcpy(bm.data(), ix->excbm, bm_words * 4, hipMemcpyDeviceToHost));
+  K4_HIP(ix, hipMemcpy(bm.data(), ix->excbm.p, bm_words * 4, hipMemcpyDeviceToHost));
   std::vector<uint32_t> blk;
   for (uint64_t w = 0; w < bm_words; w++) {
     uint32_t v = bm[w];
@@ -369,15 +368,15 @@ int k4i_build_device_structures(k4_index* ix, const void* d_seq, int kmer_k) {
     uint64_t b = (uint64_t)id >> (sup_shift - K4_EXC_SHIFT);
     sup[b >> 5] |= 1u << (b & 31);
   }
-  K4_HIP(ix, hipMalloc(&ix->excsup, K4_SUP_WORDS * 4));
-  K4_HIP(ix, hipMemcpy(ix->excsup, sup.data(), K4_SUP_WORDS * 4, hipMemcpyHostToDevice));
-  K4_HIP(ix, hipMalloc(&ix->excblk, (size_t)(n_exc + 1) * 4));
-  K4_HIP(ix, hipMalloc(&ix->excnib, (size_t)(n_exc + 1) * (K4_EXC_BLOCK / 2)));
+  K4_HIP(ix, ix->excsup.alloc(K4_SUP_WORDS * 4));
+  K4_HIP(ix, hipMemcpy(ix->excsup.p, sup.data(), K4_SUP_WORDS * 4, hipMemcpyHostToDevice));
+  K4_HIP(ix, ix->excblk.alloc((size_t)(n_exc + 1) * 4));
+  K4_HIP(ix, ix->excnib.alloc((size_t)(n_exc + 1) * (K4_EXC_BLOCK / 2)));
   ix->device_bytes += (uint64_t)(n_exc + 1) * (4 + K4_EXC_BLOCK / 2);
   if (n_exc) {
-    K4_HIP(ix, hipMemcpy(ix->excblk, blk.data(), (size_t)n_exc * 4, hipMemcpyHostToDevice));
+    K4_HIP(ix, hipMemcpy(ix->excblk.p, blk.data(), (size_t)n_exc * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k4k_exc_nibbles, dim3((unsigned)(((uint64_t)n_exc * (K4_EXC_BLOCK / 8) + 255) / 256)), dim3(256), 0, 0,
-                       (const uint8_t*)d_seq, n, ix->excblk, n_exc, ix->excnib);
+                       (const uint8_t*)d_seq, n, ix->excblk.as<uint32_t>(), n_exc, ix->excnib.as<uint32_t>());
     K4_HIP(ix, hipGetLastError());
   }
   // entries
@@ -391,27 +390,26 @@ int k4i_build_device_structures(k4_index* ix, const void* d_seq, int kmer_k) {
     ei[i] = ix->entries[i].entry_id;
     ix->tot_seqs_len += ix->entries[i].seq_len;
   }
-  K4_HIP(ix, hipMalloc(&ix->ent_start, (size_t)(ne + 1) * 8));
-  K4_HIP(ix, hipMalloc(&ix->ent_end, (size_t)(ne + 1) * 8));
-  K4_HIP(ix, hipMalloc(&ix->ent_id, (size_t)(ne + 1) * 4));
+  K4_HIP(ix, ix->ent_start.alloc((size_t)(ne + 1) * 8));
+  K4_HIP(ix, ix->ent_end.alloc((size_t)(ne + 1) * 8));
+  K4_HIP(ix, ix->ent_id.alloc((size_t)(ne + 1) * 4));
   if (ne) {
-    K4_HIP(ix, hipMemcpy(ix->ent_start, es.data(), (size_t)ne * 8, hipMemcpyHostToDevice));
-    K4_HIP(ix, hipMemcpy(ix->ent_end, ee.data(), (size_t)ne * 8, hipMemcpyHostToDevice));
-    K4_HIP(ix, hipMemcpy(ix->ent_id, ei.data(), (size_t)ne * 4, hipMemcpyHostToDevice));
+    K4_HIP(ix, hipMemcpy(ix->ent_start.p, es.data(), (size_t)ne * 8, hipMemcpyHostToDevice));
+    K4_HIP(ix, hipMemcpy(ix->ent_end.p, ee.data(), (size_t)ne * 8, hipMemcpyHostToDevice));
+    K4_HIP(ix, hipMemcpy(ix->ent_id.p, ei.data(), (size_t)ne * 4, hipMemcpyHostToDevice));
   }
-  K4_HIP(ix, hipMalloc(&ix->counters, sizeof(k4_counters) + K4_PROF_SLOTS * 8));  // (+ the profiling build's slots, k4_align.hip)
-  K4_HIP(ix, hipMemset(ix->counters, 0, sizeof(k4_counters) + K4_PROF_SLOTS * 8));
+  K4_HIP(ix, ix->counters.alloc(sizeof(k4_counters) + K4_PROF_SLOTS * 8));  // (+ the profiling build's slots, k4_align.hip)
+  K4_HIP(ix, hipMemset(ix->counters.p, 0, sizeof(k4_counters) + K4_PROF_SLOTS * 8));
   ix->d.ref2 = ref2;
-  ix->d.excbm = ix->excbm;
-  ix->d.excsup = ix->excsup;
+  ix->d.excbm = ix->excbm.as<uint32_t>();
+  ix->d.excsup = ix->excsup.as<uint32_t>();
   ix->d.sup_shift = sup_shift;
-  ix->d.excblk = ix->excblk;
-  ix->d.excnib = ix->excnib;
+  ix->d.excblk = ix->excblk.as<uint32_t>();
+  ix->d.excnib = ix->excnib.as<uint32_t>();
   ix->d.n_exc = n_exc;
-  ix->d.sa = ix->sa;
-  ix->d.ent_start = ix->ent_start;
-  ix->d.ent_end = ix->ent_end;
-  ix->d.ent_id = ix->ent_id;
+  ix->d.ent_start = ix->ent_start.as<uint64_t>();
+  ix->d.ent_end = ix->ent_end.as<uint64_t>();
+  ix->d.ent_id = ix->ent_id.as<uint32_t>();
   ix->d.n_entries = ne;
   ix->d.k = (uint32_t)choose_k(n, kmer_k);
   // 16-byte entries wherever they fit: besides lb and pos0 they hold the sixteen sub-bucket counts, with which the table answers
@@ -601,37 +599,33 @@ static int open_load(k4_index* ix, const uint8_t* h_seq, const void* d_seq_in, c
   if (rc != K4_OK) return rc;
   // suffix array (padded so the 5-byte reader may touch 8 bytes past the end)
   if (d_sa_in && adopt_sa) {
-    ix->sa = (uint8_t*)d_sa_in;
-    ix->owns_sa = false;
+    ix->d.sa = (const uint8_t*)d_sa_in;  // (lent: ix->sa stays empty and the caller keeps its array)
   } else {
     const double t_m = k4i_now();
-    if ((rc = k4_check_hip(ix, hipMalloc(&ix->sa, n * el + 16), "hipMalloc(sa)")) != K4_OK) return rc;
+    if ((rc = k4_check_hip(ix, ix->sa.alloc(n * el + 16), "hipMalloc(sa)")) != K4_OK) return rc;
+    ix->d.sa = ix->sa.as<uint8_t>();
     if (k4i_trace()) fprintf(stderr, "[k4 trace] device selected and %.2f GB allocated for the suffix array in %.2fs\n", n * el / 1e9, k4i_now() - t_m);
     ix->device_bytes += n * el + 16;
     const double t_a = k4i_now();
-    rc = d_sa_in ? k4_check_hip(ix, hipMemcpy(ix->sa, d_sa_in, n * el, hipMemcpyDeviceToDevice), "hipMemcpy(sa)")
-                 : k4i_upload_pageable(ix, ix->sa, h_sa, (size_t)(n * el));
+    rc = d_sa_in ? k4_check_hip(ix, hipMemcpy(ix->sa.p, d_sa_in, n * el, hipMemcpyDeviceToDevice), "hipMemcpy(sa)")
+                 : k4i_upload_pageable(ix, ix->sa.p, h_sa, (size_t)(n * el));
     if (rc != K4_OK) return rc;
     if (k4i_trace()) fprintf(stderr, "[k4 trace] suffix array %.2f GB on the device in %.2fs\n", n * el / 1e9, k4i_now() - t_a);
   }
   // sequence bytes: temporary on the device, only needed to derive the packed form
-  uint8_t* d_tmp = nullptr;
+  K4DevBuf d_tmp;
   const void* d_seq = d_seq_in;
   if (!d_seq) {
-    if ((rc = k4_check_hip(ix, hipMalloc(&d_tmp, n + 64), "hipMalloc(seq)")) != K4_OK) return rc;
+    if ((rc = k4_check_hip(ix, d_tmp.alloc(n + 64), "hipMalloc(seq)")) != K4_OK) return rc;
     const double t_c = k4i_now();
-    rc = k4i_upload_pageable(ix, d_tmp, h_seq, (size_t)n);
+    rc = k4i_upload_pageable(ix, d_tmp.p, h_seq, (size_t)n);
     if (k4i_trace()) fprintf(stderr, "[k4 trace] sequence %.2f GB on the device in %.2fs\n", n / 1e9, k4i_now() - t_c);
-    if (rc != K4_OK) {
-      hipFree(d_tmp);
-      return rc;
-    }
-    d_seq = d_tmp;
+    if (rc != K4_OK) return rc;
+    d_seq = d_tmp.p;
   }
   const double t_b = k4i_now();
   rc = k4i_build_device_structures(ix, d_seq, kmer_k);
   if (k4i_trace()) { (void)hipDeviceSynchronize(); fprintf(stderr, "[k4 trace] packed reference, exception tables, k-mer table built in %.2fs\n", k4i_now() - t_b); }
-  if (d_tmp) hipFree(d_tmp);
   return rc;
 }
 static int open_common(uint64_t n, uint32_t el, const uint8_t* h_seq, const void* d_seq_in, const uint8_t* h_sa,
@@ -643,7 +637,6 @@ static int open_common(uint64_t n, uint32_t el, const uint8_t* h_seq, const void
   rc = open_load(ix, h_seq, d_seq_in, h_sa, d_sa_in, adopt_sa, kmer_k);
   if (rc != K4_OK) {
     const std::string keep = ix->err;
-    if (d_sa_in && adopt_sa) { ix->sa = nullptr; ix->owns_sa = true; }  // (the caller keeps what it handed in)
     k4_close(ix);
     k4_set_global_error("%s", keep.c_str());
     *out = nullptr;
@@ -851,24 +844,13 @@ extern "C" void k4_close(k4_index* ix) {
   if (!ix) return;
   if (ix->loader.joinable()) ix->loader.join();
   hipSetDevice(ix->device);
-  K4Workspace& w = ix->ws;
-  void* ptrs[] = {ix->ref2_alloc, ix->excbm, ix->excsup, ix->excblk, ix->excnib, ix->owns_sa ? ix->sa : nullptr, ix->ktab,
-                  ix->ent_start, ix->ent_end, ix->ent_id, ix->counters, w.ids[0], w.ids[1], w.rows[0], w.rows[1], w.slow_list, w.slow_step, w.huge_list, w.huge_step, w.ctl,
-                  w.slow_probe, w.slow_hash, w.d_reads, w.d_offs, w.d_lens, w.d_out4, w.d_hits};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
-  if (ix->d_qlut) hipFree(ix->d_qlut);
-  if (ix->d_run_stats) hipFree(ix->d_run_stats);
-  if (w.d_small) hipFree(w.d_small);
-  if (w.h_small) hipHostFree(w.h_small);
-  for (void* p : {(void*)ix->pe_rr, (void*)ix->pe_hits, (void*)ix->pe_list, (void*)ix->pe_ctl, ix->rs_tasks, ix->rs_reads, ix->rs_res, ix->rs_hits})
-    if (p) hipFree(p);
   if (ix->stream) hipStreamDestroy(ix->stream);
-  k4_pool_trim_current_device();  // the ingest / emit stages' cached scratch (k4_pool.h)
   for (hipEvent_t e : ix->ev0) hipEventDestroy(e);
   for (hipEvent_t e : ix->ev1) hipEventDestroy(e);
   for (hipEvent_t e : ix->ev2) hipEventDestroy(e);
-  delete ix;
+  k4_pool_trim_current_device();  // the ingest / emit stages' cached scratch (k4_pool.h)
+  if (ix->ws.h_small) hipHostFree(ix->ws.h_small);
+  delete ix;  // (every device block of the index and its workspaces is a K4DevBuf member)
 }
 
 // ---- accessors ------------------------------------------------------------------------------------------------
@@ -931,8 +913,8 @@ extern "C" int k4_set_fastq_quality(k4_index* ix, int method) {
     if (Qphred > 40) Qphred = 40;
     lut[c] = (uint8_t)((((uint32_t)Qphred + 2) * 15) / 40);
   }
-  if (!ix->d_qlut && (rc = k4_check_hip(ix, hipMalloc(&ix->d_qlut, 256), "hipMalloc(quality table)")) != K4_OK) return rc;
-  return k4_check_hip(ix, hipMemcpy(ix->d_qlut, lut, 256, hipMemcpyHostToDevice), "hipMemcpy(quality table)");
+  if ((rc = k4_check_hip(ix, ix->d_qlut.reserve(256), "hipMalloc(quality table)")) != K4_OK) return rc;
+  return k4_check_hip(ix, hipMemcpy(ix->d_qlut.p, lut, 256, hipMemcpyHostToDevice), "hipMemcpy(quality table)");
 }
 
 extern "C" int k4_set_max_iter(k4_index* ix, int max_iter) {  // CSfxArray::SetMaxIter, SfxArray.cpp:1501
@@ -947,13 +929,13 @@ extern "C" int k4i_debug_ktab(const k4_index* ix, uint64_t c, uint64_t* out) {
   if (!ix || !out) return K4_ERR_PARAMS;
   hipSetDevice(ix->device);
   if (ix->d.ktab64) {
-    if (hipMemcpy(out, (const uint64_t*)ix->ktab + K4_KTAB_STRIDE64 * c, 16, hipMemcpyDeviceToHost) != hipSuccess) return K4_ERR_NO_DEVICE;
+    if (hipMemcpy(out, (const uint64_t*)ix->d.ktab + K4_KTAB_STRIDE64 * c, 16, hipMemcpyDeviceToHost) != hipSuccess) return K4_ERR_NO_DEVICE;
     out[2] = (out[0] >> 40) | ((out[1] >> 40) << 24);  // the sixteen 3-bit sub-bucket counts
     out[0] &= K4_KTAB64_MASK;
     out[1] &= K4_KTAB64_MASK;
   } else {
     uint32_t v[3];
-    if (hipMemcpy(v, (const uint32_t*)ix->ktab + K4_KTAB_STRIDE32 * c, 12, hipMemcpyDeviceToHost) != hipSuccess) return K4_ERR_NO_DEVICE;
+    if (hipMemcpy(v, (const uint32_t*)ix->d.ktab + K4_KTAB_STRIDE32 * c, 12, hipMemcpyDeviceToHost) != hipSuccess) return K4_ERR_NO_DEVICE;
     out[0] = v[0]; out[1] = v[1]; out[2] = v[2];
   }
   return K4_OK;
@@ -963,18 +945,14 @@ static int unpack_to_host(const k4_index* cix, uint64_t start, uint64_t len, uin
   k4_index* ix = const_cast<k4_index*>(cix);
   hipSetDevice(ix->device);
   const uint64_t chunk = 64ull << 20;
-  uint8_t* d = nullptr;
-  K4_HIP(ix, hipMalloc(&d, std::min(chunk, len ? len : 1)));
+  K4DevBuf d;
+  K4_HIP(ix, d.alloc(std::min(chunk, len)));
   for (uint64_t o = 0; o < len; o += chunk) {
     uint64_t c = std::min(chunk, len - o);
-    hipLaunchKernelGGL(k4k_unpack_range, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, 0, ix->d, start + o, c, d);
-    hipError_t e = hipMemcpy(out + o, d, c, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-      hipFree(d);
-      return k4_check_hip(ix, e, "unpack copy");
-    }
+    hipLaunchKernelGGL(k4k_unpack_range, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, 0, ix->d, start + o, c, d.as<uint8_t>());
+    const int rc = k4_check_hip(ix, hipMemcpy(out + o, d.p, c, hipMemcpyDeviceToHost), "unpack copy");
+    if (rc != K4_OK) return rc;
   }
-  hipFree(d);
   return K4_OK;
 }
 
@@ -1048,7 +1026,7 @@ extern "C" int k4_write_sfx(const k4_index* cix, const char* path) {
   hipSetDevice(ix->device);
   for (uint64_t o = 0; o < n * el; o += chunk) {
     uint64_t c = std::min(chunk, n * el - o);
-    hipError_t e = hipMemcpy(buf.data(), ix->sa + o, c, hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(buf.data(), ix->d.sa + o, c, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { fclose(fp); return k4_check_hip(ix, e, "sa copy"); }
     fwrite(buf.data(), 1, c, fp);
   }

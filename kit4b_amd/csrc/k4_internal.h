@@ -6,6 +6,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/k4sfx.h"
+#include "k4_pool.h"
 
 // ---- HBM layout of the index --------------------------------------------------------------------------
 // ref2      2-bit packed reference, MSB-first inside 32-bit words: base i lives in bits (30 - 2*(i & 15)) of
@@ -64,26 +65,24 @@ struct K4Workspace {
   int64_t cap_reads = 0;
   int32_t cap_len = 0;
   int32_t cap_hits = 0;
-  uint32_t* ids[2] = {nullptr, nullptr};   // survivors of a step: read ids ...
-  uint64_t* rows[2] = {nullptr, nullptr};  // ... and their packed rows (forward + reverse-complement words)
-  uint32_t* slow_list = nullptr; // read ids for the general kernel
-  uint8_t* slow_step = nullptr;  // and the phase ordinal at which each left the fast path
-  uint32_t* huge_list = nullptr; // reads that outgrew the small dedupe tables of the first general pass
-  uint8_t* huge_step = nullptr;
-  uint32_t* ctl = nullptr;       // [0] slow count, [1] slow head, [2+t] survivor count of step t
-  uint8_t* slow_probe = nullptr; // per slow lane: probe bytes scratch
-  uint64_t* slow_hash = nullptr; // per slow lane: open-addressing table of (generation<<32 | TargSeqID)
-  uint32_t slow_lanes = 0;
+  K4DevBuf ids[2];       // survivors of a step: read ids (u32) ...
+  K4DevBuf rows[2];      // ... and their packed rows (u64: forward + reverse-complement words)
+  K4DevBuf slow_list;    // read ids (u32) for the general kernel
+  K4DevBuf slow_step;    // and the phase ordinal (u8) at which each left the fast path
+  K4DevBuf huge_list;    // reads that outgrew the small dedupe tables of the first general pass
+  K4DevBuf huge_step;
+  K4DevBuf ctl;          // u32: [0] slow count, [1] slow head, [2+t] survivor count of step t
+  K4DevBuf slow_hash;    // u64, per slow lane: open-addressing table of (generation<<32 | TargSeqID)
   uint32_t slow_hash_cap = 0;    // entries per lane (power of two)
   // staging for the host-pointer entry points
-  uint8_t* d_reads = nullptr; size_t d_reads_cap = 0;
-  uint64_t* d_offs = nullptr; uint32_t* d_lens = nullptr;
-  int32_t* d_out4 = nullptr;     // rslt/inst/low/nxt or k4_read_result
-  k4_hit* d_hits = nullptr;
+  K4DevBuf d_reads, d_offs, d_lens;
+  K4DevBuf d_out4;       // rslt/inst/low/nxt or k4_read_result
+  K4DevBuf d_hits;
   int64_t stage_reads = 0; int32_t stage_hits = 0;
   // small host-pointer batches (the facade's AlignReads groups): one pinned block up, one down.  [0, K4_SMALL_STAGE/2):
   // offs | lens | reads; [K4_SMALL_STAGE/2, K4_SMALL_STAGE): results | hits -- same layout in h_small and d_small
-  uint8_t* h_small = nullptr; uint8_t* d_small = nullptr;
+  uint8_t* h_small = nullptr;  // (pinned: k4_close frees it)
+  K4DevBuf d_small;
   // where the current host-pointer batch lives on the device (d_small or the d_* buffers above)
   const uint8_t* c_reads = nullptr; const uint64_t* c_offs = nullptr; const uint32_t* c_lens = nullptr;
   int32_t* c_out = nullptr; k4_hit* c_hits = nullptr; bool c_small = false;
@@ -92,26 +91,16 @@ struct K4Workspace {
 struct k4_index {
   int device = 0;
   K4DevIndex d{};
-  // owning pointers
-  uint32_t* ref2_alloc = nullptr;
-  uint32_t* excbm = nullptr;
-  uint32_t* excsup = nullptr;
-  uint32_t* excblk = nullptr;
-  uint32_t* excnib = nullptr;
-  uint8_t* sa = nullptr;
-  bool owns_sa = true;
-  void* ktab = nullptr;
-  uint64_t* ent_start = nullptr;
-  uint64_t* ent_end = nullptr;
-  uint32_t* ent_id = nullptr;
-  uint64_t* counters = nullptr; // device k4_counters
+  // the blocks d points into (ref2: K4_PAD_WORDS in front of d.ref2; sa: empty when d.sa is an array the caller lent, k4_open_device)
+  K4DevBuf ref2, excbm, excsup, excblk, excnib, sa, ktab, ent_start, ent_end, ent_id;
+  K4DevBuf counters;  // device k4_counters
   // FASTQ qualities (kalign -g, etFQMethod): 3 = ignored (the default); 0 Sanger / 1 Illumina 1.3+ / 2 Solexa: the parser puts the
   // scaled 4-bit score of every base into bits 4..7 of its read byte (the reference's own in-memory form), the SAM / BAM writers emit it
   int q_method = 3;
-  uint8_t* d_qlut = nullptr;    // 256 bytes: quality character -> 4-bit score of the chosen method
+  K4DevBuf d_qlut;              // 256 bytes: quality character -> 4-bit score of the chosen method
   // `kalign -O` run tallies (k4_align_stats_collect, k4_stats.hip): K4_STATS_MULTI multihit bins, then K4_STATS_PE_LEN + 1 insert lengths;
-  // null = not collected (the align and pairing kernels then do nothing more than before)
-  unsigned long long* d_run_stats = nullptr;
+  // empty = not collected (the align and pairing kernels then do nothing more than before)
+  K4DevBuf d_run_stats;
   uint64_t filter_prior[20] = {0};  // reads the filter stages (k4_filter.hip) marked so far, by the NAR they carried before
   double deep_bucket_frac = 0;  // share of the suffixes that sit in k-mer buckets deeper than K4_DEEP_BUCKET (k4_index.hip)
   std::vector<k4_entry> entries;
@@ -123,15 +112,11 @@ struct k4_index {
   std::string err;
   K4Workspace ws;
   // paired-end pass (k4_pe.hip): both ends' SE results, their hit slots, the orphan list, {orphan count, error flag}
-  k4_read_result* pe_rr = nullptr;
-  k4_hit* pe_hits = nullptr;
-  uint32_t* pe_list = nullptr;
-  uint32_t* pe_ctl = nullptr;
+  K4DevBuf pe_rr, pe_hits, pe_list, pe_ctl;
   int64_t pe_cap_pairs = 0;
   int32_t pe_cap_hits = 0;
   // staging of k4_mate_rescue_batch (grow-only)
-  void *rs_tasks = nullptr, *rs_reads = nullptr, *rs_res = nullptr, *rs_hits = nullptr;
-  size_t rs_cap_tasks = 0, rs_cap_reads = 0;
+  K4DevBuf rs_tasks, rs_reads, rs_res, rs_hits;
   // k4_open_async: the arrays are uploaded and the device structures built by this thread; k4_open_wait joins it
   std::thread loader;
   int load_rc = 0;

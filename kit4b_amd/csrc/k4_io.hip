@@ -362,10 +362,10 @@ extern "C" int k4_parse_fastx_dev(k4_index* ix, const void* d_text_v, uint64_t t
     K4_HIP(ix, hipMemsetAsync(tot.p, 0, 16, st));  // bases and longest are counted again, exactly
     exact = true;
   }
-  if (fastq && ix->q_method != 3 && ix->d_qlut) {  // kalign -g0..2: the scores ride in the read bytes
+  if (fastq && ix->q_method != 3 && ix->d_qlut.p) {  // kalign -g0..2: the scores ride in the read bytes
     K4_HIP(ix, hipMemsetAsync(tot.as<unsigned long long>() + 3, 0, 4, st));
     hipLaunchKernelGGL(k4k_fastq_quals, dim3((unsigned)std::min<int64_t>((n_rec + 3) / 4, 1 << 16)), dim3(64), 0, st, text, nlb.as<uint32_t>(),
-                       (const uint64_t*)d_offs, (const uint32_t*)d_lens, n_rec, (uint8_t*)d_reads, (const uint8_t*)ix->d_qlut,
+                       (const uint64_t*)d_offs, (const uint32_t*)d_lens, n_rec, (uint8_t*)d_reads, ix->d_qlut.as<const uint8_t>(),
                        reinterpret_cast<uint32_t*>(tot.as<unsigned long long>() + 3));
     uint32_t mis = 0;
     K4_TRY(k4s_read_back(ix, &mis, tot.as<unsigned long long>() + 3, st));

@@ -343,27 +343,16 @@ extern "C" int k4_mate_rescue_batch(k4_index* ix, int64_t n, const k4_rescue_tas
     if (tasks[i].read_off + tasks[i].read_len > reads_bytes) return k4_fail(ix, K4_ERR_PARAMS, "rescue task %lld outside the read buffer", (long long)i);
   K4_HIP(ix, hipSetDevice(ix->device));
   // staging buffers live with the index and only grow (the facade's AlignPairedRead comes here once per orphan read)
-  if ((size_t)n > ix->rs_cap_tasks) {
-    for (void* p : {(void*)ix->rs_tasks, (void*)ix->rs_res, (void*)ix->rs_hits})
-      if (p) hipFree(p);
-    ix->rs_tasks = nullptr; ix->rs_res = nullptr; ix->rs_hits = nullptr; ix->rs_cap_tasks = 0;
-    const size_t cap = std::max<size_t>((size_t)n, 256);
-    K4_HIP(ix, hipMalloc(&ix->rs_tasks, cap * sizeof(k4_rescue_task)));
-    K4_HIP(ix, hipMalloc(&ix->rs_res, cap * 4));
-    K4_HIP(ix, hipMalloc(&ix->rs_hits, cap * sizeof(k4_hit)));
-    ix->rs_cap_tasks = cap;
-  }
-  if (reads_bytes + 16 > ix->rs_cap_reads) {
-    if (ix->rs_reads) hipFree(ix->rs_reads);
-    ix->rs_reads = nullptr; ix->rs_cap_reads = 0;
-    const size_t cap = std::max<size_t>(reads_bytes + 16, 1 << 16);
-    K4_HIP(ix, hipMalloc(&ix->rs_reads, cap));
-    ix->rs_cap_reads = cap;
-  }
-  k4_rescue_task* d_t = (k4_rescue_task*)ix->rs_tasks;
-  uint8_t* d_r = (uint8_t*)ix->rs_reads;
-  int32_t* d_res = (int32_t*)ix->rs_res;
-  k4_hit* d_h = (k4_hit*)ix->rs_hits;
+  // (each is sized by the task count alone, or by the read bytes alone: its own capacity says whether it has to grow)
+  const size_t cap = std::max<size_t>((size_t)n, 256);
+  K4_HIP(ix, ix->rs_tasks.reserve(cap * sizeof(k4_rescue_task)));
+  K4_HIP(ix, ix->rs_res.reserve(cap * 4));
+  K4_HIP(ix, ix->rs_hits.reserve(cap * sizeof(k4_hit)));
+  K4_HIP(ix, ix->rs_reads.reserve(std::max<size_t>(reads_bytes + 16, 1 << 16)));
+  k4_rescue_task* d_t = ix->rs_tasks.as<k4_rescue_task>();
+  uint8_t* d_r = ix->rs_reads.as<uint8_t>();
+  int32_t* d_res = ix->rs_res.as<int32_t>();
+  k4_hit* d_h = ix->rs_hits.as<k4_hit>();
   hipStream_t st = ix->stream;
   hipMemcpyAsync(d_t, tasks, (size_t)n * sizeof(k4_rescue_task), hipMemcpyHostToDevice, st);
   hipMemcpyAsync(d_r, reads, reads_bytes, hipMemcpyHostToDevice, st);
@@ -586,14 +575,12 @@ static int pe_reserve(k4_index* ix, int64_t n_pairs, int mh) {
   if (n_pairs <= ix->pe_cap_pairs && mh <= ix->pe_cap_hits) return K4_OK;
   const int64_t cap = std::max(n_pairs, ix->pe_cap_pairs);
   const int h = std::max(mh, ix->pe_cap_hits);
-  for (void* p : {(void*)ix->pe_rr, (void*)ix->pe_hits, (void*)ix->pe_list, (void*)ix->pe_ctl})
-    if (p) hipFree(p);
-  ix->pe_rr = nullptr; ix->pe_hits = nullptr; ix->pe_list = nullptr; ix->pe_ctl = nullptr;
   ix->pe_cap_pairs = 0;
-  K4_HIP(ix, hipMalloc(&ix->pe_rr, (size_t)(2 * cap + 1) * sizeof(k4_read_result)));
-  K4_HIP(ix, hipMalloc(&ix->pe_hits, (size_t)(2 * cap + 1) * h * sizeof(k4_hit)));
-  K4_HIP(ix, hipMalloc(&ix->pe_list, (size_t)(cap + 1) * 4));
-  K4_HIP(ix, hipMalloc(&ix->pe_ctl, 16));
+  ix->pe_cap_hits = 0;
+  K4_HIP(ix, ix->pe_rr.reserve((size_t)(2 * cap + 1) * sizeof(k4_read_result)));
+  K4_HIP(ix, ix->pe_hits.reserve((size_t)(2 * cap + 1) * h * sizeof(k4_hit)));
+  K4_HIP(ix, ix->pe_list.reserve((size_t)(cap + 1) * 4));
+  K4_HIP(ix, ix->pe_ctl.reserve(16));
   ix->pe_cap_pairs = cap;
   ix->pe_cap_hits = h;
   return K4_OK;
@@ -623,11 +610,11 @@ extern "C" int k4_kalign_pe_batch_dev(k4_index* ix, const k4_kalign_params* p, c
   rc = k4_reserve(ix, 2 * n_pairs, max_read_len, mh);
   if (rc != K4_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  K4_HIP(ix, hipMemsetAsync(ix->pe_ctl, 0, 16, st));
-  rc = k4i_kalign_batch_dev(ix, &kp, 2 * n_pairs, max_read_len, d_reads, d_offs, d_lens, ix->pe_rr, ix->pe_hits, stream, 1);
+  K4_HIP(ix, hipMemsetAsync(ix->pe_ctl.p, 0, 16, st));
+  rc = k4i_kalign_batch_dev(ix, &kp, 2 * n_pairs, max_read_len, d_reads, d_offs, d_lens, ix->pe_rr.p, ix->pe_hits.p, stream, 1);
   if (rc != K4_OK) return rc;
-  hipLaunchKernelGGL(k4k_pe_pair, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, pe, n_pairs, mh, ix->pe_rr,
-                     ix->pe_hits, (k4_pe_read*)d_out, ix->pe_list, ix->pe_ctl, k4i_stats_pe_len_dist(ix));
+  hipLaunchKernelGGL(k4k_pe_pair, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, pe, n_pairs, mh, ix->pe_rr.as<k4_read_result>(),
+                     ix->pe_hits.as<k4_hit>(), (k4_pe_read*)d_out, ix->pe_list.as<uint32_t>(), ix->pe_ctl.as<uint32_t>(), k4i_stats_pe_len_dist(ix));
   if (pe.pe_mode == 1 || pe.pe_mode == 3) {
     K4PeChim ch = {0, 0, 1, p->min_edit_dist};
     if (p->min_chimeric_len > 0) {
@@ -639,8 +626,8 @@ extern "C" int k4_kalign_pe_batch_dev(k4_index* ix, const k4_kalign_params* p, c
     }
     hipLaunchKernelGGL(k4k_pe_orphans, dim3((unsigned)std::min<int64_t>(n_pairs, 256 * 32)), dim3(64),
                        ch.min_chimeric_len > 0 ? K4_RESCUE_LDS_CHIM : K4_RESCUE_LDS, st, ix->d, pe, p->max_subs,
-                       (const uint8_t*)d_reads, (const uint64_t*)d_offs, (const uint32_t*)d_lens, ix->pe_list,
-                       (k4_pe_read*)d_out, ix->pe_ctl, ch, k4i_stats_pe_len_dist(ix));
+                       (const uint8_t*)d_reads, (const uint64_t*)d_offs, (const uint32_t*)d_lens, ix->pe_list.as<uint32_t>(),
+                       (k4_pe_read*)d_out, ix->pe_ctl.as<uint32_t>(), ch, k4i_stats_pe_len_dist(ix));
   }
   K4_HIP(ix, hipGetLastError());
   K4_HIP(ix, hipStreamSynchronize(st));  // (the call's contract, include/k4sfx.h: the stream is waited for)
@@ -662,24 +649,13 @@ extern "C" int k4_kalign_pe_batch(k4_index* ix, const k4_kalign_params* p, const
   std::vector<uint8_t> cat;
   std::vector<uint64_t> offs;
   std::vector<uint32_t> lens;
-  uint8_t* d_reads = nullptr;
-  uint64_t* d_offs = nullptr;
-  uint32_t* d_lens = nullptr;
-  k4_pe_read* d_out = nullptr;
-  size_t reads_cap = 0;
-  auto cleanup = [&]() {
-    for (void* q : {(void*)d_reads, (void*)d_offs, (void*)d_lens, (void*)d_out})
-      if (q) hipFree(q);
-  };
+  K4DevBuf d_reads, d_offs, d_lens, d_out;
   int rc = K4_OK;
   const int64_t cap = std::min(n_pairs, slice);
-  if ((rc = k4_check_hip(ix, hipMalloc(&d_offs, (size_t)(2 * cap + 1) * 8), "PE staging")) != K4_OK ||
-      (rc = k4_check_hip(ix, hipMalloc(&d_lens, (size_t)(2 * cap + 1) * 4), "PE staging")) != K4_OK ||
-      (rc = k4_check_hip(ix, hipMalloc(&d_out, (size_t)(2 * cap + 1) * sizeof(k4_pe_read)), "PE staging")) != K4_OK) {
-    cleanup();
-    return rc;
-  }
-  for (int64_t s0 = 0; s0 < n_pairs && rc == K4_OK; s0 += slice) {
+  if ((rc = k4_check_hip(ix, d_offs.alloc((size_t)(2 * cap + 1) * 8), "PE staging")) != K4_OK) return rc;
+  if ((rc = k4_check_hip(ix, d_lens.alloc((size_t)(2 * cap + 1) * 4), "PE staging")) != K4_OK) return rc;
+  if ((rc = k4_check_hip(ix, d_out.alloc((size_t)(2 * cap + 1) * sizeof(k4_pe_read)), "PE staging")) != K4_OK) return rc;
+  for (int64_t s0 = 0; s0 < n_pairs; s0 += slice) {
     const int64_t n = std::min(slice, n_pairs - s0);
     uint64_t tot = 0;
     int max_len = 1;
@@ -687,7 +663,7 @@ extern "C" int k4_kalign_pe_batch(k4_index* ix, const k4_kalign_params* p, const
       tot += (uint64_t)lens1[i] + lens2[i];
       max_len = std::max<int>(max_len, (int)std::max(lens1[i], lens2[i]));
     }
-    if (max_len > K4_MAX_READ_LEN) { rc = k4_fail(ix, K4_ERR_PARAMS, "read longer than %d bases", K4_MAX_READ_LEN); break; }
+    if (max_len > K4_MAX_READ_LEN) return k4_fail(ix, K4_ERR_PARAMS, "read longer than %d bases", K4_MAX_READ_LEN);
     cat.resize(tot + 16);
     offs.resize((size_t)2 * n);
     lens.resize((size_t)2 * n);
@@ -700,20 +676,14 @@ extern "C" int k4_kalign_pe_batch(k4_index* ix, const k4_kalign_params* p, const
       memcpy(cat.data() + o, reads2 + offs2[s0 + i], lens2[s0 + i]);
       o += lens2[s0 + i];
     }
-    if (tot + 64 > reads_cap) {
-      if (d_reads) hipFree(d_reads);
-      d_reads = nullptr;
-      if ((rc = k4_check_hip(ix, hipMalloc(&d_reads, tot + 64), "PE staging")) != K4_OK) break;
-      reads_cap = tot + 64;
-    }
+    if ((rc = k4_check_hip(ix, d_reads.reserve(tot + 64), "PE staging")) != K4_OK) return rc;
     hipStream_t st = ix->stream;
-    if ((rc = k4_check_hip(ix, hipMemcpyAsync(d_reads, cat.data(), tot, hipMemcpyHostToDevice, st), "PE upload")) != K4_OK) break;
-    if ((rc = k4_check_hip(ix, hipMemcpyAsync(d_offs, offs.data(), (size_t)2 * n * 8, hipMemcpyHostToDevice, st), "PE upload")) != K4_OK) break;
-    if ((rc = k4_check_hip(ix, hipMemcpyAsync(d_lens, lens.data(), (size_t)2 * n * 4, hipMemcpyHostToDevice, st), "PE upload")) != K4_OK) break;
-    rc = k4_kalign_pe_batch_dev(ix, p, pe_in, n, max_len, d_reads, d_offs, d_lens, d_out, st);
-    if (rc != K4_OK) break;
-    rc = k4_check_hip(ix, hipMemcpy(out + 2 * s0, d_out, (size_t)2 * n * sizeof(k4_pe_read), hipMemcpyDeviceToHost), "PE download");
+    if ((rc = k4_check_hip(ix, hipMemcpyAsync(d_reads.p, cat.data(), tot, hipMemcpyHostToDevice, st), "PE upload")) != K4_OK) return rc;
+    if ((rc = k4_check_hip(ix, hipMemcpyAsync(d_offs.p, offs.data(), (size_t)2 * n * 8, hipMemcpyHostToDevice, st), "PE upload")) != K4_OK) return rc;
+    if ((rc = k4_check_hip(ix, hipMemcpyAsync(d_lens.p, lens.data(), (size_t)2 * n * 4, hipMemcpyHostToDevice, st), "PE upload")) != K4_OK) return rc;
+    if ((rc = k4_kalign_pe_batch_dev(ix, p, pe_in, n, max_len, d_reads.p, d_offs.p, d_lens.p, d_out.p, st)) != K4_OK) return rc;
+    rc = k4_check_hip(ix, hipMemcpy(out + 2 * s0, d_out.p, (size_t)2 * n * sizeof(k4_pe_read), hipMemcpyDeviceToHost), "PE download");
+    if (rc != K4_OK) return rc;
   }
-  cleanup();
-  return rc;
+  return K4_OK;
 }

@@ -136,3 +136,29 @@ struct K4PoolBuf {
   }
   template <typename T> T* as() { return (T*)p; }
 };
+
+// Owning device block outside the pool: hipMalloc (the pool's cache is given back first when memory is short), hipFree when it
+// goes out of scope.  A stage's scratch, a temporary of the index build, or a member of k4_index / K4Workspace, which `delete ix`
+// (k4_close) frees with the index.
+struct K4DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;  // bytes held
+  K4DevBuf() = default;
+  K4DevBuf(const K4DevBuf&) = delete;
+  K4DevBuf& operator=(const K4DevBuf&) = delete;
+  ~K4DevBuf() { release(); }
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+  hipError_t alloc(size_t bytes) {  // lets go of what it held
+    release();
+    if (!bytes) bytes = 1;
+    const hipError_t e = k4_malloc_retry(&p, bytes);
+    if (e == hipSuccess) cap = bytes; else p = nullptr;
+    return e;
+  }
+  // Grow-only: nothing happens while it holds `bytes` or more; otherwise the block is replaced (contents are not kept), and a
+  // failure leaves it empty with cap 0.  Buffers that grow as a group (k4_reserve, stage_in, pe_reserve) keep the group's own
+  // capacity fields at zero until every reserve of the group has succeeded, so that a failure part-way leaves a group every
+  // user refuses instead of one with buffers of mixed sizes.
+  hipError_t reserve(size_t bytes) { return p && cap >= bytes ? hipSuccess : alloc(bytes); }
+  template <typename T> T* as() const { return (T*)p; }
+};

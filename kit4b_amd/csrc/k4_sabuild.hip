@@ -134,13 +134,6 @@ __global__ void __launch_bounds__(256) k4k_sa_to_el5(const VT* __restrict__ sa32
 }
 
 namespace {
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  void release() { if (p) hipFree(p); p = nullptr; }
-  template <typename T> T* as() { return (T*)p; }
-};
 #define SA_HIP(call)                                                                              \
   do {                                                                                            \
     hipError_t _e = (call);                                                                       \
@@ -163,7 +156,7 @@ static int refine_sorted(const uint8_t* d_seq, uint64_t n, uint64_t cnt_items, u
                          hipStream_t st, std::string* err) {
   constexpr unsigned VBITS = sizeof(VT) == 4 ? 32u : 40u;  // rank / offset bits that matter
   // ---- ties after level 0 -----------------------------------------------------------------------------------
-  DevBuf flag, cnt;
+  K4DevBuf flag, cnt;
   SA_HIP(flag.alloc(cnt_items));
   SA_HIP(cnt.alloc(8));
   hipLaunchKernelGGL(k4k_sa_ties0, dim3(nblk(cnt_items)), dim3(256), 0, st, keys, cnt_items, flag.as<uint8_t>());
@@ -172,7 +165,7 @@ static int refine_sorted(const uint8_t* d_seq, uint64_t n, uint64_t cnt_items, u
   size_t sbytes = 0;
   rocprim::counting_iterator<VT> ranks(0);
   SA_HIP(rocprim::select(nullptr, sbytes, ranks, flag.as<uint8_t>(), rk_all, cnt.as<uint64_t>(), (size_t)cnt_items, st));
-  DevBuf stmp;
+  K4DevBuf stmp;
   SA_HIP(stmp.alloc(sbytes));
   SA_HIP(rocprim::select(stmp.p, sbytes, ranks, flag.as<uint8_t>(), rk_all, cnt.as<uint64_t>(), (size_t)cnt_items, st));
   uint64_t m = 0;
@@ -186,7 +179,7 @@ static int refine_sorted(const uint8_t* d_seq, uint64_t n, uint64_t cnt_items, u
     // Refinement working set, one row per still-tied suffix, ordered by rank (tie groups are contiguous):
     //   rk   rank in the suffix array (fixed: a group keeps its rank range)     sf  suffix offset
     //   gh   rank of the group's first member (ascending along the list)
-    DevBuf rk, rk2, sf, sf2, gh, gh2, key, key2, pa, pb, ga, gb, fl2, nh;
+    K4DevBuf rk, rk2, sf, sf2, gh, gh2, key, key2, pa, pb, ga, gb, fl2, nh;
     SA_HIP(rk.alloc(m * sizeof(VT))); SA_HIP(rk2.alloc(m * sizeof(VT)));
     SA_HIP(sf.alloc(m * sizeof(VT))); SA_HIP(sf2.alloc(m * sizeof(VT)));
     SA_HIP(gh.alloc(m * sizeof(VT))); SA_HIP(gh2.alloc(m * sizeof(VT)));
@@ -207,7 +200,7 @@ static int refine_sorted(const uint8_t* d_seq, uint64_t n, uint64_t cnt_items, u
       SA_HIP(rocprim::select(nullptr, b_sel, rk.as<VT>(), fl2.as<uint8_t>(), rk2.as<VT>(), cnt.as<uint64_t>(), (size_t)m, st));
     }
     const size_t rtb = std::max(std::max(b_s1, b_s2), std::max(b_sel, b_scan));
-    DevBuf rtmp;
+    K4DevBuf rtmp;
     SA_HIP(rtmp.alloc(rtb));
     size_t tb = rtb;
     SA_HIP(rocprim::inclusive_scan(rtmp.p, tb, gh2.as<VT>(), gh.as<VT>(), (size_t)m, MaxOp(), st));
@@ -257,7 +250,7 @@ template <typename VT>
 static int build_sa_t(uint64_t n, uint32_t el, const uint8_t* d_seq, uint8_t* d_sa, int device, std::string* err) {
   SA_HIP(hipSetDevice(device));
   hipStream_t st = 0;
-  DevBuf k0, k1, v0, v1, tmp;
+  K4DevBuf k0, k1, v0, v1, tmp;
   SA_HIP(k0.alloc(n * 8));
   SA_HIP(k1.alloc(n * 8));
   SA_HIP(v0.alloc(n * sizeof(VT)));
@@ -317,7 +310,7 @@ static int build_sa_bucketed(uint64_t n, const uint8_t* d_seq, uint8_t* d_sa, in
   typedef uint64_t VT;
   SA_HIP(hipSetDevice(device));
   hipStream_t st = 0;
-  DevBuf flag, cnt, hist;
+  K4DevBuf flag, cnt, hist;
   const uint64_t PIECE = 1ull << 30;  // no rocPRIM call over the whole block: pieces of 2^30 positions
   SA_HIP(flag.alloc(PIECE));
   SA_HIP(cnt.alloc(8));
@@ -328,7 +321,7 @@ static int build_sa_bucketed(uint64_t n, const uint8_t* d_seq, uint8_t* d_sa, in
   SA_HIP(hipMemcpy(m_of, hist.p, 6 * 8, hipMemcpyDeviceToHost));
   size_t selb = 0;
   SA_HIP(rocprim::select(nullptr, selb, rocprim::counting_iterator<VT>(0), flag.as<uint8_t>(), (VT*)nullptr, cnt.as<uint64_t>(), (size_t)PIECE, st));
-  DevBuf selt;
+  K4DevBuf selt;
   SA_HIP(selt.alloc(selb));
   uint64_t done = 0;
   for (uint32_t sym = 0; sym < 6; sym++) {
@@ -338,7 +331,7 @@ static int build_sa_bucketed(uint64_t n, const uint8_t* d_seq, uint8_t* d_sa, in
       if (err) *err = "a leading-symbol bucket holds 2^32 or more suffixes";
       return K4_ERR_UNSUPPORTED;
     }
-    DevBuf k0, k1, v0, v1, tmp;
+    K4DevBuf k0, k1, v0, v1, tmp;
     SA_HIP(k0.alloc(m * 8)); SA_HIP(k1.alloc(m * 8));
     SA_HIP(v0.alloc(m * 8)); SA_HIP(v1.alloc(m * 8));
     uint64_t got = 0;

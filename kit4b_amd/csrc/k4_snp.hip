@@ -455,7 +455,7 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
     K4_HIP(ix, hipMemsetAsync(flags.p, 0, chrom_hit.size(), st));
     hipLaunchKernelGGL(k4k_snp_mark, dim3((unsigned)std::min<int64_t>((a.n_reads + 255) / 256, 2048)), dim3(256), 0, st, a, flags.as<uint8_t>(), ix->d.n_entries);
     K4_HIP(ix, hipMemcpyAsync(chrom_hit.data(), flags.p, chrom_hit.size(), hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipMemcpyAsync(ent_start_h.data(), ix->ent_start, ent_start_h.size() * 8, hipMemcpyDeviceToHost, st));
+    K4_HIP(ix, hipMemcpyAsync(ent_start_h.data(), ix->ent_start.p, ent_start_h.size() * 8, hipMemcpyDeviceToHost, st));
     K4_HIP(ix, hipStreamSynchronize(st));
   }
   for (uint32_t chrom = 1; chrom <= ix->d.n_entries && a.n_reads > 0; chrom++) {  // the sorted reads: one chromosome after the other

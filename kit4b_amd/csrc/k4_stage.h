@@ -1,7 +1,7 @@
 // kit4b_amd/csrc/k4_stage.h -- what a device stage needs on the host side: its scratch buffers, the rocPRIM calls with their
 // temporary, the list of the reads a predicate accepts, a counter brought down.  A new stage starts from here.
 //
-// The helpers are templates over the buffer type B: K4DevBuf below, or the pool-backed Buf of k4_io.hip (k4_pool.h says why the
+// The helpers are templates over the buffer type B: K4DevBuf (k4_pool.h), or the pool-backed Buf of k4_io.hip (k4_pool.h says why the
 // ingest / emit stages free nothing).  B needs `p`, `hipError_t alloc(size_t)` (which lets go of what it held) and `as<T>()`;
 // a helper's temporary is a B as well, so a stage never mixes the two kinds.  All of them return a K4_* code.
 #pragma once
@@ -18,20 +18,6 @@
     int _try = (call);               \
     if (_try != K4_OK) return _try;  \
   } while (0)
-
-// RAII device block of one stage call: hipMalloc (the pool's cache is given back first when memory is short), hipFree
-struct K4DevBuf {
-  void* p = nullptr;
-  K4DevBuf() = default;
-  K4DevBuf(const K4DevBuf&) = delete;
-  K4DevBuf& operator=(const K4DevBuf&) = delete;
-  ~K4DevBuf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t bytes) {
-    if (p) { (void)hipFree(p); p = nullptr; }
-    return k4_malloc_retry(&p, bytes ? bytes : 1);
-  }
-  template <typename T> T* as() { return (T*)p; }
-};
 
 // one trivially copyable value (a counter, a small array of them) from the device, waited for
 template <typename T>

@@ -251,23 +251,22 @@ extern "C" int k4_align_stats_collect(k4_index* ix, int on) {
   if (!ix) return K4_ERR_PARAMS;
   K4_HIP(ix, hipSetDevice(ix->device));
   if (!on) {
-    if (ix->d_run_stats) hipFree(ix->d_run_stats);
-    ix->d_run_stats = nullptr;
+    ix->d_run_stats.release();
     return K4_OK;
   }
-  if (!ix->d_run_stats) K4_HIP(ix, k4_malloc_retry((void**)&ix->d_run_stats, K4_RUN_STATS_WORDS * 8));
-  K4_HIP(ix, hipMemset(ix->d_run_stats, 0, K4_RUN_STATS_WORDS * 8));
+  K4_HIP(ix, ix->d_run_stats.reserve(K4_RUN_STATS_WORDS * 8));
+  K4_HIP(ix, hipMemset(ix->d_run_stats.p, 0, K4_RUN_STATS_WORDS * 8));
   return K4_OK;
 }
 
 // k4_align.hip calls this behind the classification of a batch (k4_kalign_*_batch_dev; the SE pass of a PE batch as well)
 int k4i_stats_tally_multi(k4_index* ix, const void* d_rr, int64_t n, void* stream) {
-  if (!ix->d_run_stats || n <= 0) return K4_OK;
+  if (!ix->d_run_stats.p || n <= 0) return K4_OK;
   hipLaunchKernelGGL(k4k_multi_tally, dim3(grid_for(256 * 16, n)), dim3(256), 0, (hipStream_t)stream, n, (const k4_read_result*)d_rr,
-                     ix->d_run_stats);
+                     ix->d_run_stats.as<unsigned long long>());
   return k4_check_hip(ix, hipGetLastError(), "k4k_multi_tally");
 }
-unsigned long long* k4i_stats_pe_len_dist(k4_index* ix) { return ix->d_run_stats ? ix->d_run_stats + K4_STATS_MULTI : nullptr; }
+unsigned long long* k4i_stats_pe_len_dist(k4_index* ix) { return ix->d_run_stats.p ? ix->d_run_stats.as<unsigned long long>() + K4_STATS_MULTI : nullptr; }
 
 extern "C" int k4_align_stats_dev(k4_index* ix, int pe, int64_t n_reads, int32_t max_ml, int32_t max_read_len, const void* d_rr,
                                   const void* d_hits, const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens,
@@ -300,9 +299,9 @@ extern "C" int k4_align_stats_dev(k4_index* ix, int pe, int64_t n_reads, int32_t
   out->ent_trimer = out->ent_indeterminate + ne;
   auto fail = [&](int rc) { free(blk); memset(out, 0, sizeof(*out)); return rc; };
   int rc;
-  if (ix->d_run_stats) {
+  if (ix->d_run_stats.p) {
     if ((rc = k4_check_hip(ix, hipStreamSynchronize(st), "stream")) != K4_OK) return fail(rc);
-    if ((rc = k4_check_hip(ix, hipMemcpy(out->multi_hit, ix->d_run_stats, K4_RUN_STATS_WORDS * 8, hipMemcpyDeviceToHost), "run tallies")) != K4_OK)
+    if ((rc = k4_check_hip(ix, hipMemcpy(out->multi_hit, ix->d_run_stats.p, K4_RUN_STATS_WORDS * 8, hipMemcpyDeviceToHost), "run tallies")) != K4_OK)
       return fail(rc);
   }
   if (n_reads == 0) return K4_OK;

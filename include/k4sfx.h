@@ -360,6 +360,31 @@ int k4_align_stats_dev(k4_index* ix, int pe, int64_t n_reads, int32_t max_ml, in
 void k4_free_align_stats(k4_align_stats* s);
 int k4_write_align_stats(k4_index* ix, const k4_align_stats* s, uint64_t n_loaded, int32_t ml_mode, int32_t max_multi, int pe,
                          const char* path);
+/* ---- start-site octamer preferences (`kalign -8 <file>`, `-9 <ofs>`; kit4b_amd/csrc/k4_siteprefs.hip) ---------------------------
+ * k4_site_prefs_dev      <- the walk of CKAligner::ProcessSiteProbabilites (KAligner.cpp:8750-8821) over the records in HBM as the last
+ *                           global stage left them: n_reads reads (PE: both ends, d_pe; SE: d_rr and hit slot 0 of d_hits).  In
+ *                           SortHitMatch order (the order of the SAM body) every accepted one-segment read gives the octamer of the
+ *                           target at `ofs` (-100..100, kalign's default -4; else K4_ERR_PARAMS) from its 5' end, located from the raw
+ *                           MatchLoci / MatchLen in the reference's 32-bit unsigned arithmetic (a locus in front of the sequence wraps and
+ *                           is clamped to the sequence's end, :8778-8782), reverse complemented for a Crick alignment; an octamer that
+ *                           holds an N is not counted.  num_occs counts the reads, num_sites the changes of locus along the walk.  A
+ *                           read whose signed locus lies in -8..-1 (the reference reads an uninitialised array) is not counted.
+ *                           Changes none of the records; waits for `stream`.  Release with k4_free_site_prefs.
+ * k4_write_site_prefs    <- the scale step (:8823-8872) and CKAligner::WriteSitePrefs (:8910-8945): per strand NumOccs / NumSites,
+ *                           the 64 largest set to 1.000 (a stable sort: ties go to the higher octamers) and every other ratio divided
+ *                           by their mean, floor 0.0001; 65535 rows per strand (the reference leaves out tttttttt).  The file is left
+ *                           empty when no read was accepted (:743, :780).  Host only; an error's text is in k4_global_error. */
+typedef struct {
+  uint32_t* num_occs[2];   /* [65536] m_OctSitePrefs[strand][octamer].NumOccs: 0 Watson, 1 Crick; first base most significant */
+  uint32_t* num_sites[2];  /* [65536] .NumSites */
+  uint64_t n_accepted;     /* accepted reads (two-segment reads included) */
+  uint64_t n_counted;      /* reads that were counted */
+  void* block;             /* the one allocation behind the arrays */
+} k4_site_prefs;
+int k4_site_prefs_dev(k4_index* ix, int pe, int64_t n_reads, int32_t max_ml, int32_t ofs, const void* d_rr, const void* d_hits,
+                      const void* d_pe, k4_site_prefs* out, void* stream);
+void k4_free_site_prefs(k4_site_prefs* s);
+int k4_write_site_prefs(const k4_site_prefs* s, const char* path);
 /* k4_best_matches_batch <- CSfxArray::LocateBestMatches (SfxArray.h:793, SfxArray.cpp:6836-7205; CKAligner's `-N`) for
  * n_reads reads: at most p->max_hits alignments with no more than p->tot_mm mismatches, sorted by mismatches; rslt = the
  * call's return value (0 none, 1..max_hits, max_hits+1 when further matches were sloughed), inst = alignments in the
@@ -595,6 +620,8 @@ int k4_pipeline_submit_host(k4_pipeline* pl, int end, const void* text, uint64_t
 int k4_pipeline_wait_aligned(k4_pipeline* pl, k4_pipeline_view* view); /* after the final chunks: every read is aligned */
 /* k4_align_stats_dev over the pipeline's own arrays; call it behind the last global stage and before k4_pipeline_format* */
 int k4_pipeline_align_stats(k4_pipeline* pl, k4_align_stats* out);
+/* k4_site_prefs_dev over the pipeline's own arrays; likewise behind the last global stage and before k4_pipeline_format* */
+int k4_pipeline_site_prefs(k4_pipeline* pl, int32_t ofs, k4_site_prefs* out);
 int k4_pipeline_format(k4_pipeline* pl, k4_sam_stats* stats, uint8_t* chrom_hit /* host, n_entries + 1, or NULL */, uint64_t* sam_bytes);
 /* ... as BAM records (k4_format_bam_dev); the pieces come down through k4_pipeline_next_sam / k4_pipeline_read_sam all the same */
 int k4_pipeline_format_bam(k4_pipeline* pl, int32_t sq_all, k4_sam_stats* stats, uint8_t* chrom_hit, uint64_t* bam_bytes);

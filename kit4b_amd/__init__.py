@@ -126,6 +126,11 @@ class AlignStats(C.Structure):  # k4_align_stats
 STATS_MULTI, STATS_PE_LEN = 500, 100000
 
 
+class SitePrefs(C.Structure):  # k4_site_prefs
+    _fields_ = [("num_occs", C.POINTER(C.c_uint32) * 2), ("num_sites", C.POINTER(C.c_uint32) * 2), ("n_accepted", C.c_uint64),
+                ("n_counted", C.c_uint64), ("block", C.c_void_p)]
+
+
 class Counters(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_lookup", C.c_uint64), ("n_probe", C.c_uint64), ("n_cand", C.c_uint64),
                 ("n_slow", C.c_uint64), ("n_bases", C.c_uint64)]
@@ -149,7 +154,7 @@ ABI_SYMBOLS = [
     "k4_pipeline_format", "k4_pipeline_next_sam", "k4_pipeline_read_sam", "k4_pipeline_close", "k4_sfx_map", "k4_sfx_unmap",
     "k4_set_raw_header", "k4_align_stats_collect", "k4_align_stats_dev", "k4_free_align_stats", "k4_write_align_stats",
     "k4_pipeline_align_stats", "k4_filter_loci_constraints_dev", "k4_filter_chroms_dev", "k4_load_loci_constraints", "k4_chrom_accept_mask",
-    "k4_filter_marked_prior",
+    "k4_filter_marked_prior", "k4_site_prefs_dev", "k4_free_site_prefs", "k4_write_site_prefs", "k4_pipeline_site_prefs",
 ]
 
 
@@ -230,6 +235,11 @@ def lib():
     L.k4_free_align_stats.restype = None
     L.k4_write_align_stats.argtypes = [vp, C.POINTER(AlignStats), u64, C.c_int32, C.c_int32, i32, C.c_char_p]
     L.k4_pipeline_align_stats.argtypes = [vp, C.POINTER(AlignStats)]
+    L.k4_site_prefs_dev.argtypes = [vp, i32, i64, C.c_int32, C.c_int32, vp, vp, vp, C.POINTER(SitePrefs), vp]
+    L.k4_free_site_prefs.argtypes = [C.POINTER(SitePrefs)]
+    L.k4_free_site_prefs.restype = None
+    L.k4_write_site_prefs.argtypes = [C.POINTER(SitePrefs), C.c_char_p]
+    L.k4_pipeline_site_prefs.argtypes = [vp, C.c_int32, C.POINTER(SitePrefs)]
     L.k4_filter_loci_constraints_dev.argtypes = [vp, C.POINTER(LociConstraint), C.c_int32, i32, i64, C.c_int32, vp, vp, vp, vp, vp, vp, vp,
                                                  C.POINTER(C.c_int64), vp]
     L.k4_filter_chroms_dev.argtypes = [vp, vp, i32, i64, C.c_int32, vp, vp, C.POINTER(C.c_int64), vp]
@@ -802,6 +812,24 @@ class SfxIndex:
                     "ent_trimer": arr(st.ent_trimer, ne * 64, np.uint32).reshape(ne, 64)}
         finally:
             lib().k4_free_align_stats(C.byref(st))
+
+    def site_prefs(self, n, max_ml, ofs=-4, d_rr=None, d_hits=None, d_pe=None, stream=0, write=None):
+        """The counts behind `kalign -8 <file> -9 <ofs>` (ProcessSiteProbabilites, KAligner.cpp:8708-8876) over n reads in device arrays
+        (torch tensors or addresses): SE d_rr + d_hits (n * max_ml slots), or PE d_pe (n = both ends).  Returns num_occs / num_sites as
+        uint32 [2, 65536] (strand, octamer) and n_accepted, n_counted.  write = path: also print the file."""
+        ptr = lambda a: None if a is None else a if isinstance(a, int) else a.data_ptr()  # noqa: E731
+        sp = SitePrefs()
+        pe = d_pe is not None
+        self._ck(lib().k4_site_prefs_dev(self.h, 1 if pe else 0, int(n), int(max_ml), int(ofs), ptr(d_rr), ptr(d_hits), ptr(d_pe), C.byref(sp),
+                                         stream))
+        try:
+            if write is not None and lib().k4_write_site_prefs(C.byref(sp), os.fsencode(write)) != 0:
+                raise K4Error(-89, lib().k4_global_error().decode())
+            arr = lambda ps: np.stack([np.ctypeslib.as_array(p, shape=(65536,)).copy() for p in ps])  # noqa: E731
+            return {"num_occs": arr(sp.num_occs), "num_sites": arr(sp.num_sites), "n_accepted": int(sp.n_accepted),
+                    "n_counted": int(sp.n_counted)}
+        finally:
+            lib().k4_free_site_prefs(C.byref(sp))
 
     def pipeline_sam(self, texts, kp, pe=None, min_len=50, max_len=500, chunk_bytes=0, ring=False, out=None, min_batch_units=0, all_reads=False, expect=True):
         """host text (bytes-like / pinned tensors: one for SE, two for PE) -> SAM body through the overlapped pipeline.

@@ -483,6 +483,14 @@ extern "C" int k4_pipeline_align_stats(k4_pipeline* pl, k4_align_stats* out) {
                             v.d_offs, v.d_lens, out, pl->s_comp);
 }
 
+extern "C" int k4_pipeline_site_prefs(k4_pipeline* pl, int32_t ofs, k4_site_prefs* out) {
+  if (!pl || !out) return K4_ERR_PARAMS;
+  k4_pipeline_view v;
+  int rc = k4_pipeline_wait_aligned(pl, &v);
+  if (rc != K4_OK) return rc;
+  return k4_site_prefs_dev(pl->ix, pl->n_ends == 2 ? 1 : 0, v.n_reads, v.max_ml, ofs, v.d_rr, v.d_hits, v.d_pe, out, pl->s_comp);
+}
+
 static int pipeline_format(k4_pipeline* pl, int bam, int sq_all, k4_sam_stats* stats, uint8_t* chrom_hit, uint64_t* sam_bytes);
 extern "C" int k4_pipeline_format(k4_pipeline* pl, k4_sam_stats* stats, uint8_t* chrom_hit, uint64_t* sam_bytes) {
   return pipeline_format(pl, 0, 0, stats, chrom_hit, sam_bytes);

@@ -15,9 +15,11 @@
 //                        the insert size file of ProcessPairedEnds :3092-3146     -> k4_pipeline_align_stats, k4_write_align_stats
 //   loci constraints (-5) CKAligner::LoadLociConstraints :1363-1545, IdentifyConstraintViolations :2716-2765
 //                                                                                  -> k4_load_loci_constraints, k4_filter_loci_constraints_dev
+//   site preferences (-8, -9) CKAligner::ProcessSiteProbabilites :8708-8876, WriteSitePrefs :8910-8945
+//                                                                                  -> k4_pipeline_site_prefs, k4_write_site_prefs
 //   chromosome filters   CKAligner::FiltByChroms :4025-4091 (kalign -Z / -z; here --chromexclude / --chromeinclude)
 //                                                                                  -> k4_chrom_accept_mask, k4_filter_chroms_dev
-// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k -O -5 (plus -g <gpu>, -S <i/N> read slice);
+// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k -O -5 -8 -9 (plus -g <gpu>, -S <i/N> read slice);
 // kalign's -Z / -z go by their long names --chromexclude / --chromeinclude (the letters mean something else here).
 #include <errno.h>
 #include <fcntl.h>
@@ -62,6 +64,8 @@ struct Opts {
   std::string loci_file;            // -5 / --lociconstraints <file>: loci base constraints CSV (KAlignerCL.cpp:255)
   std::vector<std::string> chrom_excl, chrom_incl;  // --chromexclude / --chromeinclude <regex>, each repeatable (kalign -Z / -z, KAlignerCL.cpp:274-275)
   std::string stats_file;           // -O <file>: alignment statistics (KAlignerCL.cpp:256) and its two side files
+  std::string site_file;            // -8 / --siteprefs <file>: start-site octamer preferences (KAlignerCL.cpp:252)
+  int site_ofs = -4;                // -9 / --siteprefsofs <-100..100>: cDfltRelSiteStartOfs (KAlignerCL.cpp:253,1053)
   double batch_mb = 0;              // -b <MB>: stream the input, this much text per file per batch (0: the whole input at once)
   int shard = 0, n_shards = 1;      // -S i/N: this process aligns the i-th of N contiguous slices of the reads (one process per GPU)
   int gpu = 0;
@@ -541,7 +545,7 @@ const char* kNarAbbr[20] = {"NA", "AA", "EN", "NL", "MH", "ML", "ET", "OJ", "OM"
 void usage() {
   fprintf(stderr,
           "k4align -i reads.f[aq][.gz] [-i more ...] [-u mates ...] -I index.sfx -o out.sam|out.bam [-z bgzf level=6] [-s subs/100bp=5] [-e 1|2] [-m 0..3] [-n maxNs=1]\n"
-          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
+          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
 }
 
 }  // namespace
@@ -892,6 +896,12 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
       if (pe) guard.made.push_back(stats_side_name(o.stats_file, ".GlobalPEInsertDist.csv"));
       CK(k4_align_stats_collect(ix, 1));
     }
+    if (!o.site_file.empty()) {  // created / truncated with the other outputs (KAligner.cpp:4471-4491); it stays empty when no read is accepted
+      FILE* fp = fopen(o.site_file.c_str(), "wb");
+      if (!fp) { fprintf(stderr, "k4align: unable to create/truncate site preferencing file '%s'\n", o.site_file.c_str()); return 5; }
+      fclose(fp);
+      guard.made.push_back(o.site_file);
+    }
     CK(k4_pipeline_open(ix, &pp2, &pl));
     CK(k4_pipeline_set_trims(pl, o.trim5, o.trim3));
     CK(k4_pipeline_set_sampling(pl, o.sample_nth));
@@ -1020,6 +1030,15 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
       k4_free_align_stats(&as);
       if (rc != K4_OK) { fprintf(stderr, "k4align: %s\n", k4_last_error(ix)); return 5; }
       if (chatty) fprintf(stderr, "k4align: alignment statistics written to %s in %.2fs\n", o.stats_file.c_str(), secs(ts, now()));
+    }
+    if (!o.site_file.empty()) {  // ProcessSiteProbabilites runs in front of the writer (KAligner.cpp:743), over the reads it will report
+      auto ts = now();
+      k4_site_prefs sp;
+      CK(k4_pipeline_site_prefs(pl, o.site_ofs, &sp));
+      rc = k4_write_site_prefs(&sp, o.site_file.c_str());
+      k4_free_site_prefs(&sp);
+      if (rc != K4_OK) { fprintf(stderr, "k4align: %s\n", k4_global_error()); return 5; }
+      if (chatty) fprintf(stderr, "k4align: start site octamer preferences written to %s in %.2fs\n", o.site_file.c_str(), secs(ts, now()));
     }
     // (a rank of a -G run numbers every sequence: the parent renumbers when it knows which ones any rank has hit)
     const int bam_all_sq = (info.n_entries <= (uint32_t)o.rpt_sq_thres || o.rank_bam) ? 1 : 0;
@@ -1435,6 +1454,8 @@ int main(int argc, char** argv) {
         if (name == "chromexclude") o.chrom_excl.push_back(v);
         else if (name == "chromeinclude") o.chrom_incl.push_back(v);
         else if (name == "lociconstraints") o.loci_file = v;
+        else if (name == "siteprefs") o.site_file = v;
+        else if (name == "siteprefsofs") o.site_ofs = atoi(v.c_str());
         else { usage(); return 1; }
         break;
       }
@@ -1461,6 +1482,8 @@ int main(int argc, char** argv) {
       case 'x': o.min_flank_exacts = atoi(val().c_str()); break;
       case 'k': o.pcr_win = atoi(val().c_str()); o.pcr_given = true; break;
       case 'O': o.stats_file = val(); break;
+      case '8': o.site_file = val(); break;
+      case '9': o.site_ofs = atoi(val().c_str()); break;
       case 'p': o.min_snp_reads = atoi(val().c_str()); break;
       case 'P': o.qvalue = atof(val().c_str()); break;
       case '1': o.snp_nonref_pcnt = atof(val().c_str()); break;
@@ -1555,6 +1578,15 @@ int main(int argc, char** argv) {
       return 1;
     }
     if (o.ml_mode == 5) { fprintf(stderr, "k4align: alignment statistics '-O' with every multiloci alignment reported '-r5' are not built\n"); return 3; }
+  }
+  // the site preferences are counted along one walk over all reads of the run (merging the counts of batches or ranks in walk order is not built)
+  if (abs(o.site_ofs) > 100) {  // cMaxSitePrefOfs, KAlignerCL.cpp:1054-1058
+    fprintf(stderr, "k4align: offset read start sites '-9%d' when processing site octamer preferencing must be in range -100..100\n", o.site_ofs);
+    return 1;
+  }
+  if (!o.site_file.empty() && (o.ml_mode == 5 || o.batch_mb > 0 || o.n_shards > 1 || !o.gpus.empty() || o.legacy)) {
+    fprintf(stderr, "k4align: start site octamer preferences '-8' with -r5, -b, -S i/N, -G or -Z are not built\n");
+    return 3;
   }
   // the loci constraints and the chromosome filters look at one read (pair) at a time: they run with -b, -S i/N and -G as well
   if (!o.chrom_excl.empty() || !o.chrom_incl.empty()) {

@@ -569,6 +569,29 @@ int k4_snp_run_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d
                    const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads, double qvalue,
                    double snp_nonref_pcnt, k4_snp_files* out, void* stream);
 void k4_free_host(void* p);
+/* k4_pba_run_dev <- `ngskit4b genpba` (kalignerPBA, KAlignerCL.cpp:1540-2290: CKAligner::Process with eFMPBA; ProcessSNPs
+ * KAligner.cpp:8168-8575 and the PBA branch of OutputSNPs :7194-7317): the packed base alleles of a run's accepted alignments and
+ * the coverage WIG genpba writes beside them (<out minus its extension>.covsegs.wig).  pba: the text
+ * "Type:PbA\nVersion:1\nExperimentID:<experiment_id>\nReferenceID:<the index's species>\nReadsetID:<readset_id>" and a NUL, then per
+ * sequence with a piled-up alignment, in sequence order: one byte name length, the name, a NUL, the sequence length (uint32, little
+ * endian) and one byte per locus -- four 2-bit allele scores, A in bits 7..6, C in 5..4, G in 3..2, T in 1..0 (k4_pba_classify_host
+ * has the rule).  No such sequence: pba_bytes == 0, as the reference leaves an empty file.  wig: no track line, the loci counted
+ * from 1, coverage without the indeterminate bases, every sequence's last span closed.  Alignments with an indel or a splice
+ * junction and those reaching over their sequence's end are left out, as in SNP calling.  Both blocks are malloc'd: release with
+ * k4_free_host.  The ids are written as they are (k4align cleans them as the reference's front end does). */
+typedef struct k4_pba_files {
+  uint8_t* pba; uint64_t pba_bytes;
+  char* wig;    uint64_t wig_bytes;
+  uint64_t n_chroms;
+} k4_pba_files;
+int k4_pba_run_dev(k4_index* ix, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml, const void* d_pe,
+                   const void* d_reads, const void* d_offs, const void* d_lens, const char* experiment_id, const char* readset_id,
+                   k4_pba_files* out, void* stream);
+/* genpba's per-locus rule alone, on the host (no device, no index): the same function the kernel runs.  cnt7: seven arrays of
+ * `stride` words (NumRefBases, NumNonRefBases, NonRefBaseCnts[A, C, G, T, N]); ref_bases: the target's symbol per locus (0..3 =
+ * a, c, g, t).  coverage = ref + nonref - N; byte 0 where it is 0; else per allele its count (the reference count for the target's
+ * base) / (double)coverage scored 3 / 2 / 1 from 0.75 / 0.35 / 0.20 on where coverage >= 5, and 2 / 1 from 0.70 / 0.30 on below. */
+int k4_pba_classify_host(const uint32_t* cnt7, uint64_t stride, uint32_t n_loci, const uint8_t* ref_bases, uint8_t* pba, uint32_t* coverage);
 /* k4_select_hits_dev <- MLMode eMLrand (`-r2`, KAligner.cpp:9945-9962) after k4_kalign_batch_dev with pe_mode 2: every accepted
  * read keeps ONE instance, hits[choice[i] % NumHits] moved to slot 0, NumHits = 1.  d_choice: uint32 per read, the caller's
  * draws (the reference: rand() once per read within the limit, in load order when it runs one thread). */

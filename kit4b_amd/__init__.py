@@ -131,6 +131,10 @@ class SitePrefs(C.Structure):  # k4_site_prefs
                 ("n_counted", C.c_uint64), ("block", C.c_void_p)]
 
 
+class PbaFiles(C.Structure):  # k4_pba_files
+    _fields_ = [("pba", C.c_void_p), ("pba_bytes", C.c_uint64), ("wig", C.c_void_p), ("wig_bytes", C.c_uint64), ("n_chroms", C.c_uint64)]
+
+
 class Counters(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_lookup", C.c_uint64), ("n_probe", C.c_uint64), ("n_cand", C.c_uint64),
                 ("n_slow", C.c_uint64), ("n_bases", C.c_uint64)]
@@ -155,6 +159,7 @@ ABI_SYMBOLS = [
     "k4_set_raw_header", "k4_align_stats_collect", "k4_align_stats_dev", "k4_free_align_stats", "k4_write_align_stats",
     "k4_pipeline_align_stats", "k4_filter_loci_constraints_dev", "k4_filter_chroms_dev", "k4_load_loci_constraints", "k4_chrom_accept_mask",
     "k4_filter_marked_prior", "k4_site_prefs_dev", "k4_free_site_prefs", "k4_write_site_prefs", "k4_pipeline_site_prefs",
+    "k4_pba_run_dev", "k4_pba_classify_host",
 ]
 
 
@@ -288,6 +293,8 @@ def lib():
     L.k4_snp_run_dev.argtypes = [vp, i32] + snp_head[1:] + [vp, vp]
     L.k4_free_host.argtypes = [vp]
     L.k4_free_host.restype = None
+    L.k4_pba_run_dev.argtypes = [vp, i32, i64, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_char_p, C.c_char_p, C.POINTER(PbaFiles), vp]
+    L.k4_pba_classify_host.argtypes = [vp, u64, u32, vp, vp, vp]
     L.k4_sfx_map.argtypes = [C.c_char_p, vp]
     L.k4_sfx_unmap.argtypes = [vp]
     L.k4_sfx_unmap.restype = None
@@ -698,6 +705,33 @@ class SfxIndex:
             L.k4_free_host(getattr(f, k))
         return res
 
+    def pba(self, reads, out=None, hits=None, pe_recs=None, experiment_id="Unspecified", readset_id="Unspecified"):
+        """`ngskit4b genpba` over host-side results (k4_pba_run_dev): SE (out + hits records) or PE (pe_recs, reads interleaved).
+        Returns {"pba": the .pba file's bytes, "wig": the .covsegs.wig text, "n_chroms": the number of sequence records}."""
+        import torch
+
+        dev = torch.device("cuda", self.info()["device"])
+        cat, offs, lens = _flatten(reads)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
+        d_reads = torch.from_numpy(np.concatenate([cat, np.zeros(16, np.uint8)])).to(dev)
+        d_offs, d_lens = t(offs), t(lens)
+        L = lib()
+        f = PbaFiles()
+        ids = (os.fsencode(experiment_id), os.fsencode(readset_id))
+        if pe_recs is not None:
+            d_pe = t(pe_recs)
+            self._ck(L.k4_pba_run_dev(self.h, 1, len(lens) // 2, None, None, 1, d_pe.data_ptr(), d_reads.data_ptr(), d_offs.data_ptr(),
+                                      d_lens.data_ptr(), *ids, C.byref(f), 0))
+        else:
+            d_rr, d_hits = t(out), t(hits)
+            max_ml = 1 if hits.ndim == 1 else hits.shape[1]
+            self._ck(L.k4_pba_run_dev(self.h, 0, len(lens), d_rr.data_ptr(), d_hits.data_ptr(), max_ml, None, d_reads.data_ptr(),
+                                      d_offs.data_ptr(), d_lens.data_ptr(), *ids, C.byref(f), 0))
+        res = {"pba": C.string_at(f.pba, f.pba_bytes), "wig": C.string_at(f.wig, f.wig_bytes).decode(), "n_chroms": f.n_chroms}
+        L.k4_free_host(f.pba)
+        L.k4_free_host(f.wig)
+        return res
+
     def post_stages(self, reads, out, hits, seg2, min_flank_exacts=0, orphan_splice=False, orphan_indel=False):
         """AutoTrimFlanks / RemoveOrphanSpliceJuncts / RemoveOrphanMicroInDels (KAligner.cpp:653-686) over host arrays of SE
         results, in the reference's order; returns (out, hits, counts)."""
@@ -940,6 +974,22 @@ class SfxIndex:
                               d_hits, stream=0):
         self._ck(lib().k4_align_reads_batch_dev(self.h, C.byref(params), n, max_read_len, d_reads, d_offs, d_lens,
                                                 d_rslt, d_inst, d_low, d_nxt, d_hits, stream))
+
+
+def pba_classify_host(cnt7, ref_bases):
+    """genpba's per-locus rule on the host (k4_pba_classify_host; needs the library, no GPU).  cnt7: uint32 array [7, n_loci] -- the
+    reference count, the non-reference count and the non-reference counts of A, C, G, T, N; ref_bases: the target's symbol per locus.
+    Returns (PBA bytes, coverage) as uint8 / uint32 arrays."""
+    cnt7 = np.ascontiguousarray(cnt7, dtype=np.uint32)
+    ref_bases = np.ascontiguousarray(ref_bases, dtype=np.uint8)
+    if cnt7.ndim != 2 or cnt7.shape[0] != 7 or ref_bases.shape != (cnt7.shape[1],):
+        raise ValueError("cnt7 is [7, n_loci], ref_bases [n_loci]")
+    n = cnt7.shape[1]
+    pba, cov = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+    rc = lib().k4_pba_classify_host(cnt7.ctypes.data, n, n, ref_bases.ctypes.data, pba.ctypes.data, cov.ctypes.data)
+    if rc != 0:
+        raise K4Error(rc, "k4_pba_classify_host")
+    return pba, cov
 
 
 def build_sa_device(concat_len, el_size, d_seq_ptr, d_sa_ptr, device=0):

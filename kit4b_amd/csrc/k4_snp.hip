@@ -11,7 +11,8 @@
 // chromosome -- with the reference's own floating-point operations in its order (long double n-choose-k included).
 // The files kalign writes beside it: the coverage WIG (host threads, one per chromosome) and the DiSNP / TriSNP haplotype files
 // (:7767-8101; one thread per alignment finds the called loci it covers and counts its base combination for every run of two /
-// three of them).  Not built: marker sequences, centroids, the BED form, packed base alleles.  Equal p-values keep locus order in the ranking (the reference's multi-threaded quicksort
+// three of them).  The pile-up, the pass that marks the sequences with alignments and the WIG walk live in k4_pileup.h: genpba's packed
+// base alleles (k4_pba.hip) start from the same counts.  Not built: marker sequences, centroids, the BED form.  Equal p-values keep locus order in the ranking (the reference's multi-threaded quicksort
 // leaves them in no defined order).
 #include <math.h>
 #include <stdint.h>
@@ -25,79 +26,10 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 #include "k4_device.h"
+#include "k4_pileup.h"
 #include "k4_stage.h"
 
 namespace {
-
-struct SnpArgs {
-  K4DevIndex ix;
-  int pe;
-  int64_t n_reads;
-  const k4_read_result* rr;
-  const k4_hit* hits;
-  int max_ml;
-  const k4_pe_read* pr;
-  const uint8_t* reads;
-  const uint64_t* offs;
-  const uint32_t* lens;
-  uint32_t chrom_id;
-  uint64_t cs;       // concat offset of the chromosome
-  uint32_t clen;
-  uint32_t* cnt;     // seven arrays of clen + 16: ref, nonref, A, C, G, T, N
-  unsigned long long* tot;  // [0] TotMatch [1] TotMismatch [2] reads piled up [3] their aligned bases
-};
-#define K4_SNP_STRIDE(a) ((size_t)(a).clen + 16)
-
-// ProcessSNPs' inner loop (:8468-8557, base space), one wave per accepted alignment on this chromosome
-__global__ void __launch_bounds__(256) k4k_snp_pileup(SnpArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * 256) >> 6;
-  unsigned long long m = 0, mm = 0, nr = 0, nb = 0;
-  for (int64_t i = wave0; i < a.n_reads; i += n_waves) {
-    const int nar = a.pe ? a.pr[i].nar : a.rr[i].nar;
-    if (nar != K4_NAR_ACCEPTED) continue;
-    const k4_hit h = a.pe ? a.pr[i].hit : a.hits[i * a.max_ml];
-    if (h.chrom_id != a.chrom_id || (h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE))) continue;
-    const uint32_t tl = K4_HIT_TRIM_LEFT(h);
-    uint32_t match_len = k4d_adj_len(h);
-    const uint32_t loci0 = k4d_adj_start(h);
-    if ((uint64_t)loci0 + match_len > a.clen) continue;                  // (GetSeq comes back short: the read is skipped, :8420)
-    const uint8_t* src = a.reads + a.offs[i] + tl;
-    if (lane == 0) { nr++; nb += match_len; }
-    for (uint32_t q = lane; q < match_len; q += 64) {
-      const uint32_t ref = k4d_ref_base(a.ix, a.cs + loci0 + q);
-      uint32_t r = h.strand == '+' ? (src[q] & 7u) : (src[match_len - 1 - q] & 7u);
-      if (h.strand != '+' && r <= 3) r = 3 - r;
-      if (ref >= 4 || r > 4) continue;
-      uint32_t* c = a.cnt + loci0 + q;
-      if (ref == r) { atomicAdd(c, 1u); m++; }
-      else {
-        atomicAdd(c + K4_SNP_STRIDE(a), 1u);
-        atomicAdd(c + (2 + r) * K4_SNP_STRIDE(a), 1u);
-        mm++;
-      }
-    }
-  }
-  for (int d = 32; d > 0; d >>= 1) { m += __shfl_down(m, d, 64); mm += __shfl_down(mm, d, 64); }
-  if (lane == 0) {
-    if (m) atomicAdd(&a.tot[0], m);
-    if (mm) atomicAdd(&a.tot[1], mm);
-    if (nr) { atomicAdd(&a.tot[2], nr); atomicAdd(&a.tot[3], nb); }
-  }
-}
-
-// which sequences hold an alignment the pile-up would take at all: one pass over the reads before the per-sequence work, so that
-// an assembly of 10^5 contigs costs its hit contigs, not its contigs (the reference walks its sorted reads once)
-__global__ void __launch_bounds__(256) k4k_snp_mark(SnpArgs a, uint8_t* __restrict__ flags, uint32_t n_entries) {
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n_reads; i += stride) {
-    const int nar = a.pe ? a.pr[i].nar : a.rr[i].nar;
-    if (nar != K4_NAR_ACCEPTED) continue;
-    const k4_hit h = a.pe ? a.pr[i].hit : a.hits[i * a.max_ml];
-    if ((h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE)) || h.chrom_id < 1 || h.chrom_id > n_entries) continue;
-    flags[h.chrom_id] = 1;
-  }
-}
 
 struct Cand { uint32_t loci, n_ref, n_nonref, by_base[5], loc_mm, loc_m, ref_base, pad; };  // 48 bytes
 
@@ -243,77 +175,6 @@ static std::string hap_header(int n) {  // :8252-8330
     s += "\"";
   }
   return s + "\n";
-}
-
-// The coverage WIG kalign writes beside the SNP file: variableStep spans of roughly equal coverage (AccumWIGCnts / CompleteWIGSpan,
-// KAligner.cpp:6993-7085), fed with the locus counted from 0 (:7375) -- so a span that starts at locus 0 is never written.  The
-// walk is sequential by nature (where a span ends depends on its running mean): one host thread per chromosome, running while the
-// device piles up the next chromosomes.  Returns the text of the chromosome's closed spans; `tail` = what closing the last open
-// span adds (the reference does that only for chromosomes with at least one candidate locus, :7582-7608 / :8135).
-struct WigOut { std::string body, tail; };
-// The running mean cnts / len is kept as quotient and remainder (a span grows by one locus at a time), so the walk has no division:
-// 100 * (cnts / len) against 100 c, 75 c and 125 c is q against c, 4 q against 3 c and 5 c.
-template <typename T>
-static WigOut wig_walk(const T* cov, uint32_t clen, const std::string& name) {
-  WigOut o;
-  uint32_t loci = 0, len = 0, rptd_len = 0;
-  bool started = false, rptd = false;  // m_WIGChromID != 0, m_WIGRptdChromID == this chromosome
-  uint64_t cnts = 0, q = 0;            // q = cnts / len
-  int64_t r = 0;                       // cnts - q * len
-  // (a genome at low coverage makes a span of nearly every run of equal coverage -- hundreds of millions of lines: own digits, no printf)
-  const std::string head = "variableStep chrom=" + name + " span=";
-  char line[64];
-  auto put = [](char* p, uint32_t v) {
-    char t[10];
-    int n = 0;
-    do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-    while (n) *p++ = t[--n];
-    return p;
-  };
-  auto complete = [&](std::string& dst) {
-    if (started && len > 0 && loci > 0 && cnts > 0) {
-      if (!rptd || len != rptd_len) {
-        dst += head;
-        char* p = put(line, len);
-        *p++ = '\n';
-        dst.append(line, (size_t)(p - line));
-        rptd = true; rptd_len = len;
-      }
-      char* p = put(line, loci);
-      *p++ = ' ';
-      p = put(p, (uint32_t)(q + (r > 0 ? 1 : 0)));  // (cnts + len - 1) / len
-      *p++ = '\n';
-      dst.append(line, (size_t)(p - line));
-    }
-    loci = 0; len = 0; cnts = 0;
-  };
-  for (uint32_t l = 0; l < clen; l++) {
-    const uint64_t c = cov[l];
-    if (!started || len >= 100000u || c == 0) {
-      if (started) complete(o.body);
-      if (c > 0) { started = true; loci = l; len = 1; cnts = c; q = c; r = 0; }
-      continue;
-    }
-    if (len == 0 || cnts == 0) { loci = l; len = 1; cnts = c; q = c; r = 0; continue; }
-    if ((c <= 5 && c != q) || 4 * q < 3 * c || 4 * q >= 5 * c) {
-      complete(o.body);
-      loci = l; len = 1; cnts = c; q = c; r = 0;
-      continue;
-    }
-    cnts += c;
-    len = l - loci + 1;  // (= len + 1: the loci of a span follow each other)
-    r += (int64_t)c - (int64_t)q;
-    while (r >= (int64_t)len) { q++; r -= len; }
-    while (r < 0) { q--; r += len; }
-  }
-  complete(o.tail);
-  return o;
-}
-// `width` bytes per locus (k4k_snp_coverage)
-static WigOut wig_chromosome(std::unique_ptr<uint8_t[]> cov, int width, uint32_t clen, std::string name) {
-  if (width == 1) return wig_walk<uint8_t>(cov.get(), clen, name);
-  if (width == 2) return wig_walk<uint16_t>((const uint16_t*)cov.get(), clen, name);
-  return wig_walk<uint32_t>((const uint32_t*)cov.get(), clen, name);
 }
 
 // ---- CStats (libkit4b/Stats.cpp:489-564), operation for operation ------------------------------------------------------------
@@ -488,7 +349,7 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
       K4_HIP(ix, hipStreamSynchronize(st));
       if (wig_jobs.size() >= 12) wig_jobs[wig_jobs.size() - 12].f.wait();
       wig_slot = wig_jobs.size();
-      wig_jobs.push_back({std::async(std::launch::async, wig_chromosome, std::move(cov), width, a.clen, std::string(e.name)), false});
+      wig_jobs.push_back({std::async(std::launch::async, wig_chromosome, std::move(cov), width, a.clen, std::string(e.name), 0u), false});
     }
     // prefix sums over [0, clen]: element l = sum of the loci below l (the arrays are zero behind clen)
     K4_TRY(k4s_exclusive_scan(ix, a.cnt, pref.as<uint64_t>(), (uint64_t)0, (size_t)a.clen + 1, rocprim::plus<uint64_t>(), st, &tmp));

@@ -79,7 +79,10 @@ struct Opts {
   int sample_nth = 1;               // -# <n>: every n-th read / pair of the input is processed (KAlignerCL.cpp:244,484-489)
   int trim5 = 0, trim3 = 0;         // -y / -Y <n>: bases taken off the 5' / 3' end of every read when loading (KAlignerCL.cpp:763-774)
   int align_strand = 0;             // -Q <0|1|2>: align to either strand, the sense or the antisense strand only (KAlignerCL.cpp:241,491)
-  int fmode = 0;                    // -M <0|1>: 0 SAM / BAM with the accepted alignments, 1 SAM with every loaded read (KAlignerCL.cpp:217)
+  int fmode = 0;                    // -M <0|1|3>: 0 SAM / BAM with the accepted alignments, 1 SAM with every loaded read (KAlignerCL.cpp:217),
+                                    // 3 no SAM: -o is genpba's packed base alleles file (kalignerPBA, KAlignerCL.cpp:1540-2290)
+  std::string experiment_id, readset_id;  // --experimentid / --readsetid <str>: genpba's -w / -W (KAlignerCL.cpp:1617-1618), required with -M3
+  std::string given;                // the option letters of the command line (genpba's argument table is narrower than kalign's)
   bool legacy = false;              // -Z: the serial whole-input path of round 1 (one batch, no overlap), kept for comparison
   int chunk_mb = 256;               // -B <MB>: size of one pinned upload buffer of the pipeline
   int io_threads = 8;               // -t <n>: concurrent pread / pwrite calls per buffer; BAM: deflate threads
@@ -542,10 +545,25 @@ int feed_dealt(k4_pipeline* pl, int end, const std::vector<std::string>& files, 
 
 const char* kNarAbbr[20] = {"NA", "AA", "EN", "NL", "MH", "ML", "ET", "OJ", "OM", "DP", "DS", "FC", "PR", "UI", "OI", "UP", "IS", "IT", "NP", "LC"};
 
+// the front end's cleaning of an identifier (KAlignerCL.cpp:1697-1729): at most 81 characters, every quote dropped
+// (CUtility::TrimQuotes), white space trimmed off both ends and every run of it inside made one space (ReduceWhitespace)
+std::string clean_id(const std::string& raw) {
+  std::string t;
+  for (const char c : raw.substr(0, 81))
+    if (c != '"' && c != '\'') t += c;
+  std::string out;
+  for (const char c : t) {
+    if (!isspace((unsigned char)c)) out += c;
+    else if (!out.empty() && out.back() != ' ') out += ' ';
+  }
+  if (!out.empty() && out.back() == ' ') out.pop_back();
+  return out;
+}
+
 void usage() {
   fprintf(stderr,
           "k4align -i reads.f[aq][.gz] [-i more ...] [-u mates ...] -I index.sfx -o out.sam|out.bam [-z bgzf level=6] [-s subs/100bp=5] [-e 1|2] [-m 0..3] [-n maxNs=1]\n"
-          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
+          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads | -M3 --experimentid id --readsetid id: packed base alleles to -o, no SAM] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
 }
 
 }  // namespace
@@ -966,6 +984,33 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
       k4_free_host(txt);
       if (!ok) { fprintf(stderr, "k4align: unable to write %s\n", fn.c_str()); return 5; }
       if (chatty) fprintf(stderr, "k4align: %llu %s reads written to %s\n", (unsigned long long)nl, which ? "multi-aligned" : "unalignable", fn.c_str());
+    }
+    if (o.fmode == 3) {  // genpba: ProcessSNPs in PBA mode is the report (KAligner.cpp:741-790); no SAM is written
+      auto ts = now();
+      k4_pba_files pf;
+      CK(k4_pba_run_dev(ix, pe ? 1 : 0, v.n_units, v.d_rr, v.d_hits, v.max_ml, v.d_pe, v.d_reads, v.d_offs, v.d_lens, o.experiment_id.c_str(),
+                        o.readset_id.c_str(), &pf, nullptr));
+      // the WIG's name: <-o cut at its last '.'> + .covsegs.wig (CUtility::AppendFileNameSuffix, KAligner.cpp:4341)
+      const struct { std::string name; const void* p; uint64_t n; } files[2] = {{o.out, pf.pba, pf.pba_bytes},
+                                                                                {stats_side_name(o.out, ".covsegs.wig"), pf.wig, pf.wig_bytes}};
+      std::string failed;
+      for (const auto& f : files) {
+        FILE* fp = fopen(f.name.c_str(), "wb");
+        bool ok = fp != nullptr;
+        if (ok) guard.made.push_back(f.name);
+        if (ok) ok = fwrite(f.p, 1, f.n, fp) == f.n;
+        if (fp && fclose(fp) != 0) ok = false;
+        if (!ok && failed.empty()) failed = f.name;
+      }
+      k4_free_host(pf.pba); k4_free_host(pf.wig);
+      if (!failed.empty()) { fprintf(stderr, "k4align: unable to write %s\n", failed.c_str()); return 5; }
+      if (chatty) fprintf(stderr, "k4align: packed base alleles of %llu sequences (%llu bytes) written to %s, coverage to %s in %.2fs\n",
+                          (unsigned long long)pf.n_chroms, (unsigned long long)pf.pba_bytes, o.out.c_str(), files[1].name.c_str(), secs(ts, now()));
+      k4_pipeline_close(pl);
+      pl = nullptr;
+      guard.ok = true;
+      k4_close(ix);
+      return 0;
     }
     if (o.min_snp_reads > 0) {  // ProcessSNPs (KAligner.cpp:768-790 calls it behind the alignment report): the SNP file and its side files
       auto ts = now();
@@ -1444,6 +1489,7 @@ int main(int argc, char** argv) {
     std::string a = argv[i];
     if (a.size() < 2 || a[0] != '-') { usage(); return 1; }
     auto val = [&]() -> std::string { return a.size() > 2 ? a.substr(2) : (i + 1 < argc ? std::string(argv[++i]) : std::string()); };
+    if (a[1] != '-') o.given += a[1];
     switch (a[1]) {
       case '-': {  // kalign's long names, for the options whose letters are taken here: --name value | --name=value
         std::string name = a.substr(2), v;
@@ -1453,9 +1499,11 @@ int main(int argc, char** argv) {
         else { usage(); return 1; }
         if (name == "chromexclude") o.chrom_excl.push_back(v);
         else if (name == "chromeinclude") o.chrom_incl.push_back(v);
-        else if (name == "lociconstraints") o.loci_file = v;
-        else if (name == "siteprefs") o.site_file = v;
-        else if (name == "siteprefsofs") o.site_ofs = atoi(v.c_str());
+        else if (name == "lociconstraints") { o.loci_file = v; o.given += '5'; }
+        else if (name == "siteprefs") { o.site_file = v; o.given += '8'; }
+        else if (name == "siteprefsofs") { o.site_ofs = atoi(v.c_str()); o.given += '9'; }
+        else if (name == "experimentid") { o.experiment_id = clean_id(v); o.given += 'w'; }
+        else if (name == "readsetid") { o.readset_id = clean_id(v); o.given += 'W'; }
         else { usage(); return 1; }
         break;
       }
@@ -1541,6 +1589,27 @@ int main(int argc, char** argv) {
   }
   if (o.in1.empty() || o.sfx.empty() || o.out.empty()) { usage(); return 1; }
   const bool pe = !o.in2.empty();
+  // -M3: `ngskit4b genpba` (kalignerPBA, KAlignerCL.cpp:1540-2290).  Its argument table (:1556-1628) is kalign's without the
+  // second-segment phases, the side files and SNP calling; -w / -W are required there (arg_str1, cleaned :1697-1729)
+  if (o.fmode == 3) {
+    for (const char c : std::string("aAOjJ895pP1N"))
+      if (o.given.find(c) != std::string::npos) { fprintf(stderr, "k4align: genpba '-M3' has no option '-%c'\n", c); return 1; }
+    if (!o.snp_file.empty()) { fprintf(stderr, "k4align: genpba '-M3' calls no SNPs: no SNP file '-S%s'\n", o.snp_file.c_str()); return 1; }
+    if (o.given.find('w') == std::string::npos || o.given.find('W') == std::string::npos) {
+      fprintf(stderr, "k4align: packed base alleles '-M3' need --experimentid <id> and --readsetid <id>\n");
+      return 1;
+    }
+    if (o.experiment_id.empty()) { fprintf(stderr, "k4align: No experiment identifier specified\n"); return 1; }
+    if (o.readset_id.empty()) { fprintf(stderr, "k4align: No readset identifier specified\n"); return 1; }
+    const bool bam_name = o.out.size() >= 4 && strcasecmp(o.out.c_str() + o.out.size() - 4, ".bam") == 0;
+    if (o.batch_mb > 0 || o.n_shards > 1 || !o.gpus.empty() || o.legacy || o.ml_mode == 5 || bam_name) {
+      fprintf(stderr, "k4align: packed base alleles '-M3' pile up the whole run's alignments: with -b, -S i/N, -G, -Z, -r5 or a .bam output name they are not built\n");
+      return 3;
+    }
+  } else if (o.given.find('w') != std::string::npos || o.given.find('W') != std::string::npos) {
+    fprintf(stderr, "k4align: --experimentid / --readsetid belong to the packed base alleles output '-M3'\n");
+    return 1;
+  }
   // multi-loci modes (KAlignerCL.cpp:686-707): 0 slough, 1 statistics only, 5 report every locus up to -R; the modes that
   // pick or cluster one locus (2 random, 3/4 AssignMultiMatches) are not part of this path
   if (o.ml_mode < 0 || o.ml_mode > 5) { fprintf(stderr, "k4align: -r%d is not supported (0..5 are)\n", o.ml_mode); return 1; }
@@ -1613,10 +1682,10 @@ int main(int argc, char** argv) {
   if (pe && (o.micro_indel || o.splice_junct)) { fprintf(stderr, "k4align: microInDel '-a' / splice junction '-A' processing not supported in paired end processing\n"); return 1; }
   if (o.ml_mode == 5 && (o.micro_indel || o.splice_junct)) { fprintf(stderr, "k4align: microInDels / splice junctions not supported when reporting multiloci alignments '-r5'\n"); return 1; }
   if (o.min_chimeric && (o.best || o.ml_mode == 3 || o.ml_mode == 4)) { fprintf(stderr, "k4align: chimeric read processing cannot be combined with -N / -r3 / -r4\n"); return 1; }
-  // output format (KAlignerCL.cpp:217,514-519): -M0 the accepted alignments, -M1 every loaded read; -M2 (BED) and -M3 (packed base
-  // alleles) are not built
+  // output format (KAlignerCL.cpp:217,514-519): -M0 the accepted alignments, -M1 every loaded read, -M3 genpba's packed base
+  // alleles (checked above); -M2 (BED) is not built
   if (o.fmode < 0 || o.fmode > 3) { fprintf(stderr, "k4align: output format mode '-M%d' specified outside of range 0..3\n", o.fmode); return 1; }
-  if (o.fmode >= 2) { fprintf(stderr, "k4align: output format -M%d (BED / packed base alleles) is not built\n", o.fmode); return 3; }
+  if (o.fmode == 2) { fprintf(stderr, "k4align: output format -M2 (BED) is not built\n"); return 3; }
   if (o.fmode == 1) {
     if (o.batch_mb > 0 || o.n_shards > 1 || o.legacy || o.ml_mode == 5) {
       fprintf(stderr, "k4align: -M1 is written by the pipelined modes (not with -b, -S i/N, -Z, -r5)\n");

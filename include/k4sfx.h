@@ -539,7 +539,7 @@ int k4_format_bam_dev(k4_index* ix, int pe, int64_t n_units, const void* d_rr, c
  * device: base counts per locus, the 51-base background window, the coverage / non-reference tests; on the host, for the loci that
  * pass: binomial p-value (CStats::Binomial), Benjamini-Hochberg at `qvalue`, ranks, text.  min_snp_reads: kalign -p (1..),
  * snp_nonref_pcnt: kalign -1 (percent).  *csv is malloc'd: release with k4_free_host.  The files kalign writes beside the CSV
- * (coverage WIG, DiSNPs, TriSNPs, markers) are not produced. */
+ * (coverage WIG, DiSNPs, TriSNPs, markers, centroids) come from k4_snp_files_dev / k4_snp_run_dev / k4_snp_run2_dev. */
 int k4_snp_csv_dev(k4_index* ix, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml, const void* d_pe,
                    const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads, double qvalue,
                    double snp_nonref_pcnt, char** csv, uint64_t* csv_bytes, uint64_t* n_snps, void* stream);
@@ -568,6 +568,41 @@ typedef struct k4_snp_files {
 int k4_snp_run_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
                    const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads, double qvalue,
                    double snp_nonref_pcnt, k4_snp_files* out, void* stream);
+/* ... and the two files kalign writes from the same per-locus counts when asked to:
+ *   markers (kalign -K<len> [--markerpolythres <dbl>], KAligner.cpp:7494-7560; the file is <snp file>.markers): for every candidate
+ *   locus that passed the background noise test, the marker_len (0: none, else 25..500) consensus bases around it, marker_len / 2
+ *   in front.  A candidate too close to an end, with a non-reference proportion below 0.5, with a marker locus covered by fewer
+ *   than min_snp_reads bases or too polymorphic (k4_marker_classify_host has that rule), or whose centre calls the reference base
+ *   has no marker and is DROPPED before the p-values and the Benjamini-Hochberg cut: ranks, calls, DiSNPs / TriSNPs and the WIG's
+ *   last span all follow.  An accepted one gets the next marker id of the run, a FASTA record
+ *   ">Marker<id> <chrom> <start>|<len>|<locus>|<len / 2>|<SNP base>|<ref base>|<polymorphic sites>" whether or not it is called later,
+ *   and its id and polymorphic site count in the CSV's last two columns.
+ *   centroids (kalign -7 <file>, :7380-7398, :8104-8133, :8626-8660): a CSV of all 4^7 7-mers, one line each: how many loci with at
+ *   least min_snp_reads bases have it as the reference sequence around them (3 bases either side, no non-ACGT symbol; counted on
+ *   the device over every locus of every sequence with alignments, independent of calling), how many called SNPs, and the sums of
+ *   those SNPs' reference count and five non-reference counts as piled.  Counts are kept in 64 bits and printed as int, as the
+ *   reference prints them.
+ * Without either option the four texts are those of k4_snp_run_dev; markers / centroids stay NULL unless asked for.  Each text is
+ * malloc'd: release with k4_free_host. */
+typedef struct k4_snp_opts {
+  int32_t marker_len;        /* kalign -K: 0 or 25..500 */
+  int32_t want_centroids;    /* kalign -7 */
+  double marker_poly_thres;  /* kalign --markerpolythres: 0.0..0.5 (kalign's default: 1.0 / 3.0) */
+} k4_snp_opts;
+typedef struct k4_snp_files2 {
+  k4_snp_files files;
+  char* markers;   uint64_t markers_bytes;  uint64_t n_markers;
+  char* centroids; uint64_t centroids_bytes;
+} k4_snp_files2;
+int k4_snp_run2_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
+                    const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads, double qvalue,
+                    double snp_nonref_pcnt, const k4_snp_opts* opts, k4_snp_files2* out, void* stream);
+/* the marker rule of one locus alone, on the host (no device, no index): the same function the kernel runs.  cnt7 / ref_bases as for
+ * k4_pba_classify_host.  tot = ref + nonref; tot < min_snp_reads: base 0xff (the marker is rejected).  nonref / (double)tot <=
+ * poly_thres: the target's base, polymorphic when that proportion > 0.1.  Else the first of A, C, G, T, N with a count > 0 and
+ * count / (double)tot >= 1.0 - poly_thres: that base (0..4), polymorphic when its proportion < 0.9; none: base 0xfe (rejected). */
+int k4_marker_classify_host(const uint32_t* cnt7, uint64_t stride, uint32_t n_loci, const uint8_t* ref_bases, int32_t min_snp_reads,
+                            double poly_thres, uint8_t* base, uint8_t* poly);
 void k4_free_host(void* p);
 /* k4_pba_run_dev <- `ngskit4b genpba` (kalignerPBA, KAlignerCL.cpp:1540-2290: CKAligner::Process with eFMPBA; ProcessSNPs
  * KAligner.cpp:8168-8575 and the PBA branch of OutputSNPs :7194-7317): the packed base alleles of a run's accepted alignments and

@@ -140,6 +140,22 @@ class Counters(C.Structure):
                 ("n_slow", C.c_uint64), ("n_bases", C.c_uint64)]
 
 
+class SnpFiles(C.Structure):  # k4_snp_files
+    _fields_ = [("snp", C.c_void_p), ("snp_bytes", C.c_uint64), ("n_snps", C.c_uint64), ("wig", C.c_void_p), ("wig_bytes", C.c_uint64),
+                ("disnp", C.c_void_p), ("disnp_bytes", C.c_uint64), ("trisnp", C.c_void_p), ("trisnp_bytes", C.c_uint64)]
+
+
+class SnpOpts(C.Structure):  # k4_snp_opts
+    _fields_ = [("marker_len", C.c_int32), ("want_centroids", C.c_int32), ("marker_poly_thres", C.c_double)]
+
+
+class SnpFiles2(C.Structure):  # k4_snp_files2
+    _fields_ = [("files", SnpFiles), ("markers", C.c_void_p), ("markers_bytes", C.c_uint64), ("n_markers", C.c_uint64),
+                ("centroids", C.c_void_p), ("centroids_bytes", C.c_uint64)]
+
+
+DFLT_MARKER_POLY_THRES = 1.0 / 3.0  # cDfltMinMarkerSNPProp (KAligner.h:73)
+
 _lib = None
 
 # every symbol include/k4sfx.h declares
@@ -159,7 +175,7 @@ ABI_SYMBOLS = [
     "k4_set_raw_header", "k4_align_stats_collect", "k4_align_stats_dev", "k4_free_align_stats", "k4_write_align_stats",
     "k4_pipeline_align_stats", "k4_filter_loci_constraints_dev", "k4_filter_chroms_dev", "k4_load_loci_constraints", "k4_chrom_accept_mask",
     "k4_filter_marked_prior", "k4_site_prefs_dev", "k4_free_site_prefs", "k4_write_site_prefs", "k4_pipeline_site_prefs",
-    "k4_pba_run_dev", "k4_pba_classify_host",
+    "k4_pba_run_dev", "k4_pba_classify_host", "k4_snp_run2_dev", "k4_marker_classify_host",
 ]
 
 
@@ -291,6 +307,8 @@ def lib():
     L.k4_snp_vcf_dev.argtypes = snp_head + [pvp, pu64, pu64, vp]
     L.k4_snp_files_dev.argtypes = [vp, i32] + snp_head[1:] + [pvp, pu64, pu64, pvp, pu64, vp]
     L.k4_snp_run_dev.argtypes = [vp, i32] + snp_head[1:] + [vp, vp]
+    L.k4_snp_run2_dev.argtypes = [vp, i32] + snp_head[1:] + [C.POINTER(SnpOpts), C.POINTER(SnpFiles2), vp]
+    L.k4_marker_classify_host.argtypes = [vp, u64, u32, vp, C.c_int32, dbl, vp, vp]
     L.k4_free_host.argtypes = [vp]
     L.k4_free_host.restype = None
     L.k4_pba_run_dev.argtypes = [vp, i32, i64, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_char_p, C.c_char_p, C.POINTER(PbaFiles), vp]
@@ -674,15 +692,16 @@ class SfxIndex:
         L.k4_free_host(csv)
         return text, ns.value
 
-    def snp_files(self, reads, out=None, hits=None, pe_recs=None, min_snp_reads=5, qvalue=0.05, snp_nonref_pcnt=25.0, vcf=False):
+    def snp_files(self, reads, out=None, hits=None, pe_recs=None, min_snp_reads=5, qvalue=0.05, snp_nonref_pcnt=25.0, vcf=False, marker_len=0,
+                  marker_poly_thres=None, centroids=False):
         """every file of a kalign SNP run (k4_snp_run_dev) over host-side results, as a dict of texts: "snp" (CSV, or VCF), "wig"
-        (.covsegs.wig), "disnp" (.disnp.csv), "trisnp" (.trisnp.csv), and "n_snps"."""
+        (.covsegs.wig), "disnp" (.disnp.csv), "trisnp" (.trisnp.csv), and "n_snps".  marker_len (kalign -K, 25..500; marker_poly_thres:
+        --markerpolythres, default 1/3) adds "markers" (<snp file>.markers) and "n_markers"; centroids=True (kalign -7) adds
+        "centroids" (k4_snp_run2_dev)."""
         import torch
 
-        class SnpFiles(C.Structure):
-            _fields_ = [("snp", C.c_void_p), ("snp_bytes", C.c_uint64), ("n_snps", C.c_uint64), ("wig", C.c_void_p), ("wig_bytes", C.c_uint64),
-                        ("disnp", C.c_void_p), ("disnp_bytes", C.c_uint64), ("trisnp", C.c_void_p), ("trisnp_bytes", C.c_uint64)]
-
+        if marker_len or centroids:
+            return self._snp_files2(reads, out, hits, pe_recs, min_snp_reads, qvalue, snp_nonref_pcnt, vcf, marker_len, marker_poly_thres, centroids)
         dev = torch.device("cuda", self.info()["device"])
         cat, offs, lens = _flatten(reads)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
@@ -703,6 +722,38 @@ class SfxIndex:
         for k in ("snp", "wig", "disnp", "trisnp"):
             res[k] = C.string_at(getattr(f, k), getattr(f, k + "_bytes")).decode()
             L.k4_free_host(getattr(f, k))
+        return res
+
+    def _snp_files2(self, reads, out, hits, pe_recs, min_snp_reads, qvalue, snp_nonref_pcnt, vcf, marker_len, marker_poly_thres, centroids):
+        import torch
+
+        dev = torch.device("cuda", self.info()["device"])
+        cat, offs, lens = _flatten(reads)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
+        d_reads = torch.from_numpy(np.concatenate([cat, np.zeros(16, np.uint8)])).to(dev)
+        d_offs, d_lens = t(offs), t(lens)
+        L = lib()
+        f = SnpFiles2()
+        o = SnpOpts(int(marker_len), 1 if centroids else 0, DFLT_MARKER_POLY_THRES if marker_poly_thres is None else float(marker_poly_thres))
+        if pe_recs is not None:
+            d_pe = t(pe_recs)
+            self._ck(L.k4_snp_run2_dev(self.h, 1 if vcf else 0, 1, len(lens) // 2, None, None, 1, d_pe.data_ptr(), d_reads.data_ptr(), d_offs.data_ptr(),
+                                       d_lens.data_ptr(), min_snp_reads, qvalue, snp_nonref_pcnt, C.byref(o), C.byref(f), 0))
+        else:
+            d_rr, d_hits = t(out), t(hits)
+            max_ml = 1 if hits.ndim == 1 else hits.shape[1]
+            self._ck(L.k4_snp_run2_dev(self.h, 1 if vcf else 0, 0, len(lens), d_rr.data_ptr(), d_hits.data_ptr(), max_ml, None, d_reads.data_ptr(),
+                                       d_offs.data_ptr(), d_lens.data_ptr(), min_snp_reads, qvalue, snp_nonref_pcnt, C.byref(o), C.byref(f), 0))
+        res = {"n_snps": f.files.n_snps}
+        for k in ("snp", "wig", "disnp", "trisnp"):
+            res[k] = C.string_at(getattr(f.files, k), getattr(f.files, k + "_bytes")).decode()
+            L.k4_free_host(getattr(f.files, k))
+        if marker_len:
+            res["markers"], res["n_markers"] = C.string_at(f.markers, f.markers_bytes).decode(), f.n_markers
+            L.k4_free_host(f.markers)
+        if centroids:
+            res["centroids"] = C.string_at(f.centroids, f.centroids_bytes).decode()
+            L.k4_free_host(f.centroids)
         return res
 
     def pba(self, reads, out=None, hits=None, pe_recs=None, experiment_id="Unspecified", readset_id="Unspecified"):
@@ -990,6 +1041,23 @@ def pba_classify_host(cnt7, ref_bases):
     if rc != 0:
         raise K4Error(rc, "k4_pba_classify_host")
     return pba, cov
+
+
+def marker_classify_host(cnt7, ref_bases, min_snp_reads, poly_thres=DFLT_MARKER_POLY_THRES):
+    """the per-locus rule of kalign's marker sequences on the host (k4_marker_classify_host; needs the library, no GPU).  cnt7 and
+    ref_bases as for pba_classify_host.  Returns (base, polymorphic) as uint8 arrays: base 0..4 = A, C, G, T, N, 0xff = fewer than
+    min_snp_reads bases there, 0xfe = no allele reaches 1 - poly_thres (both reject the marker)."""
+    cnt7 = np.ascontiguousarray(cnt7, dtype=np.uint32)
+    ref_bases = np.ascontiguousarray(ref_bases, dtype=np.uint8)
+    if cnt7.ndim != 2 or cnt7.shape[0] != 7 or ref_bases.shape != (cnt7.shape[1],):
+        raise ValueError("cnt7 is [7, n_loci], ref_bases [n_loci]")
+    n = cnt7.shape[1]
+    base, poly = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    rc = lib().k4_marker_classify_host(cnt7.ctypes.data, n, n, ref_bases.ctypes.data, int(min_snp_reads), float(poly_thres), base.ctypes.data,
+                                       poly.ctypes.data)
+    if rc != 0:
+        raise K4Error(rc, "k4_marker_classify_host")
+    return base, poly
 
 
 def build_sa_device(concat_len, el_size, d_seq_ptr, d_sa_ptr, device=0):

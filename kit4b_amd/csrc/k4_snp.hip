@@ -12,8 +12,15 @@
 // The files kalign writes beside it: the coverage WIG (host threads, one per chromosome) and the DiSNP / TriSNP haplotype files
 // (:7767-8101; one thread per alignment finds the called loci it covers and counts its base combination for every run of two /
 // three of them).  The pile-up, the pass that marks the sequences with alignments and the WIG walk live in k4_pileup.h: genpba's packed
-// base alleles (k4_pba.hip) start from the same counts.  Not built: marker sequences, centroids, the BED form.  Equal p-values keep locus order in the ranking (the reference's multi-threaded quicksort
-// leaves them in no defined order).
+// base alleles (k4_pba.hip) start from the same counts.  Not built: the BED form.  Equal p-values keep locus order in the ranking (the
+// reference's multi-threaded quicksort leaves them in no defined order).
+// With the options of k4_snp_run2_dev two more files come out of the same counts:
+//   SNP centroids (kalign -7; :7380-7398, :8104-8133, :8626-8660): how often each of the 4^7 reference 7-mers lies around a locus
+//   with enough coverage (NumInsts: one streaming kernel per chromosome, k4k_snp_centroid_insts, a histogram in LDS per workgroup)
+//   and around a called SNP (NumSNPs and the base counts: on the host, from the 7-mer index the candidate kernel leaves in Cand.cent).
+//   Marker sequences (kalign -K; :7494-7560): for every candidate locus that passed the noise test, the MarkerLen consensus bases
+//   around it (k4k_snp_markers, one wave per candidate, the per-locus rule in k4_marker_classify.h); a candidate without a marker
+//   is dropped BEFORE the p-values and the Benjamini-Hochberg cut, so every file of the run changes with -K.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -26,18 +33,35 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 #include "k4_device.h"
+#include "k4_marker_classify.h"
 #include "k4_pileup.h"
 #include "k4_stage.h"
 
 namespace {
 
-struct Cand { uint32_t loci, n_ref, n_nonref, by_base[5], loc_mm, loc_m, ref_base, pad; };  // 48 bytes
+struct Cand { uint32_t loci, n_ref, n_nonref, by_base[5], loc_mm, loc_m, ref_base, cent; };  // 48 bytes
+
+#define K4_CENT_FLANK 3u                // cSNPCentfFlankLen
+#define K4_CENT_BINS 16384u             // 4^7: cSNPCentroidEls
+#define K4_CENT_NONE 0xffffffffu        // the locus has no 7-mer: too close to an end, or a non-ACGT symbol in the window
+
+// the reference 7-mer around locus l as the centroid table's index (first base in the highest two bits, :7385-7394)
+K4_DEV uint32_t snp_centroid_index(const SnpArgs& a, uint32_t l) {
+  if (l < K4_CENT_FLANK || (uint64_t)l + K4_CENT_FLANK >= a.clen) return K4_CENT_NONE;
+  uint32_t idx = 0;
+  for (uint32_t k = 0; k < 2 * K4_CENT_FLANK + 1; k++) {
+    const uint32_t b = k4d_ref_base(a.ix, a.cs + l - K4_CENT_FLANK + k) & 7u;
+    if (b > 3) return K4_CENT_NONE;
+    idx = (idx << 2) | b;
+  }
+  return idx;
+}
 
 // OutputSNPs' per-locus tests that need no error rate (:7375-7438): coverage, non-reference count and proportion; the window
 // [l - 25, l + 26) clamped into the chromosome as the reference's sliding sums have it
 __global__ void __launch_bounds__(256) k4k_snp_candidates(SnpArgs a, const uint64_t* __restrict__ p_ref, const uint64_t* __restrict__ p_non,
                                                           int min_snp_reads, double nonref_frac, Cand* __restrict__ out, uint32_t cap,
-                                                          uint32_t* __restrict__ n_out) {
+                                                          uint32_t* __restrict__ n_out, int want_cent) {
   const uint32_t l = blockIdx.x * 256u + threadIdx.x;
   if (l >= a.clen) return;
   const size_t S = K4_SNP_STRIDE(a);
@@ -59,8 +83,97 @@ __global__ void __launch_bounds__(256) k4k_snp_candidates(SnpArgs a, const uint6
   for (int b = 0; b < 5; b++) c.by_base[b] = a.cnt[(2 + b) * S + l];
   c.loc_mm = loc_mm; c.loc_m = loc_m;
   c.ref_base = k4d_ref_base(a.ix, a.cs + l);  // pSNP->RefBase: the target symbol (a covered locus: the reference has set it)
-  c.pad = 0;
+  c.cent = want_cent ? snp_centroid_index(a, l) : 0u;  // (a few hundred candidates per chromosome: seven symbol look-ups each are nothing)
   out[slot] = c;
+}
+
+// SNP centroids, NumInsts (:7377-7398): every locus of the chromosome with at least MinSNPreads bases counts for the reference 7-mer
+// around it.  One streaming pass over the two coverage arrays: a thread takes four consecutive loci (one 16-byte load per array, as
+// k4k_pba_classify), and only where one of them is covered deeply enough does it walk the ten reference symbols its four windows
+// span -- rolled through a 14-bit index, two bits per locus, with a 7-bit mask of the non-ACGT symbols beside it (K4Tb: one packed
+// word, one look-up of a flagged block for the whole walk).  A symbol outside the chromosome enters as non-ACGT, which is the
+// reference's bounds test (Loci >= 3 && Loci < ChromLen - 3).
+// The histogram is private to the workgroup: 16384 uint32 bins = 64 KiB of LDS, so two workgroups of 512 threads share a CU's
+// 160 KiB (16 waves per CU, enough for a pass that waits on memory); a workgroup strides over tiles of 2048 loci and adds its
+// non-zero bins to the run's 64-bit table at the end (a 32-bit bin holds a workgroup's share: far fewer than 2^32 loci).
+#define K4_CENT_LPT 4u
+#define K4_CENT_THREADS 512u
+__global__ void __launch_bounds__(K4_CENT_THREADS) k4k_snp_centroid_insts(SnpArgs a, int min_snp_reads, unsigned long long* __restrict__ table) {
+  __shared__ uint32_t bins[K4_CENT_BINS];
+  for (uint32_t k = threadIdx.x; k < K4_CENT_BINS; k += K4_CENT_THREADS) bins[k] = 0;
+  __syncthreads();
+  const size_t S = K4_SNP_STRIDE(a);
+  const uint64_t tile = (uint64_t)K4_CENT_THREADS * K4_CENT_LPT;
+  K4Tb tb;
+  tb.init(a.ix);
+  for (uint64_t t0 = (uint64_t)blockIdx.x * tile; t0 < a.clen; t0 += (uint64_t)gridDim.x * tile) {
+    const uint64_t l0 = t0 + (uint64_t)threadIdx.x * K4_CENT_LPT;
+    if (l0 >= a.clen) continue;
+    uint32_t nr[K4_CENT_LPT], nn[K4_CENT_LPT];
+    k4d_load_words<K4_CENT_LPT>(a.cnt + l0, nr);      // (the arrays carry 16 zeroed words behind the chromosome)
+    k4d_load_words<K4_CENT_LPT>(a.cnt + S + l0, nn);
+    bool any = false;
+#pragma unroll
+    for (uint32_t j = 0; j < K4_CENT_LPT; j++) any |= (int)(nr[j] + nn[j]) >= min_snp_reads;
+    if (!any) continue;
+    uint32_t idx = 0, bad = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < K4_CENT_LPT + 2 * K4_CENT_FLANK; k++) {  // symbols l0 - 3 .. l0 + 6; after symbol l + 3 the window of l is whole
+      const int64_t l = (int64_t)l0 + k - K4_CENT_FLANK;
+      const uint32_t b = l >= 0 && l < (int64_t)a.clen ? tb.get((int64_t)a.cs + l) : 4u;
+      idx = ((idx << 2) | (b & 3u)) & (K4_CENT_BINS - 1u);
+      bad = ((bad << 1) | (b > 3 ? 1u : 0u)) & 0x7fu;
+      if (k >= 2 * K4_CENT_FLANK) {
+        const uint32_t j = k - 2 * K4_CENT_FLANK;
+        if (!bad && (int)(nr[j] + nn[j]) >= min_snp_reads) atomicAdd(&bins[idx], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < K4_CENT_BINS; k += K4_CENT_THREADS)
+    if (bins[k]) atomicAdd(&table[k], (unsigned long long)bins[k]);
+}
+
+// Marker sequences (:7494-7545): one wave per candidate locus.  The tests on the candidate itself (inside the chromosome with its
+// flanks, its own non-reference proportion at least 0.5) first; then the lanes stride over the MarkerLen loci, apply the per-locus
+// rule and write the base; the wave gathers whether any locus rejected and how many are polymorphic; last the centre's base against
+// the reference base there.  Per candidate: hdr[2 w] = 1 accepted / 0 rejected, hdr[2 w + 1] = NumPolymorphicSites, seq[w * len ..].
+__global__ void __launch_bounds__(256) k4k_snp_markers(SnpArgs a, const uint32_t* __restrict__ loci, uint32_t n, int marker_len, int min_snp_reads,
+                                                       double poly_thres, uint32_t* __restrict__ hdr, uint8_t* __restrict__ seq) {
+  const uint32_t w = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+  if (w >= n) return;  // (whole waves leave: the shuffles below see all their lanes)
+  const size_t S = K4_SNP_STRIDE(a);
+  const uint32_t m5 = (uint32_t)marker_len / 2u, m3 = (uint32_t)marker_len - 1u - m5;  // m_Marker5Len, m_Marker3Len (:260-261)
+  const uint32_t l = loci[w];
+  bool ok = l < a.clen && l >= m5 && (uint64_t)l + m3 < a.clen;
+  if (ok) {
+    const uint32_t n_ref = a.cnt[l], n_non = a.cnt[S + l];
+    const int tot = (int)(n_non + n_ref);
+    ok = tot > 0 && !((double)n_non / tot < 0.5);
+  }
+  uint32_t poly = 0, centre = 0;
+  bool rej = false;
+  if (ok) {
+    for (uint32_t q = lane; q < (uint32_t)marker_len; q += 64u) {
+      const uint32_t ml = l - m5 + q;
+      const uint32_t by_base[5] = {a.cnt[2 * S + ml], a.cnt[3 * S + ml], a.cnt[4 * S + ml], a.cnt[5 * S + ml], a.cnt[6 * S + ml]};
+      int p = 0;
+      const int b = k4_marker_base(a.cnt[ml], a.cnt[S + ml], by_base, k4d_ref_base(a.ix, a.cs + ml) & 7u, min_snp_reads, poly_thres, &p);
+      if (b < 0) { rej = true; continue; }
+      poly += (uint32_t)p;
+      seq[(size_t)w * (uint32_t)marker_len + q] = (uint8_t)"ACGTN"[b];
+      if (q == m5) centre = (uint32_t)b;
+    }
+  }
+  for (int d = 32; d > 0; d >>= 1) poly += __shfl_down(poly, d, 64);
+  const bool any_rej = __ballot(rej) != 0ull;
+  centre = __shfl(centre, (int)(m5 & 63u), 64);
+  if (lane == 0) {
+    uint32_t ref = k4d_ref_base(a.ix, a.cs + (l < a.clen ? l : 0u)) & 7u;
+    if (ref > 4) ref = 4;
+    hdr[2 * w] = ok && !any_rej && centre != ref ? 1u : 0u;  // (:7543: the centre must not call the reference base)
+    hdr[2 * w + 1] = poly;
+  }
 }
 
 // coverage per locus (TotBases) for the WIG: ref + nonref.  First its maximum, then the array in the narrowest of 1 / 2 / 4 bytes
@@ -207,14 +320,28 @@ struct LociPV {
   uint32_t loci, rank, num_reads, num_subs, local_reads, local_subs, ref_base;
   uint32_t by_base[5];
   double pvalue, bkgnd;
+  uint32_t cent, marker_id, n_poly;
 };
+
+// what k4_snp_run2_dev adds to a run: the options, the centroid table and the marker text it fills
+struct SnpExtra {
+  int marker_len = 0;
+  double poly_thres = 0.0;
+  bool want_centroids = false;
+  std::string markers;
+  uint64_t n_markers = 0;  // m_MarkerID: counted over the whole run
+  std::string centroids;
+};
+struct Centroid { uint64_t n_insts, n_snps, ref_cnt, by_base[5]; };
+const uint32_t kMarkerChunk = 4096;  // candidates per launch of k4k_snp_markers: one wave each fills the device; the output stays below 2.1 MB
 
 }  // namespace
 
 static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
                         const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
                         double qvalue, double snp_nonref_pcnt, char** csv, uint64_t* csv_bytes, uint64_t* n_snps, void* stream,
-                        char** wig = nullptr, uint64_t* wig_bytes = nullptr, std::string* di_text = nullptr, std::string* tri_text = nullptr);
+                        char** wig = nullptr, uint64_t* wig_bytes = nullptr, std::string* di_text = nullptr, std::string* tri_text = nullptr,
+                        SnpExtra* extra = nullptr);
 // both files of a kalign SNP run: the SNP file (CSV, or VCF when vcf != 0) and the coverage WIG (<snp file>.covsegs.wig)
 extern "C" int k4_snp_files_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
                                 const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
@@ -225,14 +352,14 @@ extern "C" int k4_snp_files_dev(k4_index* ix, int vcf, int pe, int64_t n_units, 
                       n_snps, stream, wig, wig_bytes);
 }
 // every file of a kalign SNP run: the SNP file, the coverage WIG and the two haplotype files (.disnp.csv, .trisnp.csv)
-extern "C" int k4_snp_run_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
-                              const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
-                              double qvalue, double snp_nonref_pcnt, k4_snp_files* out, void* stream) {
+static int snp_run(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml, const void* d_pe,
+                   const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads, double qvalue, double snp_nonref_pcnt,
+                   k4_snp_files* out, void* stream, SnpExtra* extra) {
   if (!out) return K4_ERR_PARAMS;
   memset(out, 0, sizeof(*out));
   std::string di = hap_header(2), tri = hap_header(3);
   int rc = snp_text_dev(ix, vcf, pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens, min_snp_reads, qvalue, snp_nonref_pcnt, &out->snp,
-                        &out->snp_bytes, &out->n_snps, stream, &out->wig, &out->wig_bytes, &di, &tri);
+                        &out->snp_bytes, &out->n_snps, stream, &out->wig, &out->wig_bytes, &di, &tri, extra);
   if (rc == K4_OK) {
     out->disnp = (char*)malloc(di.size() + 1);
     out->trisnp = (char*)malloc(tri.size() + 1);
@@ -247,6 +374,54 @@ extern "C" int k4_snp_run_dev(k4_index* ix, int vcf, int pe, int64_t n_units, co
     memset(out, 0, sizeof(*out));
   }
   return rc;
+}
+extern "C" int k4_snp_run_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
+                              const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
+                              double qvalue, double snp_nonref_pcnt, k4_snp_files* out, void* stream) {
+  return snp_run(ix, vcf, pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens, min_snp_reads, qvalue, snp_nonref_pcnt, out, stream, nullptr);
+}
+// ... and, as the options ask, the marker sequences (<snp file>.markers) and the SNP centroid distribution
+extern "C" int k4_snp_run2_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
+                               const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
+                               double qvalue, double snp_nonref_pcnt, const k4_snp_opts* opts, k4_snp_files2* out, void* stream) {
+  if (!out || !opts) return K4_ERR_PARAMS;
+  memset(out, 0, sizeof(*out));
+  SnpExtra ex;
+  ex.marker_len = opts->marker_len; ex.poly_thres = opts->marker_poly_thres; ex.want_centroids = opts->want_centroids != 0;
+  int rc = snp_run(ix, vcf, pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens, min_snp_reads, qvalue, snp_nonref_pcnt, &out->files, stream, &ex);
+  if (rc != K4_OK) return rc;
+  auto keep = [](const std::string& s, char** p, uint64_t* n) {
+    *p = (char*)malloc(s.size() + 1);
+    if (!*p) return false;
+    memcpy(*p, s.c_str(), s.size() + 1);
+    *n = s.size();
+    return true;
+  };
+  bool ok = true;
+  if (ex.marker_len) ok = keep(ex.markers, &out->markers, &out->markers_bytes);
+  if (ok && ex.want_centroids) ok = keep(ex.centroids, &out->centroids, &out->centroids_bytes);
+  out->n_markers = ex.n_markers;
+  if (!ok) {
+    free(out->files.snp); free(out->files.wig); free(out->files.disnp); free(out->files.trisnp); free(out->markers); free(out->centroids);
+    memset(out, 0, sizeof(*out));
+    return k4_fail(ix, K4_ERR_MEM, "out of memory");
+  }
+  return K4_OK;
+}
+// the marker rule alone, on the host: no device, no index.  cnt7: seven arrays of `stride` words each (ref, nonref, A, C, G, T, N);
+// base[l] = 0..4, or 0xff (coverage below min_snp_reads) / 0xfe (no allele reaches 1 - threshold); poly[l] = 1 for a polymorphic locus
+extern "C" int k4_marker_classify_host(const uint32_t* cnt7, uint64_t stride, uint32_t n_loci, const uint8_t* ref_bases, int32_t min_snp_reads,
+                                       double poly_thres, uint8_t* base, uint8_t* poly) {
+  if ((!cnt7 || !ref_bases || !base || !poly) && n_loci) return K4_ERR_PARAMS;
+  if (stride < n_loci || min_snp_reads < 1) return K4_ERR_PARAMS;
+  for (uint32_t l = 0; l < n_loci; l++) {
+    const uint32_t by_base[5] = {cnt7[2 * stride + l], cnt7[3 * stride + l], cnt7[4 * stride + l], cnt7[5 * stride + l], cnt7[6 * stride + l]};
+    int p = 0;
+    const int b = k4_marker_base(cnt7[l], cnt7[stride + l], by_base, ref_bases[l], min_snp_reads, poly_thres, &p);
+    base[l] = b == K4_MARKER_NO_COVERAGE ? 0xff : b == K4_MARKER_NO_ALLELE ? 0xfe : (uint8_t)b;
+    poly[l] = (uint8_t)p;
+  }
+  return K4_OK;
 }
 extern "C" int k4_snp_csv_dev(k4_index* ix, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
                               const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
@@ -264,8 +439,10 @@ extern "C" int k4_snp_vcf_dev(k4_index* ix, int pe, int64_t n_units, const void*
 static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
                         const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
                         double qvalue, double snp_nonref_pcnt, char** csv, uint64_t* csv_bytes, uint64_t* n_snps, void* stream,
-                        char** wig, uint64_t* wig_bytes, std::string* di_text, std::string* tri_text) {
+                        char** wig, uint64_t* wig_bytes, std::string* di_text, std::string* tri_text, SnpExtra* extra) {
   if (!ix || !csv || !csv_bytes) return K4_ERR_PARAMS;
+  const int marker_len = extra ? extra->marker_len : 0;
+  const bool want_cent = extra && extra->want_centroids;
   *csv = nullptr;
   *csv_bytes = 0;
   if (wig) { *wig = nullptr; *wig_bytes = 0; }
@@ -274,6 +451,8 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
   K4DevBuf covb, covmax;
   if (n_snps) *n_snps = 0;
   if (n_units < 0 || min_snp_reads < 1 || qvalue < 0.0 || snp_nonref_pcnt < 0.0) return k4_fail(ix, K4_ERR_PARAMS, "SNP parameters out of range");
+  if (marker_len != 0 && (marker_len < 25 || marker_len > 500 || !(extra->poly_thres >= 0.0 && extra->poly_thres <= 0.5)))  // cMinMarkerLen .. cMaxMarkerLen
+    return k4_fail(ix, K4_ERR_PARAMS, "marker length must be 0 or 25..500 and the marker polymorphism threshold 0.0..0.5");
   if (n_units > 0 && ((pe && !d_pe) || (!pe && (!d_rr || !d_hits || max_ml < 1)) || !d_reads || !d_offs || !d_lens))
     return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
   K4_HIP(ix, hipSetDevice(ix->device));
@@ -302,6 +481,19 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
   K4_HIP(ix, pnon.alloc((S + 1) * 8));
   K4_HIP(ix, cands.alloc((size_t)cap * sizeof(Cand)));
   K4_HIP(ix, ncand.alloc(4));
+  K4DevBuf cent_tab, mk_loci, mk_out;  // the run's centroid instance counts; a chunk of candidate loci and their markers
+  std::vector<Centroid> cent_rows;
+  if (want_cent) {  // :8319-8332
+    cent_rows.assign(K4_CENT_BINS, Centroid{0, 0, 0, {0, 0, 0, 0, 0}});
+    K4_HIP(ix, cent_tab.alloc((size_t)K4_CENT_BINS * 8));
+    K4_HIP(ix, hipMemsetAsync(cent_tab.p, 0, (size_t)K4_CENT_BINS * 8, st));
+  }
+  if (marker_len) {
+    K4_HIP(ix, mk_loci.alloc((size_t)kMarkerChunk * 4));
+    K4_HIP(ix, mk_out.alloc((size_t)kMarkerChunk * ((size_t)marker_len + 8)));
+  }
+  std::vector<uint32_t> mk_l;
+  std::vector<uint8_t> mk_h;
   K4_TRY(k4s_exclusive_scan(ix, cnt.as<uint32_t>(), pref.as<uint64_t>(), (uint64_t)0, S + 1, rocprim::plus<uint64_t>(), st, &tmp, true));
   uint64_t tot_snps = 0;
   const double nonref_frac = snp_nonref_pcnt / 100.0;  // m_SNPNonRefPcnt, KAligner.cpp:256
@@ -332,6 +524,12 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
     unsigned long long t3[4] = {0, 0, 0, 0};
     K4_TRY(k4s_read_back(ix, &t3, tot.p, st));
     if (t3[2] == 0) continue;  // no alignment on this chromosome
+    if (want_cent) {  // NumInsts of every locus of this chromosome (independent of SNP calling, :7380-7398)
+      const uint64_t tiles = ((uint64_t)a.clen + K4_CENT_THREADS * K4_CENT_LPT - 1) / (K4_CENT_THREADS * K4_CENT_LPT);
+      hipLaunchKernelGGL(k4k_snp_centroid_insts, dim3((unsigned)std::min<uint64_t>(tiles, 512)), dim3(K4_CENT_THREADS), 0, st, a, (int)min_snp_reads,
+                         cent_tab.as<unsigned long long>());
+      K4_HIP(ix, hipGetLastError());
+    }
     size_t wig_slot = 0;
     if (wig) {  // coverage down to the host, its walk on a thread of its own (at most twelve chromosomes in flight)
       if (!covb.p) { K4_HIP(ix, covb.alloc(S * 4)); K4_HIP(ix, covmax.alloc(4)); }
@@ -355,7 +553,7 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
     K4_TRY(k4s_exclusive_scan(ix, a.cnt, pref.as<uint64_t>(), (uint64_t)0, (size_t)a.clen + 1, rocprim::plus<uint64_t>(), st, &tmp));
     K4_TRY(k4s_exclusive_scan(ix, a.cnt + Sc, pnon.as<uint64_t>(), (uint64_t)0, (size_t)a.clen + 1, rocprim::plus<uint64_t>(), st, &tmp));
     hipLaunchKernelGGL(k4k_snp_candidates, dim3((a.clen + 255) / 256), dim3(256), 0, st, a, pref.as<uint64_t>(), pnon.as<uint64_t>(), (int)min_snp_reads,
-                       nonref_frac, cands.as<Cand>(), cap, ncand.as<uint32_t>());
+                       nonref_frac, cands.as<Cand>(), cap, ncand.as<uint32_t>(), want_cent ? 1 : 0);
     uint32_t nc = 0;
     K4_TRY(k4s_read_back(ix, &nc, ncand.p, st));
     if (nc > cap) return k4_fail(ix, K4_ERR_MEM, "more than %u candidate SNP loci on %s", cap, e.name);
@@ -378,13 +576,51 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
       if (local_rate > 0.20) continue;  // cMaxBkgdNoiseThres
       LociPV p;
       const int tot_bases = (int)(c.n_ref + c.n_nonref);
-      p.pvalue = 1.0 - binomial(tot_bases, (int)c.n_nonref, local_rate);
+      p.pvalue = 0.0; p.cent = c.cent; p.marker_id = 0; p.n_poly = 0;
       p.loci = c.loci; p.rank = 0; p.bkgnd = local_rate; p.local_reads = ltmm + ltm; p.local_subs = ltmm;
       p.num_reads = (uint32_t)tot_bases; p.num_subs = c.n_nonref;
       for (int b = 0; b < 5; b++) p.by_base[b] = c.by_base[b];
       p.ref_base = c.ref_base > 4 ? 4 : c.ref_base;
       pv.push_back(p);
     }
+    if (marker_len && !pv.empty()) {  // the marker gate (:7494-7560): in locus order, chunk by chunk; a candidate without a marker leaves here
+      const size_t row = (size_t)marker_len;
+      size_t kept = 0;
+      char head[600];
+      for (size_t c0 = 0; c0 < pv.size(); c0 += kMarkerChunk) {
+        const uint32_t nq = (uint32_t)std::min<size_t>(kMarkerChunk, pv.size() - c0);
+        mk_l.resize(nq);
+        for (uint32_t k = 0; k < nq; k++) mk_l[k] = pv[c0 + k].loci;
+        uint32_t* d_hdr = mk_out.as<uint32_t>();
+        uint8_t* d_seq = mk_out.as<uint8_t>() + (size_t)nq * 8;
+        K4_HIP(ix, hipMemcpyAsync(mk_loci.p, mk_l.data(), (size_t)nq * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k4k_snp_markers, dim3((nq + 3) / 4), dim3(256), 0, st, a, mk_loci.as<uint32_t>(), nq, marker_len, (int)min_snp_reads,
+                           extra->poly_thres, d_hdr, d_seq);
+        K4_HIP(ix, hipGetLastError());
+        mk_h.resize((size_t)nq * (row + 8));
+        K4_HIP(ix, hipMemcpyAsync(mk_h.data(), mk_out.p, mk_h.size(), hipMemcpyDeviceToHost, st));
+        K4_HIP(ix, hipStreamSynchronize(st));
+        for (uint32_t k = 0; k < nq; k++) {
+          uint32_t h2[2];
+          memcpy(h2, &mk_h[(size_t)k * 8], 8);
+          if (!h2[0]) continue;
+          LociPV p = pv[c0 + k];
+          const uint8_t* sq = &mk_h[(size_t)nq * 8 + (size_t)k * row];
+          const int m5 = marker_len / 2;
+          p.marker_id = (uint32_t)++extra->n_markers;
+          p.n_poly = h2[1];
+          // >MarkerNNN Chrom StartLoci|MarkerLen|SNPLoci|Marker5Len|SNPbase|RefBase|NumPolymorphicSites (:7552)
+          const int hn = snprintf(head, sizeof(head), ">Marker%d %s %d|%d|%d|%d|%c|%c|%d\n", (int)p.marker_id, e.name, (int)p.loci - m5, marker_len, (int)p.loci,
+                                  m5, (char)sq[m5], "ACGTN"[p.ref_base], (int)p.n_poly);
+          extra->markers.append(head, (size_t)std::min<int>(hn, (int)sizeof(head) - 1));
+          extra->markers.append((const char*)sq, row);
+          extra->markers += '\n';
+          pv[kept++] = p;  // (kept <= c0 + k: nothing is overwritten before it is read)
+        }
+      }
+      pv.resize(kept);
+    }
+    for (LociPV& p : pv) p.pvalue = 1.0 - binomial((int)p.num_reads, (int)p.num_subs, p.bkgnd);
     if (wig && !pv.empty()) wig_jobs[wig_slot].close_tail = true;  // (a chromosome without a candidate never closes its last span)
     if (pv.empty()) continue;
     std::stable_sort(pv.begin(), pv.end(), [](const LociPV& x, const LociPV& y) { return x.pvalue < y.pvalue; });
@@ -443,6 +679,12 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
     }
     for (LociPV& p : pv) {
       tot_snps++;
+      if (want_cent && p.cent != K4_CENT_NONE) {  // the called SNP's counts as piled, for the 7-mer around it (:8104-8133)
+        Centroid& r = cent_rows[p.cent];
+        r.n_snps++;
+        r.ref_cnt += p.num_reads - p.num_subs;
+        for (int b = 0; b < 5; b++) r.by_base[b] += p.by_base[b];
+      }
       int rel = (int)(999 - ((999 * (int64_t)p.rank) / (int64_t)n_acc));
       if (rel < 1) rel = 1;
       char line[512];
@@ -469,7 +711,7 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
       const int n = snprintf(line, sizeof(line), "%d,\"SNP\",\"%s\",\"%s\",%d,%d,1,\"+\",%d,%f,%d,%d,\"%c\",%d,%d,%d,%d,%d,%f,%d,%d,%d,%d\n", (int)tot_snps,
                              ix->dataset.c_str(), e.name, (int)p.loci, (int)p.loci, rel, p.pvalue, (int)p.num_reads, (int)p.num_subs, "ACGTN"[p.ref_base],
                              (int)p.by_base[0], (int)p.by_base[1], (int)p.by_base[2], (int)p.by_base[3], (int)p.by_base[4], p.bkgnd, (int)p.local_reads,
-                             (int)p.local_subs, 0, 0);
+                             (int)p.local_subs, (int)p.marker_id, (int)p.n_poly);
       text.append(line, (size_t)n);
     }
   }
@@ -498,6 +740,23 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
     wo[total] = 0;
     *wig = wo;
     *wig_bytes = total;
+  }
+  if (want_cent) {  // the centroid file (:8626-8660): every 7-mer, whether seen or not
+    std::vector<unsigned long long> insts(K4_CENT_BINS);
+    K4_HIP(ix, hipMemcpyAsync(insts.data(), cent_tab.p, (size_t)K4_CENT_BINS * 8, hipMemcpyDeviceToHost, st));
+    K4_HIP(ix, hipStreamSynchronize(st));
+    std::string& ct = extra->centroids;
+    ct = "\"CentroidID\",\"Seq\",\"NumInsts\",\"NumSNPs\",\"RefBase\",\"RefBaseCnt\",\"BaseA\",\"BaseC\",\"BaseG\",\"BaseT\",\"BaseN\"\n";
+    char line[256];
+    for (uint32_t id = 0; id < K4_CENT_BINS; id++) {
+      char sq[8];
+      for (int k = 0; k < 7; k++) sq[k] = "ACGT"[(id >> (2 * (6 - k))) & 3u];
+      sq[7] = 0;
+      const Centroid& r = cent_rows[id];
+      const int n = snprintf(line, sizeof(line), "%d,\"%s\",%d,%d,\"%c\",%d,%d,%d,%d,%d,%d\n", (int)id + 1, sq, (int)insts[id], (int)r.n_snps, sq[3], (int)r.ref_cnt,
+                             (int)r.by_base[0], (int)r.by_base[1], (int)r.by_base[2], (int)r.by_base[3], (int)r.by_base[4]);
+      ct.append(line, (size_t)n);
+    }
   }
   char* out = (char*)malloc(text.size() + 1);
   if (!out) return k4_fail(ix, K4_ERR_MEM, "out of memory");

@@ -89,6 +89,10 @@ struct Opts {
   int min_snp_reads = 0;            // -p <n> (0: no SNP calling), -P <qvalue>, -1 <pct>, -S <file> (KAlignerCL.cpp:259,284-291,877-932)
   double qvalue = 0.0, snp_nonref_pcnt = 25.0;
   std::string snp_file;
+  std::string cent_file;            // -7 / --snpcentroid <file>: SNP centroid distribution (KAlignerCL.cpp:260,976-983)
+  int marker_len = 0;               // -K / --markerlen <25..500>: marker sequences to <snp file>.markers (KAlignerCL.cpp:261,949-960)
+  bool marker_thres_given = false;
+  double marker_poly_thres = 0.0;   // --markerpolythres <0.0..0.5> (kalign's -G; here -G is the GPU list): cDfltMinMarkerSNPProp when not given
   int bam_level = 6;                // -z <0..9>: BGZF deflate level of a .bam output (WriteBAMReadHits is called with 6, KAligner.cpp:759)
 };
 
@@ -563,7 +567,7 @@ std::string clean_id(const std::string& raw) {
 void usage() {
   fprintf(stderr,
           "k4align -i reads.f[aq][.gz] [-i more ...] [-u mates ...] -I index.sfx -o out.sam|out.bam [-z bgzf level=6] [-s subs/100bp=5] [-e 1|2] [-m 0..3] [-n maxNs=1]\n"
-          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads | -M3 --experimentid id --readsetid id: packed base alleles to -o, no SAM] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
+          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads | -M3 --experimentid id --readsetid id: packed base alleles to -o, no SAM] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv] [-7 centroids.csv] [-K markerlen 25..500 [--markerpolythres 0..0.5=0.333]]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
 }
 
 }  // namespace
@@ -1017,22 +1021,36 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
       // a file name ending in .vcf: VCF instead of the CSV (KAligner.cpp:186-187)
       const bool vcf = o.snp_file.size() >= 4 && strcasecmp(o.snp_file.c_str() + o.snp_file.size() - 4, ".vcf") == 0;
       k4_snp_files sf;
-      CK(k4_snp_run_dev(ix, vcf ? 1 : 0, pe ? 1 : 0, v.n_units, v.d_rr, v.d_hits, v.max_ml, v.d_pe, v.d_reads, v.d_offs, v.d_lens, o.min_snp_reads,
-                        o.qvalue, o.snp_nonref_pcnt, &sf, nullptr));
+      k4_snp_files2 sf2;
+      memset(&sf2, 0, sizeof(sf2));
+      const bool more = o.marker_len != 0 || !o.cent_file.empty();  // the marker and centroid files out of the same counts
+      if (more) {
+        k4_snp_opts so;
+        so.marker_len = o.marker_len; so.want_centroids = o.cent_file.empty() ? 0 : 1; so.marker_poly_thres = o.marker_poly_thres;
+        CK(k4_snp_run2_dev(ix, vcf ? 1 : 0, pe ? 1 : 0, v.n_units, v.d_rr, v.d_hits, v.max_ml, v.d_pe, v.d_reads, v.d_offs, v.d_lens, o.min_snp_reads,
+                           o.qvalue, o.snp_nonref_pcnt, &so, &sf2, nullptr));
+        sf = sf2.files;
+      } else
+        CK(k4_snp_run_dev(ix, vcf ? 1 : 0, pe ? 1 : 0, v.n_units, v.d_rr, v.d_hits, v.max_ml, v.d_pe, v.d_reads, v.d_offs, v.d_lens, o.min_snp_reads,
+                          o.qvalue, o.snp_nonref_pcnt, &sf, nullptr));
       // side files: <snp file cut at its last '.'> + suffix (CUtility::AppendFileNameSuffix, KAligner.cpp:4512, 4553-4554)
       std::string stem = o.snp_file;
       for (size_t q = stem.size(); q > 0; q--) {
         if (stem[q - 1] == '.') { stem.resize(q - 1); break; }
         if (stem[q - 1] == '/' || stem[q - 1] == '\\') break;
       }
-      const struct { std::string name; const char* p; uint64_t n; } files[4] = {{stem + ".covsegs.wig", sf.wig, sf.wig_bytes},
-                                                                                {stem + ".disnp.csv", sf.disnp, sf.disnp_bytes},
-                                                                                {stem + ".trisnp.csv", sf.trisnp, sf.trisnp_bytes},
-                                                                                {o.snp_file, sf.snp, sf.snp_bytes}};
+      struct SnpOut { std::string name; const char* p; uint64_t n; bool guarded; };
+      std::vector<SnpOut> files = {{stem + ".covsegs.wig", sf.wig, sf.wig_bytes, false},
+                                   {stem + ".disnp.csv", sf.disnp, sf.disnp_bytes, false},
+                                   {stem + ".trisnp.csv", sf.trisnp, sf.trisnp_bytes, false},
+                                   {o.snp_file, sf.snp, sf.snp_bytes, false}};
+      if (o.marker_len) files.push_back({o.snp_file + ".markers", sf2.markers, sf2.markers_bytes, true});  // (the name is appended, KAlignerCL.cpp:957-959)
+      if (!o.cent_file.empty()) files.push_back({o.cent_file, sf2.centroids, sf2.centroids_bytes, true});
       std::string failed;
       for (const auto& f : files) {  // (the coverage WIG of a genome at low coverage runs to gigabytes: pwrite()s side by side)
         FILE* fp = fopen(f.name.c_str(), "wb");
         bool ok = fp != nullptr;
+        if (ok && f.guarded) guard.made.push_back(f.name);
         if (ok && f.n >= (64u << 20)) {
           const int fd = fileno(fp);
           const int nt = std::max(o.io_threads, 1);
@@ -1056,9 +1074,13 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
         if (!ok && failed.empty()) failed = f.name;
       }
       k4_free_host(sf.snp); k4_free_host(sf.wig); k4_free_host(sf.disnp); k4_free_host(sf.trisnp);
+      k4_free_host(sf2.markers); k4_free_host(sf2.centroids);
       if (!failed.empty()) { fprintf(stderr, "k4align: unable to write %s\n", failed.c_str()); return 5; }
       if (chatty) fprintf(stderr, "k4align: SNP processing completed with %llu putative SNPs discovered, written to %s in %.2fs\n",
                           (unsigned long long)sf.n_snps, o.snp_file.c_str(), secs(ts, now()));
+      if (chatty && o.marker_len) fprintf(stderr, "k4align: %llu marker sequences of %d bases written to %s.markers\n", (unsigned long long)sf2.n_markers,
+                                          o.marker_len, o.snp_file.c_str());
+      if (chatty && !o.cent_file.empty()) fprintf(stderr, "k4align: SNP centroid distribution written to %s\n", o.cent_file.c_str());
     }
     if (!o.stats_file.empty()) {  // behind every stage that can still drop a read: the counted reads are the reported ones
       auto ts = now();
@@ -1502,6 +1524,9 @@ int main(int argc, char** argv) {
         else if (name == "lociconstraints") { o.loci_file = v; o.given += '5'; }
         else if (name == "siteprefs") { o.site_file = v; o.given += '8'; }
         else if (name == "siteprefsofs") { o.site_ofs = atoi(v.c_str()); o.given += '9'; }
+        else if (name == "snpcentroid") { o.cent_file = v; o.given += '7'; }
+        else if (name == "markerlen") { o.marker_len = atoi(v.c_str()); o.given += 'K'; }
+        else if (name == "markerpolythres") { o.marker_poly_thres = atof(v.c_str()); o.marker_thres_given = true; o.given += 'K'; }
         else if (name == "experimentid") { o.experiment_id = clean_id(v); o.given += 'w'; }
         else if (name == "readsetid") { o.readset_id = clean_id(v); o.given += 'W'; }
         else { usage(); return 1; }
@@ -1535,6 +1560,8 @@ int main(int argc, char** argv) {
       case 'p': o.min_snp_reads = atoi(val().c_str()); break;
       case 'P': o.qvalue = atof(val().c_str()); break;
       case '1': o.snp_nonref_pcnt = atof(val().c_str()); break;
+      case '7': o.cent_file = val(); break;
+      case 'K': o.marker_len = atoi(val().c_str()); break;
       case 'X': o.clamp = true; break;
       case 'N': o.best = true; break;
       case 'S': {  // "i/N": this process's slice of the reads; anything else: kalign's -S, the SNP file
@@ -1592,7 +1619,7 @@ int main(int argc, char** argv) {
   // -M3: `ngskit4b genpba` (kalignerPBA, KAlignerCL.cpp:1540-2290).  Its argument table (:1556-1628) is kalign's without the
   // second-segment phases, the side files and SNP calling; -w / -W are required there (arg_str1, cleaned :1697-1729)
   if (o.fmode == 3) {
-    for (const char c : std::string("aAOjJ895pP1N"))
+    for (const char c : std::string("aAOjJ895pP1N7K"))
       if (o.given.find(c) != std::string::npos) { fprintf(stderr, "k4align: genpba '-M3' has no option '-%c'\n", c); return 1; }
     if (!o.snp_file.empty()) { fprintf(stderr, "k4align: genpba '-M3' calls no SNPs: no SNP file '-S%s'\n", o.snp_file.c_str()); return 1; }
     if (o.given.find('w') == std::string::npos || o.given.find('W') == std::string::npos) {
@@ -1703,6 +1730,21 @@ int main(int argc, char** argv) {
     if (o.snp_nonref_pcnt < 0.1 || o.snp_nonref_pcnt > 35.0) { fprintf(stderr, "k4align: SNP minimum non-ref '-1%f' must be in range 0.1 to 35.0\n", o.snp_nonref_pcnt); return 1; }
     if (o.ml_mode == 5) { fprintf(stderr, "k4align: SNP processing is not supported when reporting all multiloci alignments '-r5'\n"); return 1; }
     if (o.batch_mb > 0 || o.n_shards > 1 || !o.gpus.empty() || o.legacy) { fprintf(stderr, "k4align: SNP calling runs over the whole run's alignments: not with -b, -S i/N, -G, -Z\n"); return 3; }
+  }
+  // marker sequences and SNP centroids (KAlignerCL.cpp:949-983; the range test keeps the reference's precedence: only -K0 means none)
+  if ((o.marker_len != 0 && o.marker_len < 25) || o.marker_len > 500) { fprintf(stderr, "k4align: Marker length specified with '-K%d' must be in range 25 to 500\n", o.marker_len); return 1; }
+  if (o.marker_len) {
+    if (!o.marker_thres_given) o.marker_poly_thres = 1.0 / 3.0;  // cDfltMinMarkerSNPProp
+    if (o.marker_poly_thres < 0.0 || o.marker_poly_thres > 0.50) {
+      fprintf(stderr, "k4align: Max marker sequence base polymorphism specified with '--markerpolythres %1.3f' must be in range 0.0 to 0.5\n", o.marker_poly_thres);
+      return 1;
+    }
+  } else
+    o.marker_poly_thres = 0.0;
+  // (kalign opens both files without SNP calling and leaves them empty; here that is an error)
+  if ((o.marker_len || !o.cent_file.empty()) && o.min_snp_reads == 0) {
+    fprintf(stderr, "k4align: marker sequences '-K' and SNP centroids '-7' are written by SNP calling: give '-p<n>' or '-S<file>'\n");
+    return 1;
   }
   if (o.splice_junct > 0 && o.min_chimeric == 0 && o.min_flank_exacts == 0) o.min_flank_exacts = o.max_subs;  // "force flank trim", :829-830
   if (o.min_flank_exacts > 7) o.min_flank_exacts = 7;

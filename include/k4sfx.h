@@ -279,6 +279,21 @@ int k4_remove_orphan_juncts_dev(k4_index* ix, uint32_t which, int64_t n_reads, i
  *                           NumDnUniques), 0 for win_len 0.  Waits for `stream` and returns the count in *n_dups. */
 int k4_reduce_pcr_dups_dev(k4_index* ix, int32_t win_len, int64_t n_reads, int32_t max_ml, void* d_rr, void* d_hits, int64_t* n_dups,
                            void* stream);
+/* k4_pcr5_primer_correct_dev <- CKAligner::PCR5PrimerCorrect (KAligner.cpp:2115-2226; `kalign -6 <n>`, which aligns with
+ *                           min(MaxSubs + n, 15) substitutions per 100 bp, :245-248, and calls this with the user's MaxSubs behind
+ *                           ReducePCRduplicates and in front of AutoTrimFlanks, :642-651; SE and PE, genpba too): for each accepted
+ *                           one-segment read whose match_len is the read's length and whose low_mm exceeds (max_subs * len + 50) / 100,
+ *                           the bases among its first klen that differ from the target's (the window reverse complemented for a Crick
+ *                           alignment; symbol codes compared, so an N on either side differs) are rewritten in d_reads to the target's
+ *                           symbol, bits 3..7 of the byte kept, in read order until the read is within that bound; low_mm and the
+ *                           hit's mismatches become the bound.  A read the klen bases cannot bring there becomes K4_NAR_NOHIT with
+ *                           num_hits = 0, its bases and inst as they were.  klen: 1..12, kalign always passes 12; klen < 1 does nothing.
+ *                           pe: d_rr_or_pe holds n_reads k4_pe_read records (both ends, read by read; d_hits unused), else
+ *                           k4_read_result with hit slot 0 of d_hits.  Waits for `stream`; counts = reads corrected, bases corrected,
+ *                           reads rejected.  A second call changes nothing. */
+int k4_pcr5_primer_correct_dev(k4_index* ix, int32_t max_subs, int32_t klen, int pe, int64_t n_reads, int32_t max_ml, void* d_rr_or_pe,
+                               void* d_hits, void* d_reads, const void* d_offs, const void* d_lens,
+                               int64_t counts[3] /* reads corrected, bases corrected, reads rejected */, void* stream);
 /* ---- which accepted alignments are kept (`kalign -5 <file>`, `-Z <regex>`, `-z <regex>`; kit4b_amd/csrc/k4_filter.hip) ------------
  * k4_filter_loci_constraints_dev <- CKAligner::IdentifyConstraintViolations (KAligner.cpp:2716-2765; AcceptLociConstraints :2647-2714,
  *                           AcceptBaseConstraint :2598-2645), which kalign runs behind ProcessPairedEnds / AssignMultiMatches and in front

@@ -169,7 +169,7 @@ ABI_SYMBOLS = [
     "k4_copy_to_device", "k4_copy_to_host", "k4_upload_pageable", "k4_host_register", "k4_host_unregister", "k4_best_matches_batch", "k4_best_matches_batch_dev",
     "k4_get_sfx_header", "k4_set_description", "k4_select_hits_dev",
     "k4_assign_multi_dev", "k4_align_reads_ext_batch", "k4_align_reads_ext_batch_dev", "k4_kalign_ext_batch",
-    "k4_kalign_ext_batch_dev", "k4_auto_trim_flanks_dev", "k4_remove_orphan_juncts_dev", "k4_reduce_pcr_dups_dev", "k4_format_sam_ext_dev",
+    "k4_kalign_ext_batch_dev", "k4_auto_trim_flanks_dev", "k4_remove_orphan_juncts_dev", "k4_reduce_pcr_dups_dev", "k4_pcr5_primer_correct_dev", "k4_format_sam_ext_dev",
     "k4_pipeline_open", "k4_pipeline_acquire", "k4_pipeline_submit", "k4_pipeline_submit_host", "k4_pipeline_wait_aligned",
     "k4_pipeline_format", "k4_pipeline_next_sam", "k4_pipeline_read_sam", "k4_pipeline_close", "k4_sfx_map", "k4_sfx_unmap",
     "k4_set_raw_header", "k4_align_stats_collect", "k4_align_stats_dev", "k4_free_align_stats", "k4_write_align_stats",
@@ -250,6 +250,7 @@ def lib():
     L.k4_auto_trim_flanks_dev.argtypes = [vp, C.c_int32, i32, i64, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(C.c_int64), vp]
     L.k4_remove_orphan_juncts_dev.argtypes = [vp, u32, i64, C.c_int32, vp, vp, vp, C.POINTER(C.c_int64), vp]
     L.k4_reduce_pcr_dups_dev.argtypes = [vp, C.c_int32, i64, C.c_int32, vp, vp, C.POINTER(C.c_int64), vp]
+    L.k4_pcr5_primer_correct_dev.argtypes = [vp, C.c_int32, C.c_int32, i32, i64, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(C.c_int64), vp]
     L.k4_align_stats_collect.argtypes = [vp, i32]
     L.k4_align_stats_dev.argtypes = [vp, i32, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, C.POINTER(AlignStats), vp]
     L.k4_free_align_stats.argtypes = [C.POINTER(AlignStats)]
@@ -815,6 +816,18 @@ class SfxIndex:
         ptr = lambda a: a if isinstance(a, int) else a.data_ptr()  # noqa: E731
         self._ck(lib().k4_reduce_pcr_dups_dev(self.h, int(win_len), int(n), int(max_ml), ptr(d_rr), ptr(d_hits), C.byref(c), stream))
         return c.value
+
+    def pcr5_primer_correct(self, max_subs, n, max_ml, d_reads, d_offs, d_lens, d_rr=None, d_hits=None, d_pe=None, klen=12, stream=0):
+        """PCR5PrimerCorrect (`kalign -6`, KAligner.cpp:2115-2226) in place over device arrays (torch tensors or addresses): accepted
+        one-segment full-length reads over (max_subs * len + 50) / 100 mismatches get the mismatching bases among their first klen
+        rewritten in d_reads to the target's until they are within it, or become NAR_NOHIT.  SE d_rr + d_hits (n * max_ml slots), or PE
+        d_pe (n = both ends).  Returns (reads corrected, bases corrected, reads rejected)."""
+        c = (C.c_int64 * 3)()
+        ptr = lambda a: None if a is None else a if isinstance(a, int) else a.data_ptr()  # noqa: E731
+        pe = d_pe is not None
+        self._ck(lib().k4_pcr5_primer_correct_dev(self.h, int(max_subs), int(klen), 1 if pe else 0, int(n), int(max_ml), ptr(d_pe if pe else d_rr),
+                                                  ptr(d_hits), ptr(d_reads), ptr(d_offs), ptr(d_lens), c, stream))
+        return tuple(int(x) for x in c)
 
     def load_loci_constraints(self, path):
         """LoadLociConstraints (`kalign -5 <file>`, KAligner.cpp:1363-1545): the CSV `sequence,start,end,bases` as a LOCI_CONSTRAINT_DTYPE

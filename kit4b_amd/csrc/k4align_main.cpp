@@ -11,6 +11,8 @@
 //   SAM                  CKAligner::WriteBAMReadHits :5718-5914, ReportBAMread :5957-6320, SortHitMatch :10969,
 //                        CSAMfile::AddAlignment libkit4b/SAMfile.cpp:2194-2377 -> k4_format_sam_dev; header :1615,1667-1669,1799
 //   PCR duplicates (-k)  CKAligner::ReducePCRduplicates :2303-2400                -> k4_reduce_pcr_dups_dev
+//   5' primer correction (-6) CKAligner::PCR5PrimerCorrect :2115-2226 (aligned with min(-s + n, 15), :245-248; behind -k, in front of -x)
+//                                                                                  -> k4_pcr5_primer_correct_dev
 //   statistics files (-O) CKAligner::WriteSubDist :6469-6525, WriteBasicCountStats :4159-4300, ReportTargHitCnts :5458-5712,
 //                        the insert size file of ProcessPairedEnds :3092-3146     -> k4_pipeline_align_stats, k4_write_align_stats
 //   loci constraints (-5) CKAligner::LoadLociConstraints :1363-1545, IdentifyConstraintViolations :2716-2765
@@ -19,7 +21,7 @@
 //                                                                                  -> k4_pipeline_site_prefs, k4_write_site_prefs
 //   chromosome filters   CKAligner::FiltByChroms :4025-4091 (kalign -Z / -z; here --chromexclude / --chromeinclude)
 //                                                                                  -> k4_chrom_accept_mask, k4_filter_chroms_dev
-// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k -O -5 -8 -9 (plus -g <gpu>, -S <i/N> read slice);
+// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k -6 -O -5 -8 -9 (plus -g <gpu>, -S <i/N> read slice);
 // kalign's -Z / -z go by their long names --chromexclude / --chromeinclude (the letters mean something else here).
 #include <errno.h>
 #include <fcntl.h>
@@ -61,6 +63,7 @@ struct Opts {
   int min_chimeric = 0, micro_indel = 0, splice_junct = 0, min_flank_exacts = 0;  // -c / -a / -A / -x (KAlignerCL.cpp:237,245,246,267)
   int pcr_win = -1;                 // -k <0..250>: PCR artefact reduction window (KAlignerCL.cpp:222,738-743); -1 = off
   bool pcr_given = false;           // (an explicit -k-1 is turned down like any value outside 0..250)
+  int primer_subs = 0;              // -6 / --pcrprimersubs <0..5>: align with -s + n, then correct 5' primer artefacts back to -s (KAlignerCL.cpp:268,803-815); 0 = off
   std::string loci_file;            // -5 / --lociconstraints <file>: loci base constraints CSV (KAlignerCL.cpp:255)
   std::vector<std::string> chrom_excl, chrom_incl;  // --chromexclude / --chromeinclude <regex>, each repeatable (kalign -Z / -z, KAlignerCL.cpp:274-275)
   std::string stats_file;           // -O <file>: alignment statistics (KAlignerCL.cpp:256) and its two side files
@@ -567,7 +570,7 @@ std::string clean_id(const std::string& raw) {
 void usage() {
   fprintf(stderr,
           "k4align -i reads.f[aq][.gz] [-i more ...] [-u mates ...] -I index.sfx -o out.sam|out.bam [-z bgzf level=6] [-s subs/100bp=5] [-e 1|2] [-m 0..3] [-n maxNs=1]\n"
-          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads | -M3 --experimentid id --readsetid id: packed base alleles to -o, no SAM] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv] [-7 centroids.csv] [-K markerlen 25..500 [--markerpolythres 0..0.5=0.333]]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
+          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads | -M3 --experimentid id --readsetid id: packed base alleles to -o, no SAM] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-6 pcrprimersubs 0..5] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv] [-7 centroids.csv] [-K markerlen 25..500 [--markerpolythres 0..0.5=0.333]]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
 }
 
 }  // namespace
@@ -707,7 +710,9 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
     fprintf(stderr, "k4align: -a / -A drop junctions no second read of the RUN supports; they cannot be combined with -b or -S\n");
     return 1;
   }
-  k4_kalign_params kp = {o.max_subs, o.min_edit, o.max_ns, o.pmode, o.align_strand /* K4_STRAND_*: the same codes as eALStrand */, max_ml,
+  // -6: the reads are aligned with m_InitalAlignSubs (KAligner.cpp:245-248, :504, :607); everything else keeps the user's -s
+  const int align_subs = o.primer_subs > 0 ? std::min(o.max_subs + o.primer_subs, 15) : o.max_subs;
+  k4_kalign_params kp = {align_subs, o.min_edit, o.max_ns, o.pmode, o.align_strand /* K4_STRAND_*: the same codes as eALStrand */, max_ml,
                          o.ml_mode == 5 ? (o.best ? 4 : o.clamp ? 3 : 2) : o.ml_mode == 2 ? 2 : o.ml_mode != 0 ? 1 : 0,
                          mcl, slides, o.min_chimeric, o.micro_indel, o.splice_junct};
   const bool two_seg = o.micro_indel > 0 || o.splice_junct > 0;
@@ -757,6 +762,12 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
     if (!pe && o.pcr_win >= 0) {  // ReducePCRduplicates, behind AssignMultiMatches and before the filters (KAligner.cpp:628-640)
       CK(k4_reduce_pcr_dups_dev(ix, o.pcr_win, n, max_ml, d_rr, d_hits, &cnt, nullptr));
       fprintf(stderr, "k4align: %lld potential PCR artefact reads removed\n", (long long)cnt);
+    }
+    if (o.primer_subs > 0) {  // PCR5PrimerCorrect, behind ReducePCRduplicates and in front of AutoTrimFlanks, SE and PE (KAligner.cpp:642-651)
+      int64_t c3[3] = {0, 0, 0};
+      CK(k4_pcr5_primer_correct_dev(ix, o.max_subs, 12, pe ? 1 : 0, pe ? 2 * n : n, max_ml, pe ? d_pe : d_rr, d_hits, d_reads, d_offs, d_lens, c3, nullptr));
+      fprintf(stderr, "k4align: PCR 5' primer correction: %lld reads with %lld bases corrected, %lld reads with excessive substitutions rejected\n",
+              (long long)c3[0], (long long)c3[1], (long long)c3[2]);
     }
     // the filters, in CKAligner::Align's order (KAligner.cpp:653-686)
     if (o.min_flank_exacts > 0) {
@@ -1522,6 +1533,7 @@ int main(int argc, char** argv) {
         if (name == "chromexclude") o.chrom_excl.push_back(v);
         else if (name == "chromeinclude") o.chrom_incl.push_back(v);
         else if (name == "lociconstraints") { o.loci_file = v; o.given += '5'; }
+        else if (name == "pcrprimersubs") { o.primer_subs = atoi(v.c_str()); o.given += '6'; }
         else if (name == "siteprefs") { o.site_file = v; o.given += '8'; }
         else if (name == "siteprefsofs") { o.site_ofs = atoi(v.c_str()); o.given += '9'; }
         else if (name == "snpcentroid") { o.cent_file = v; o.given += '7'; }
@@ -1533,6 +1545,7 @@ int main(int argc, char** argv) {
         break;
       }
       case '5': o.loci_file = val(); break;
+      case '6': o.primer_subs = atoi(val().c_str()); break;
       case 'i': o.in1.push_back(val()); break;
       case 'u': o.in2.push_back(val()); break;
       case 'I': o.sfx = val(); break;
@@ -1666,6 +1679,19 @@ int main(int argc, char** argv) {
       return 1;
     }
     if (o.ml_mode == 5) { fprintf(stderr, "k4align: PCR artefact reduction '-k' with every multiloci alignment reported '-r5' is not built\n"); return 3; }
+  }
+  // -6 (KAlignerCL.cpp:803-815; genpba :1975-1987).  The stage looks at one read at a time: it runs with -b, -S i/N and -G as well
+  if (o.primer_subs < 0 || o.primer_subs > 5) {
+    fprintf(stderr, "k4align: PCR primer correction subs '-6%d' specified outside of range 0..5\n", o.primer_subs);
+    return 1;
+  }
+  if (o.primer_subs != 0 && o.min_chimeric != 0) {
+    fprintf(stderr, "k4align: PCR primer correction subs not allowed when also specifying chimeric trimming\n");
+    return 1;
+  }
+  if (o.primer_subs > 0 && o.ml_mode == 5) {  // (there every reported locus is a read of its own to the reference)
+    fprintf(stderr, "k4align: PCR primer correction '-6' with every multiloci alignment reported '-r5' is not built\n");
+    return 3;
   }
   // the statistics count over all reads of the run in one place (summing per-rank counters is not built)
   if (!o.stats_file.empty()) {

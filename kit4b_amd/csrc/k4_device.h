@@ -243,3 +243,50 @@ K4_DEV uint32_t k4d_mm_count(uint64_t x) {  // mismatching bases in a XOR of two
   uint64_t y = (x | (x >> 1)) & 0x5555555555555555ull;
   return (uint32_t)__popcll(y);
 }
+
+// The records a stage behind the aligner works on, in either form (a stage's host side fills it with k4s_read_set, k4_stage.h):
+//   SE  rr[i] and the read's max_ml hit slots hits[i * max_ml ..], slot 0 the reported hit; seg2[i] where the hit has two segments
+//   PE  pr[i] with the hit inside, mates at 2q and 2q + 1; rr, hits and seg2 are null
+// pr != nullptr tells the two apart.  Passed to kernels by value; a stage that only reads takes it `const`, and the accessors that
+// write are the non-const ones.
+struct K4ReadSet {
+  k4_read_result* rr;
+  k4_hit* hits;
+  k4_pe_read* pr;
+  int max_ml;
+  const k4_seg2* seg2;
+  uint8_t* reads;        // the read bytes, read i at reads + offs[i], lens[i] of them
+  const uint64_t* offs;
+  const uint32_t* lens;
+  int64_t n_reads;       // SE reads or 2 x pairs
+
+  K4_DEV bool pe() const { return pr != nullptr; }
+  K4_DEV int nar(int64_t i) const { return pr ? pr[i].nar : rr[i].nar; }
+  K4_DEV k4_hit hit(int64_t i) const { return pr ? pr[i].hit : hits[i * max_ml]; }
+  K4_DEV k4_hit* hit_ptr(int64_t i) { return pr ? &pr[i].hit : &hits[i * max_ml]; }
+  // accepted, and then h = the reported hit
+  K4_DEV bool accepted(int64_t i, k4_hit& h) const {
+    if (pr) {
+      if (pr[i].nar != K4_NAR_ACCEPTED) return false;
+      h = pr[i].hit;
+      return true;
+    }
+    if (rr[i].nar != K4_NAR_ACCEPTED) return false;
+    h = hits[i * max_ml];
+    return true;
+  }
+  K4_DEV int low_mm(int64_t i) const { return pr ? pr[i].low_mm : rr[i].low_mm; }
+  K4_DEV void set_low_mm(int64_t i, int v) {
+    if (pr) pr[i].low_mm = v; else rr[i].low_mm = v;
+  }
+  // Taking read i out of the report: NAR = nar and NumHits = 0; LowHitInstances = 0 as well where the reference's stage clears it
+  // (DESIGN.md "Where a stage reads and rejects records" has the table).  The hit itself stays as it was.
+  K4_DEV void reject(int64_t i, int nar, bool clear_inst) {
+    if (pr) { pr[i].nar = nar; pr[i].num_hits = 0; if (clear_inst) pr[i].inst = 0; }
+    else { rr[i].nar = nar; rr[i].num_hits = 0; if (clear_inst) rr[i].inst = 0; }
+  }
+  // ... NumHits = 0 alone: the NAR stays
+  K4_DEV void drop_hits(int64_t i) {
+    if (pr) pr[i].num_hits = 0; else rr[i].num_hits = 0;
+  }
+};

@@ -58,10 +58,8 @@ K4_DEV uint32_t k4d_first_ge(const uint32_t* a, uint32_t lo, uint32_t hi, uint32
 // The table as the host lays it out (32-bit words): start[n] | end[n] | running max of end within the sequence [n] |
 // {sequence id, first, one past last}[nc] | the constraint bytes, four to a word.
 __global__ void __launch_bounds__(K4_FILTER_THREADS)
-k4k_filter_loci(K4DevIndex ix, const uint32_t* __restrict__ g_tab, uint32_t n_c, uint32_t n_ch, uint32_t tab_words, int64_t n_reads,
-                int max_ml, k4_read_result* __restrict__ rr, const k4_hit* __restrict__ hits, const k4_seg2* __restrict__ seg2,
-                k4_pe_read* __restrict__ pr, const uint8_t* __restrict__ reads, const uint64_t* __restrict__ offs,
-                const uint32_t* __restrict__ lens, unsigned long long* __restrict__ n_marked) {
+k4k_filter_loci(K4DevIndex ix, const uint32_t* __restrict__ g_tab, uint32_t n_c, uint32_t n_ch, uint32_t tab_words, K4ReadSet rs,
+                unsigned long long* __restrict__ n_marked) {
   extern __shared__ uint32_t lds[];
   for (uint32_t k = threadIdx.x; k < tab_words; k += K4_FILTER_THREADS) lds[k] = g_tab[k];
   __syncthreads();
@@ -73,6 +71,7 @@ k4k_filter_loci(K4DevIndex ix, const uint32_t* __restrict__ g_tab, uint32_t n_c,
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * (K4_FILTER_THREADS / 64) + (threadIdx.x >> 6);
   const int64_t n_waves = (int64_t)gridDim.x * (K4_FILTER_THREADS / 64);
+  const int64_t n_reads = rs.n_reads;
   uint32_t marked = 0;
   for (int64_t base = wave * 64; base < n_reads; base += n_waves * 64) {  // (base is wave-uniform: the wave stays together)
     const int64_t i = base + lane;
@@ -82,9 +81,9 @@ k4k_filter_loci(K4DevIndex ix, const uint32_t* __restrict__ g_tab, uint32_t n_c,
     uint32_t seg_s[2] = {0, 0}, seg_e[2] = {0, 0}, seg_q[2] = {0, 0}, seg_k0[2] = {0, 0}, seg_k1[2] = {0, 0};
     uint32_t rlen = 0, off_lo = 0, off_hi = 0;
     if (i < n_reads) {
-      nar = pr ? pr[i].nar : rr[i].nar;
+      nar = rs.nar(i);
       if (nar == K4_NAR_ACCEPTED) {
-        h = pr ? pr[i].hit : hits[i * max_ml];
+        h = rs.hit(i);
         uint32_t lo = 0, hi = n_ch;  // the sequence among the constrained ones (m_ConstrainedChromIDs)
         while (lo < hi) {
           const uint32_t mid = (lo + hi) >> 1;
@@ -100,8 +99,8 @@ k4k_filter_loci(K4DevIndex ix, const uint32_t* __restrict__ g_tab, uint32_t n_c,
             seg_k1[0] = k4d_first_gt(c_start, t_lo, t_hi, seg_e[0]);
             seg_k0[0] = k4d_first_ge(c_pmax, t_lo, seg_k1[0], seg_s[0]);
           }
-          if ((h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE)) && seg2 && !pr) {  // FlagSegs: Seg[1] (no trims of its own)
-            const k4_seg2 s2 = seg2[i];
+          if ((h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE)) && rs.seg2) {  // FlagSegs: Seg[1] (no trims of its own)
+            const k4_seg2 s2 = rs.seg2[i];
             if (s2.match_len) {
               seg_s[1] = s2.match_loci;
               seg_e[1] = s2.match_loci + (uint32_t)s2.match_len - 1u;
@@ -111,9 +110,9 @@ k4k_filter_loci(K4DevIndex ix, const uint32_t* __restrict__ g_tab, uint32_t n_c,
             }
           }
           if (seg_k0[0] < seg_k1[0] || seg_k0[1] < seg_k1[1]) {
-            const uint64_t o = offs[i];
+            const uint64_t o = rs.offs[i];
             off_lo = (uint32_t)o; off_hi = (uint32_t)(o >> 32);
-            rlen = lens[i];
+            rlen = rs.lens[i];
           }
         }
       }
@@ -125,7 +124,7 @@ k4k_filter_loci(K4DevIndex ix, const uint32_t* __restrict__ g_tab, uint32_t n_c,
       const int src = __ffsll((long long)todo) - 1;
       todo &= todo - 1;
       const uint32_t b_len = __shfl(rlen, src, 64);
-      const uint8_t* rd = reads + (((uint64_t)__shfl(off_hi, src, 64) << 32) | __shfl(off_lo, src, 64));
+      const uint8_t* rd = rs.reads + (((uint64_t)__shfl(off_hi, src, 64) << 32) | __shfl(off_lo, src, 64));
       const bool b_minus = __shfl((int)h.strand, src, 64) == '-';
       const uint64_t b_cs = ix.ent_start[__shfl(h.chrom_id, src, 64) - 1];
       bool fail = false;
@@ -159,16 +158,13 @@ k4k_filter_loci(K4DevIndex ix, const uint32_t* __restrict__ g_tab, uint32_t n_c,
     }
     // ---- the marks: every lane its own record; PE mates are lanes 2q, 2q + 1
     bool lc = viol;
-    if (pr) {
+    if (rs.pe()) {
       lc = lc || nar == K4_NAR_LOCICONSTRAINED;
       const int mate = __shfl_xor((int)lc, 1, 64);  // (every lane takes part: no short circuit in front of the shuffle)
       lc = lc || mate != 0;
     }
     const bool fresh = lc && i < n_reads && nar != K4_NAR_LOCICONSTRAINED;
-    if (fresh) {
-      if (pr) { pr[i].nar = K4_NAR_LOCICONSTRAINED; pr[i].num_hits = 0; pr[i].inst = 0; }
-      else { rr[i].nar = K4_NAR_LOCICONSTRAINED; rr[i].num_hits = 0; rr[i].inst = 0; }
-    }
+    if (fresh) rs.reject(i, K4_NAR_LOCICONSTRAINED, true);  // NAR, NumHits and LowHitInstances (:2736-2738, the mate :2753-2755)
     // (PE: a mate that was not accepted is tallied by the NAR it loses; few of them)
     if (fresh && nar != K4_NAR_ACCEPTED && nar >= 0 && nar < 20) atomicAdd(n_marked + 1 + nar, 1ull);
     marked += (uint32_t)__popcll(__ballot(fresh));
@@ -177,26 +173,22 @@ k4k_filter_loci(K4DevIndex ix, const uint32_t* __restrict__ g_tab, uint32_t n_c,
 }
 
 // FiltByChroms: an accepted read on a sequence the expressions reject
-__global__ void __launch_bounds__(256) k4k_filter_chroms(uint32_t n_entries, const uint8_t* __restrict__ accept, int64_t n_reads, int max_ml,
-                                                         k4_read_result* __restrict__ rr, const k4_hit* __restrict__ hits,
-                                                         k4_pe_read* __restrict__ pr, unsigned long long* __restrict__ n_marked) {
+__global__ void __launch_bounds__(256) k4k_filter_chroms(uint32_t n_entries, const uint8_t* __restrict__ accept, K4ReadSet rs,
+                                                         unsigned long long* __restrict__ n_marked) {
   const int lane = threadIdx.x & 63;
   const int64_t stride = (int64_t)gridDim.x * 256;
+  const int64_t n_reads = rs.n_reads;
   uint32_t marked = 0;
   for (int64_t base = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63); base < n_reads; base += stride) {
     const int64_t i = base + lane;
     bool drop = false;
     if (i < n_reads) {
-      const int32_t nar = pr ? pr[i].nar : rr[i].nar;
-      if (nar == K4_NAR_ACCEPTED) {
-        const uint32_t c = pr ? pr[i].hit.chrom_id : hits[i * max_ml].chrom_id;
+      if (rs.nar(i) == K4_NAR_ACCEPTED) {
+        const uint32_t c = rs.hit(i).chrom_id;
         drop = c >= 1 && c <= n_entries && accept[c] == 0;
       }
     }
-    if (drop) {
-      if (pr) { pr[i].nar = K4_NAR_CHROMFILT; pr[i].num_hits = 0; pr[i].inst = 0; }
-      else { rr[i].nar = K4_NAR_CHROMFILT; rr[i].num_hits = 0; rr[i].inst = 0; }
-    }
+    if (drop) rs.reject(i, K4_NAR_CHROMFILT, true);  // NAR, NumHits and LowHitInstances (:4058-4060, :4074-4076)
     marked += (uint32_t)__popcll(__ballot(drop));
   }
   if (lane == 0 && marked) atomicAdd(n_marked, (unsigned long long)marked);
@@ -215,15 +207,16 @@ extern "C" int k4_filter_chroms_dev(k4_index* ix, const void* d_accept, int pe, 
   if (!ix) return K4_ERR_PARAMS;
   if (n_removed) *n_removed = 0;
   if (n_reads <= 0) return K4_OK;
-  if (!d_accept || !d_rr_or_pe || (!pe && (!d_hits || max_ml < 1))) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
+  K4ReadSet rs;
+  K4_TRY(k4s_read_set(ix, pe, n_reads, d_rr_or_pe, d_hits, max_ml, d_rr_or_pe, nullptr, nullptr, nullptr, nullptr, K4RS_HITS, &rs));
+  if (!d_accept) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
   K4DevBuf cnt;
   K4_HIP(ix, cnt.alloc(8));
   K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 8, st));
   const int64_t blocks = std::min<int64_t>((n_reads + 255) / 256, grid_for(ix->device, 8));
-  hipLaunchKernelGGL(k4k_filter_chroms, dim3((unsigned)blocks), dim3(256), 0, st, ix->d.n_entries, (const uint8_t*)d_accept, n_reads, (int)max_ml,
-                     pe ? nullptr : (k4_read_result*)d_rr_or_pe, (const k4_hit*)d_hits, pe ? (k4_pe_read*)d_rr_or_pe : nullptr,
+  hipLaunchKernelGGL(k4k_filter_chroms, dim3((unsigned)blocks), dim3(256), 0, st, ix->d.n_entries, (const uint8_t*)d_accept, rs,
                      cnt.as<unsigned long long>());
   K4_HIP(ix, hipGetLastError());
   unsigned long long c = 0;
@@ -248,7 +241,9 @@ extern "C" int k4_filter_loci_constraints_dev(k4_index* ix, const k4_loci_constr
   if (n_constraints < 0 || n_constraints > K4_MAX_CONSTRAINED_LOCI)
     return k4_fail(ix, K4_ERR_PARAMS, "%d loci base constraints, at most %d are allowed", (int)n_constraints, K4_MAX_CONSTRAINED_LOCI);
   if (n_constraints == 0 || n_units <= 0) return K4_OK;  // "there may be no constraints!"
-  if (!constraints || !d_reads || !d_offs || !d_lens || (pe ? !d_pe : (!d_rr || !d_hits || max_ml < 1))) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
+  K4ReadSet rs;
+  K4_TRY(k4s_read_set(ix, pe, n_units, d_rr, d_hits, max_ml, d_pe, d_seg2, d_reads, d_offs, d_lens, K4RS_HITS | K4RS_READS | K4RS_UNITS, &rs));
+  if (!constraints) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
   // the table: checked, sorted by (sequence, start, end) as the reference sorts it, with the running maximum of `end`
   std::vector<k4_loci_constraint> t(constraints, constraints + n_constraints);
   for (const k4_loci_constraint& c : t) {
@@ -286,11 +281,8 @@ extern "C" int k4_filter_loci_constraints_dev(k4_index* ix, const k4_loci_constr
   K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 8 * 21, st));
   const size_t lds = (size_t)words * 4;  // at most 84 KB of the CU's 160
   K4_HIP(ix, hipFuncSetAttribute((const void*)k4k_filter_loci, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t n_reads = pe ? 2 * n_units : n_units;
-  const int64_t blocks = std::min<int64_t>((n_reads + K4_FILTER_THREADS - 1) / K4_FILTER_THREADS, grid_for(ix->device, 1));
-  hipLaunchKernelGGL(k4k_filter_loci, dim3((unsigned)blocks), dim3(K4_FILTER_THREADS), lds, st, ix->d, d_tab.as<uint32_t>(), n, nc, words, n_reads,
-                     (int)max_ml, pe ? nullptr : (k4_read_result*)d_rr, (const k4_hit*)d_hits, pe ? nullptr : (const k4_seg2*)d_seg2,
-                     pe ? (k4_pe_read*)d_pe : nullptr, (const uint8_t*)d_reads, (const uint64_t*)d_offs, (const uint32_t*)d_lens,
+  const int64_t blocks = std::min<int64_t>((rs.n_reads + K4_FILTER_THREADS - 1) / K4_FILTER_THREADS, grid_for(ix->device, 1));
+  hipLaunchKernelGGL(k4k_filter_loci, dim3((unsigned)blocks), dim3(K4_FILTER_THREADS), lds, st, ix->d, d_tab.as<uint32_t>(), n, nc, words, rs,
                      cnt.as<unsigned long long>());
   K4_HIP(ix, hipGetLastError());
   unsigned long long c[21];

@@ -469,16 +469,7 @@ extern "C" int k4_prepare_reads_trim_dev(k4_index* ix, int pe, int64_t n, int32_
 namespace {
 
 struct K4SamArgs {
-  int pe;                       // 0: SE (rr + hits), 1: PE (k4_pe_read per read, reads interleaved)
-  int64_t n_reads;              // SE reads or 2 * pairs
-  const k4_read_result* rr;
-  const k4_hit* hits;
-  int max_ml;
-  const k4_pe_read* pr;
-  const k4_seg2* seg2;          // SE: second segments of microInDel / splice hits, one per read, or null
-  const uint8_t* reads;
-  const uint64_t* offs;
-  const uint32_t* lens;
+  K4ReadSet rs;                 // (read only; PE: the reads are interleaved; seg2 may be null)
   const uint8_t* text[2];
   const uint64_t* name_off[2];
   const uint32_t* name_len[2];
@@ -490,35 +481,40 @@ struct K4SamArgs {
   int quals;                    // kalign -g0..2: bits 4..7 of the read bytes hold 4-bit scores; QUAL is written from them (KAligner.cpp:6120-6145)
 };
 #define K4_SAM_NAME_STRIDE 96
+// the name buffers of the file(s) the reads came from
+bool sam_names_given(const k4_sam_names* n, int pe) {
+  for (int w = 0; w < (pe ? 2 : 1); w++)
+    if (!n->d_text[w] || !n->d_name_off[w] || !n->d_name_len[w]) return false;
+  return true;
+}
 
 // does read i carry any non-zero score?  (SumScores of ReportBAMread: none -> QUAL `*` / 0xff)
 K4_DEV bool k4d_sam_has_qual(const K4SamArgs& a, int64_t i) {
   if (!a.quals) return false;
-  const uint8_t* s = a.reads + a.offs[i];
-  const uint32_t len = a.lens[i];
+  const uint8_t* s = a.rs.reads + a.rs.offs[i];
+  const uint32_t len = a.rs.lens[i];
   uint32_t acc = 0;
   for (uint32_t q = 0; q < len; q++) acc |= s[q];
   return (acc & 0xF0u) != 0;
 }
 // A SAM line is addressed by v = read * vm + instance (vm = max_ml for SE, 1 for PE): with MLMode eMLall a read with
 // NumHits instances yields that many lines (CKAligner::WriteHitLoci, KAligner.cpp:6922-6990).
-K4_DEV int k4d_sam_nar(const K4SamArgs& a, int64_t i) { return a.pe ? a.pr[i].nar : a.rr[i].nar; }
-K4_DEV int64_t k4d_sam_read(const K4SamArgs& a, int64_t v) { return a.pe ? v : v / a.max_ml; }
-K4_DEV k4_hit k4d_sam_hit(const K4SamArgs& a, int64_t v) { return a.pe ? a.pr[v].hit : a.hits[v]; }
+K4_DEV int64_t k4d_sam_read(const K4SamArgs& a, int64_t v) { return a.rs.pe() ? v : v / a.rs.max_ml; }
+K4_DEV k4_hit k4d_sam_hit(const K4SamArgs& a, int64_t v) { return a.rs.pe() ? a.rs.pr[v].hit : a.rs.hits[v]; }  // (instance v, not slot 0)
 K4_DEV bool k4d_sam_reported(const K4SamArgs& a, int64_t v) {
-  if (a.pe) return a.pr[v].nar == K4_NAR_ACCEPTED || (a.all_reads && a.lens[v] != 0);
-  const int64_t i = v / a.max_ml;
-  const k4_read_result r = a.rr[i];
-  if (r.nar != K4_NAR_ACCEPTED) return a.all_reads && v == i * a.max_ml && a.lens[i] != 0;  // one record, if the read was loaded
-  return (int)(v - i * a.max_ml) < max(r.num_hits, 1);
+  if (a.rs.pe()) return a.rs.pr[v].nar == K4_NAR_ACCEPTED || (a.all_reads && a.rs.lens[v] != 0);
+  const int64_t i = v / a.rs.max_ml;
+  const k4_read_result r = a.rs.rr[i];
+  if (r.nar != K4_NAR_ACCEPTED) return a.all_reads && v == i * a.rs.max_ml && a.rs.lens[i] != 0;  // one record, if the read was loaded
+  return (int)(v - i * a.rs.max_ml) < max(r.num_hits, 1);
 }
 // a line of a read that was not accepted (only with all_reads)
-K4_DEV bool k4d_sam_unaligned(const K4SamArgs& a, int64_t v) { return a.all_reads && k4d_sam_nar(a, k4d_sam_read(a, v)) != K4_NAR_ACCEPTED; }
+K4_DEV bool k4d_sam_unaligned(const K4SamArgs& a, int64_t v) { return a.all_reads && a.rs.nar(k4d_sam_read(a, v)) != K4_NAR_ACCEPTED; }
 // the unaligned record of `-M1` (ReportBAMread's last branch, KAligner.cpp:6253-6276, as CSAMfile::AddAlignment prints it):
 //   QNAME FLAG * 0 128 <len>M * 0 0 SEQ * <empty> YU:Z:<NAR code>     FLAG: 4, PE: 1 | 2 | 64 / 128 | 4 and the mate's 8 or 32
 K4_DEV uint32_t k4d_sam_unaligned_flag(const K4SamArgs& a, int64_t i) {
-  if (!a.pe) return 0x4u;
-  const k4_pe_read me = a.pr[i], mt = a.pr[i ^ 1];
+  if (!a.rs.pe()) return 0x4u;
+  const k4_pe_read me = a.rs.pr[i], mt = a.rs.pr[i ^ 1];
   uint32_t f = 0x1u | 0x2u | ((i & 1) ? 0x80u : 0x40u) | 0x4u;
   if (me.pe_aligned && mt.pe_aligned && mt.nar == K4_NAR_ACCEPTED) f |= mt.hit.strand != '+' ? 0x20u : 0u;
   else f |= 0x8u;
@@ -539,15 +535,15 @@ struct K4SamFields {
 K4_DEV bool k4d_two_segs(const k4_hit& h) { return (h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE)) != 0; }
 K4_DEV k4_seg2 k4d_sam_seg2(const K4SamArgs& a, int64_t i, const k4_hit& h) {
   k4_seg2 z = {0, 0, 0, 0, 0, 0, 0};
-  return (!a.pe && a.seg2 && k4d_two_segs(h)) ? a.seg2[i] : z;
+  return (!a.rs.pe() && a.rs.seg2 && k4d_two_segs(h)) ? a.rs.seg2[i] : z;
 }
 // ReportBAMread (KAligner.cpp:6041-6251): FLAG, POS, CIGAR, MAPQ = max(1, M * aligned / readlen) with M = 254, less 20 for
 // a splice junction and 10 for a microInDel, mate fields
 K4_DEV K4SamFields k4d_sam_fields(const K4SamArgs& a, int64_t v, const k4_hit& h) {
   const int64_t i = k4d_sam_read(a, v);
   K4SamFields f;
-  const uint32_t rl = a.lens[i];
-  const bool two = !a.pe && a.seg2 && k4d_two_segs(h);
+  const uint32_t rl = a.rs.lens[i];
+  const bool two = !a.rs.pe() && a.rs.seg2 && k4d_two_segs(h);
   const k4_seg2 s2 = k4d_sam_seg2(a, i, h);
   const uint32_t tl = K4_HIT_TRIM_LEFT(h), tr = K4_HIT_TRIM_RIGHT(h);
   const uint32_t len0 = k4d_adj_len(h), len1 = two ? s2.match_len : 0u;
@@ -575,11 +571,11 @@ K4_DEV K4SamFields k4d_sam_fields(const K4SamArgs& a, int64_t v, const k4_hit& h
   f.pnext = 0;
   f.tlen = 0;
   f.mate_eq = false;
-  if (!a.pe) {
+  if (!a.rs.pe()) {
     f.flag = h.strand == '+' ? 0u : 0x10u;
     return f;
   }
-  const k4_pe_read me = a.pr[i], mt = a.pr[i ^ 1];
+  const k4_pe_read me = a.rs.pr[i], mt = a.rs.pr[i ^ 1];
   f.flag = 0x1u | 0x2u | ((i & 1) ? 0x80u : 0x40u) | (h.strand == '+' ? 0u : 0x10u);
   if (me.pe_aligned && mt.pe_aligned && mt.nar == K4_NAR_ACCEPTED) {
     if (mt.hit.strand != '+') f.flag |= 0x20u;
@@ -616,14 +612,14 @@ __global__ void __launch_bounds__(256) k4k_sam_key_minor(K4SamArgs a, const uint
   const k4_hit h = k4d_sam_hit(a, v);
   // AdjHitLen(Seg[0]), Strand, then the READ's LowMMCnt (both segments' mismatches for a two-segment hit)
   const int64_t i = k4d_sam_read(a, v);
-  const uint32_t mm = a.pe ? h.mismatches : (k4d_two_segs(h) ? (uint32_t)a.rr[i].low_mm & 0xFFu : h.mismatches);
+  const uint32_t mm = a.rs.pe() ? h.mismatches : (k4d_two_segs(h) ? (uint32_t)a.rs.rr[i].low_mm & 0xFFu : h.mismatches);
   key[j] = (k4d_adj_len(h) << 16) | ((uint32_t)h.strand << 8) | mm;
 }
 __global__ void __launch_bounds__(256) k4k_sam_key_major(K4SamArgs a, const uint32_t* __restrict__ idx, uint64_t m, uint64_t* __restrict__ key) {
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= m) return;
   if (k4d_sam_unaligned(a, idx[j])) {  // behind every accepted alignment, by NAR (SortHitMatch: NAR first; accepted is the lowest in use)
-    const int nar = k4d_sam_nar(a, k4d_sam_read(a, idx[j]));
+    const int nar = a.rs.nar(k4d_sam_read(a, idx[j]));
     key[j] = (uint64_t)(a.n_entries + 1u + (uint32_t)(nar & 31)) << 32;
     return;
   }
@@ -637,12 +633,12 @@ __global__ void __launch_bounds__(256) k4k_sam_stats(K4SamArgs a, unsigned long 
   if (threadIdx.x < 22) h[threadIdx.x] = 0;
   __syncthreads();
   const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n_reads; i += stride) {
-    if (a.lens[i] == 0) continue;  // a slot whose read was not loaded (under / over length)
-    const int nar = k4d_sam_nar(a, i);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.rs.n_reads; i += stride) {
+    if (a.rs.lens[i] == 0) continue;  // a slot whose read was not loaded (under / over length)
+    const int nar = a.rs.nar(i);
     atomicAdd(&h[nar >= 0 && nar < 20 ? nar : 0], 1u);
     if (nar == K4_NAR_ACCEPTED) {
-      const int vm = a.pe ? 1 : a.max_ml;
+      const int vm = a.rs.pe() ? 1 : a.rs.max_ml;
       for (int q = 0; q < vm; q++) {
         if (!k4d_sam_reported(a, i * vm + q)) break;
         const k4_hit hh = k4d_sam_hit(a, i * vm + q);
@@ -658,22 +654,22 @@ __global__ void __launch_bounds__(256) k4k_sam_stats(K4SamArgs a, unsigned long 
 K4_DEV uint32_t k4d_sam_line_len(const K4SamArgs& a, int64_t v) {
   if (k4d_sam_unaligned(a, v)) {
     const int64_t i = k4d_sam_read(a, v);
-    const int w = a.pe ? (int)(i & 1) : 0;
-    const int64_t rec = a.pe ? (i >> 1) : i;
+    const int w = a.rs.pe() ? (int)(i & 1) : 0;
+    const int64_t rec = a.rs.pe() ? (i >> 1) : i;
     return a.name_len[w][rec] + 1 + k4d_udigits(k4d_sam_unaligned_flag(a, i)) + 1 + 2 /* "*\t" */ + 2 /* "0\t" */ + 4 /* "128\t" */ +
-           k4d_udigits(a.lens[i]) + 2 /* "M\t" */ + 2 /* "*\t" */ + 2 + 2 /* "0\t0\t" */ + a.lens[i] + K4_SAM_UNALIGNED_TAIL +
-           (k4d_sam_has_qual(a, i) ? a.lens[i] - 1 : 0);
+           k4d_udigits(a.rs.lens[i]) + 2 /* "M\t" */ + 2 /* "*\t" */ + 2 + 2 /* "0\t0\t" */ + a.rs.lens[i] + K4_SAM_UNALIGNED_TAIL +
+           (k4d_sam_has_qual(a, i) ? a.rs.lens[i] - 1 : 0);
   }
   const k4_hit h = k4d_sam_hit(a, v);
   const K4SamFields f = k4d_sam_fields(a, v, h);
   const int64_t i = k4d_sam_read(a, v);
-  const int w = a.pe ? (int)(i & 1) : 0;
-  const int64_t rec = a.pe ? (i >> 1) : i;
+  const int w = a.rs.pe() ? (int)(i & 1) : 0;
+  const int64_t rec = a.rs.pe() ? (i >> 1) : i;
   uint32_t n = a.name_len[w][rec] + 1 + k4d_udigits(f.flag) + 1 + a.cname_len[h.chrom_id - 1] + 1 + k4d_udigits(f.pos) + 1 +
                k4d_udigits(f.mapq) + 1 + 1 + 1 /*RNEXT*/ + 1 + k4d_udigits(f.pnext) + 1;
   for (uint32_t q = 0; q < f.n_ops; q++) n += k4d_udigits(f.op_len[q]) + 1;
   n += (f.tlen < 0 ? 1 : 0) + k4d_udigits((uint32_t)(f.tlen < 0 ? -(int64_t)f.tlen : f.tlen)) + 1;
-  n += a.lens[i] + 1 + (k4d_sam_has_qual(a, i) ? a.lens[i] : 1 /* '*' */) + 1 /* '\n' */;
+  n += a.rs.lens[i] + 1 + (k4d_sam_has_qual(a, i) ? a.rs.lens[i] : 1 /* '*' */) + 1 /* '\n' */;
   return n;
 }
 // the same alignment as a BAM record (CSAMfile::AddAlignment's BAM branch, SAMfile.cpp:2379-2640, over ReportBAMread's fields):
@@ -681,15 +677,15 @@ K4_DEV uint32_t k4d_sam_line_len(const K4SamArgs& a, int64_t v) {
 #define K4_BAM_UNALIGNED_AUX 6  // 'Y' 'U' 'Z' + the two-letter NAR code + NUL
 K4_DEV uint32_t k4d_bam_n_ops(const K4SamArgs& a, int64_t v, const k4_hit& h) {
   const uint32_t tl = K4_HIT_TRIM_LEFT(h), tr = K4_HIT_TRIM_RIGHT(h);
-  const bool two = !a.pe && a.seg2 && k4d_two_segs(h);
+  const bool two = !a.rs.pe() && a.rs.seg2 && k4d_two_segs(h);
   return 1u + (tl ? 1u : 0u) + (tr ? 1u : 0u) + (two ? 2u : 0u);
 }
 K4_DEV uint32_t k4d_bam_rec_len(const K4SamArgs& a, int64_t v) {
   const k4_hit h = k4d_sam_hit(a, v);
   const int64_t i = k4d_sam_read(a, v);
-  const int w = a.pe ? (int)(i & 1) : 0;
-  const int64_t rec = a.pe ? (i >> 1) : i;
-  const uint32_t len = a.lens[i];
+  const int w = a.rs.pe() ? (int)(i & 1) : 0;
+  const int64_t rec = a.rs.pe() ? (i >> 1) : i;
+  const uint32_t len = a.rs.lens[i];
   if (k4d_sam_unaligned(a, v)) return 4u + 32u + a.name_len[w][rec] + 1u + 4u + (len + 1) / 2 + len + K4_BAM_UNALIGNED_AUX;
   return 4u + 32u + a.name_len[w][rec] + 1u + 4u * k4d_bam_n_ops(a, v, h) + (len + 1) / 2 + len;
 }
@@ -711,15 +707,15 @@ K4_DEV uint32_t k4d_bam_reg2bin(int32_t beg, int32_t end) {
 K4_DEV void k4d_put_le32(char* p, uint32_t v) { p[0] = (char)v; p[1] = (char)(v >> 8); p[2] = (char)(v >> 16); p[3] = (char)(v >> 24); }
 // one record (or sub-lane `sub`'s share of its sequence and quality bytes) at `line`
 K4_DEV void k4d_bam_put_rec(const K4SamArgs& a, int64_t v, const k4_hit& h, int64_t i, char* line, uint32_t line_len, int sub, int lpl) {
-  const uint32_t len = a.lens[i];
+  const uint32_t len = a.rs.lens[i];
   const uint32_t nseq = (len + 1) / 2;
   const bool unal = k4d_sam_unaligned(a, v);
   const uint32_t aux = unal ? K4_BAM_UNALIGNED_AUX : 0u;
   char* seq = line + line_len - aux - len - nseq;
   char* qual = line + line_len - aux - len;
   if (sub == 0 && unal) {  // ReportBAMread's unaligned branch (KAligner.cpp:6253-6276): refID / pos / mate -1, bin 0, MAPQ 128, <len>M, YU:Z:<NAR>
-    const int w = a.pe ? (int)(i & 1) : 0;
-    const int64_t rec = a.pe ? (i >> 1) : i;
+    const int w = a.rs.pe() ? (int)(i & 1) : 0;
+    const int64_t rec = a.rs.pe() ? (i >> 1) : i;
     const uint32_t nl_ = a.name_len[w][rec];
     k4d_put_le32(line, line_len - 4);
     k4d_put_le32(line + 4, 0xFFFFFFFFu);
@@ -735,14 +731,14 @@ K4_DEV void k4d_bam_put_rec(const K4SamArgs& a, int64_t v, const k4_hit& h, int6
     for (uint32_t q = 0; q < nl_; q++) p[q] = (char)nm[q];
     p[nl_] = 0;
     k4d_put_le32(p + nl_ + 1, len << 4);
-    const int nar = k4d_sam_nar(a, i);
+    const int nar = a.rs.nar(i);
     const int code = nar >= 0 && nar < 20 ? nar : 0;
     char* t = line + line_len - K4_BAM_UNALIGNED_AUX;
     t[0] = 'Y'; t[1] = 'U'; t[2] = 'Z'; t[3] = k4_nar_codes[2 * code]; t[4] = k4_nar_codes[2 * code + 1]; t[5] = 0;
   } else if (sub == 0) {
     const K4SamFields f = k4d_sam_fields(a, v, h);
-    const int w = a.pe ? (int)(i & 1) : 0;
-    const int64_t rec = a.pe ? (i >> 1) : i;
+    const int w = a.rs.pe() ? (int)(i & 1) : 0;
+    const int64_t rec = a.rs.pe() ? (i >> 1) : i;
     const uint32_t nl_ = a.name_len[w][rec];
     const int32_t refid = a.refid[h.chrom_id - 1];
     const int32_t pos0 = (int32_t)f.pos - 1;
@@ -768,7 +764,7 @@ K4_DEV void k4d_bam_put_rec(const K4SamArgs& a, int64_t v, const k4_hit& h, int6
     }
   }
   // sequence: `=ACMGRSVTWYHKDBN' codes, first base in the high nibble, reverse complemented for a Crick alignment (:6254-6300)
-  const uint8_t* s = a.reads + a.offs[i];
+  const uint8_t* s = a.rs.reads + a.rs.offs[i];
   const uint32_t b0 = (uint32_t)((uint64_t)nseq * sub / lpl), b1 = (uint32_t)((uint64_t)nseq * (sub + 1) / lpl);
   const uint64_t fwd = 0x0F0F0F0F08040201ull, rev = 0x0F0F0F0F01020408ull;  // by symbol: A C G T N.. / their complements
   for (uint32_t b = b0; b < b1; b++) {
@@ -784,9 +780,9 @@ K4_DEV void k4d_bam_put_rec(const K4SamArgs& a, int64_t v, const k4_hit& h, int6
   }
   const uint32_t q0 = (uint32_t)((uint64_t)len * sub / lpl), q1 = (uint32_t)((uint64_t)len * (sub + 1) / lpl);
   if (k4d_sam_has_qual(a, i)) {  // the reference stores the SAM characters themselves in the BAM record (SAMfile.cpp:2468 copies pBAMalign->qual)
-    const uint8_t* rs = a.reads + a.offs[i];
+    const uint8_t* rq = a.rs.reads + a.rs.offs[i];
     const bool rv = !unal && h.strand != '+';
-    for (uint32_t q = q0; q < q1; q++) qual[q] = (char)(33 + (((uint32_t)(rs[rv ? len - 1 - q : q] >> 4) & 0x0f) * 40) / 15);
+    for (uint32_t q = q0; q < q1; q++) qual[q] = (char)(33 + (((uint32_t)(rq[rv ? len - 1 - q : q] >> 4) & 0x0f) * 40) / 15);
   } else
     for (uint32_t q = q0; q < q1; q++) qual[q] = (char)0xFF;
 }
@@ -808,13 +804,13 @@ K4_DEV uint32_t k4d_read4(const uint32_t* __restrict__ s32, uint32_t sh, uint32_
 // one line (or sub-lane `sub`'s share of it) at `line`; inlined once with an LDS and once with a global destination
 K4_DEV void k4d_sam_put_line(const K4SamArgs& a, int64_t v, const k4_hit& h, int64_t i, char* line, uint32_t line_len, int sub,
                              int lpl) {
-  const uint32_t len = a.lens[i];
+  const uint32_t len = a.rs.lens[i];
   const bool unal = k4d_sam_unaligned(a, v);
   const bool hq = k4d_sam_has_qual(a, i);  // QUAL holds len characters instead of `*`
   char* seq = line + line_len - (unal ? K4_SAM_UNALIGNED_TAIL : 3) - len - (hq ? len - 1 : 0);
   if (sub == 0 && unal) {
-    const int w = a.pe ? (int)(i & 1) : 0;
-    const int64_t rec = a.pe ? (i >> 1) : i;
+    const int w = a.rs.pe() ? (int)(i & 1) : 0;
+    const int64_t rec = a.rs.pe() ? (i >> 1) : i;
     char* p = line;
     const uint8_t* nm = a.text[w] + a.name_off[w][rec];
     const uint32_t nl_ = a.name_len[w][rec];
@@ -826,7 +822,7 @@ K4_DEV void k4d_sam_put_line(const K4SamArgs& a, int64_t v, const k4_hit& h, int
     p += k4d_put_uint(p, len);
     const char mid2[] = "M\t*\t0\t0\t";
     for (int q = 0; q < 8; q++) *p++ = mid2[q];
-    const int nar = k4d_sam_nar(a, i);
+    const int nar = a.rs.nar(i);
     const int code = nar >= 0 && nar < 20 ? nar : 0;
     char* t = seq + len;
     t[0] = '\t';
@@ -836,8 +832,8 @@ K4_DEV void k4d_sam_put_line(const K4SamArgs& a, int64_t v, const k4_hit& h, int
     t[9] = k4_nar_codes[2 * code]; t[10] = k4_nar_codes[2 * code + 1]; t[11] = '\n';
   } else if (sub == 0) {
     const K4SamFields f = k4d_sam_fields(a, v, h);
-    const int w = a.pe ? (int)(i & 1) : 0;
-    const int64_t rec = a.pe ? (i >> 1) : i;
+    const int w = a.rs.pe() ? (int)(i & 1) : 0;
+    const int64_t rec = a.rs.pe() ? (i >> 1) : i;
     char* p = line;
     const uint8_t* nm = a.text[w] + a.name_off[w][rec];
     const uint32_t nl_ = a.name_len[w][rec];
@@ -862,7 +858,7 @@ K4_DEV void k4d_sam_put_line(const K4SamArgs& a, int64_t v, const k4_hit& h, int
     if (!hq) seq[len + 1] = '*';
     seq[len + 1 + (hq ? len : 1)] = '\n';
   }
-  const uint8_t* s = a.reads + a.offs[i];
+  const uint8_t* s = a.rs.reads + a.rs.offs[i];
   const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(s) & 3);
   const uint32_t* __restrict__ s32 = reinterpret_cast<const uint32_t*>(s - sh);
   const uint32_t span = len + sh;
@@ -985,16 +981,16 @@ namespace {
 struct NarIs {
   K4SamArgs a;
   int nar;
-  __device__ bool operator()(uint32_t i) const { return a.lens[i] != 0 && k4d_sam_nar(a, i) == nar; }
+  __device__ bool operator()(uint32_t i) const { return a.rs.lens[i] != 0 && a.rs.nar(i) == nar; }
 };
 struct IsLoaded {
   const uint32_t* lens;
   __device__ uint32_t operator()(uint32_t i) const { return lens[i] != 0 ? 1u : 0u; }
 };
 K4_DEV uint32_t k4d_fasta_rec_len(const K4SamArgs& a, int64_t i, uint32_t id) {
-  const int w = a.pe ? (int)(i & 1) : 0;
-  const int64_t rec = a.pe ? (i >> 1) : i;
-  const uint32_t len = a.lens[i];
+  const int w = a.rs.pe() ? (int)(i & 1) : 0;
+  const int64_t rec = a.rs.pe() ? (i >> 1) : i;
+  const uint32_t len = a.rs.lens[i];
   return 8u + k4d_udigits(id) + 1u + a.name_len[w][rec] + 1u + k4d_udigits(id) + 3u + k4d_udigits(len) + 1u + len + (len + 69u) / 70u;
 }
 __global__ void __launch_bounds__(256) k4k_fasta_lens(K4SamArgs a, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ ids, uint64_t m,
@@ -1007,9 +1003,9 @@ __global__ void __launch_bounds__(256) k4k_fasta_write(K4SamArgs a, const uint32
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= m) return;
   const int64_t i = idx[j];
-  const uint32_t id = ids[i] + 1, len = a.lens[i];
-  const int w = a.pe ? (int)(i & 1) : 0;
-  const int64_t rec = a.pe ? (i >> 1) : i;
+  const uint32_t id = ids[i] + 1, len = a.rs.lens[i];
+  const int w = a.rs.pe() ? (int)(i & 1) : 0;
+  const int64_t rec = a.rs.pe() ? (i >> 1) : i;
   char* p = out + lo[j];
   const char* head = multi ? ">lcl|ml|" : ">lcl|na|";
   for (int q = 0; q < 8; q++) *p++ = head[q];
@@ -1023,7 +1019,7 @@ __global__ void __launch_bounds__(256) k4k_fasta_write(K4SamArgs a, const uint32
   *p++ = '|'; *p++ = '1'; *p++ = '|';
   p += k4d_put_uint(p, len);
   *p++ = '\n';
-  const uint8_t* s = a.reads + a.offs[i];
+  const uint8_t* s = a.rs.reads + a.rs.offs[i];
   for (uint32_t q = 0; q < len; q++) {
     *p++ = "ACGTNU-?"[s[q] & 7u];  // CSeqTrans::MapSeq2Ascii's defaults (N, undefined, InDel; SeqTrans.cpp:157-181)
     if (q % 70 == 69 || q + 1 == len) *p++ = '\n';
@@ -1045,16 +1041,13 @@ extern "C" int k4_unaligned_fasta_dev(k4_index* ix, int pe, int64_t n_units, con
   if (n_reads >= 0xFFFFFF00ll) return k4_fail(ix, K4_ERR_PARAMS, "at most 2^32-256 reads per call");
   auto empty = [&]() { *text = (char*)calloc(1, 1); return *text ? K4_OK : k4_fail(ix, K4_ERR_MEM, "out of memory"); };
   if (n_reads == 0) return empty();
-  if ((pe && !d_pe) || (!pe && !d_rr) || !d_reads || !d_offs || !d_lens || !names->d_text[0] || !names->d_name_off[0] || !names->d_name_len[0] ||
-      (pe && (!names->d_text[1] || !names->d_name_off[1] || !names->d_name_len[1])))
-    return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
+  K4SamArgs a;
+  memset(&a, 0, sizeof(a));
+  K4_TRY(k4s_read_set(ix, pe, n_reads, d_rr, nullptr, 1, d_pe, nullptr, d_reads, d_offs, d_lens, K4RS_READS, &a.rs));
+  if (!sam_names_given(names, pe)) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
   PoolStream pool_scope(st);
-  K4SamArgs a;
-  memset(&a, 0, sizeof(a));
-  a.pe = pe ? 1 : 0; a.n_reads = n_reads; a.rr = (const k4_read_result*)d_rr; a.pr = (const k4_pe_read*)d_pe; a.max_ml = 1;
-  a.reads = (const uint8_t*)d_reads; a.offs = (const uint64_t*)d_offs; a.lens = (const uint32_t*)d_lens;
   for (int w = 0; w < 2; w++) {
     a.text[w] = (const uint8_t*)names->d_text[w]; a.name_off[w] = (const uint64_t*)names->d_name_off[w];
     a.name_len[w] = (const uint32_t*)names->d_name_len[w];
@@ -1065,7 +1058,7 @@ extern "C" int k4_unaligned_fasta_dev(k4_index* ix, int pe, int64_t n_units, con
   K4_HIP(ix, cnt.alloc(8));
   {  // ReadID - 1: the loaded reads before this one
     rocprim::counting_iterator<uint32_t> all(0);
-    auto loaded = rocprim::make_transform_iterator(all, IsLoaded{a.lens});
+    auto loaded = rocprim::make_transform_iterator(all, IsLoaded{a.rs.lens});
     K4_TRY(k4s_exclusive_scan<Buf>(ix, loaded, ids.as<uint32_t>(), 0u, (size_t)n_reads, rocprim::plus<uint32_t>(), st));
   }
   uint64_t m = 0;
@@ -1169,9 +1162,10 @@ int k4i_format_records(k4_index* ix, int bam, int sq_all, int pe, int64_t n_unit
   const int64_t n_reads = pe ? 2 * n_units : n_units;
   const int64_t n_virt = pe ? n_reads : n_reads * (int64_t)std::max(max_ml, 1);  // addressable SAM lines
   if (n_virt >= 0xFFFFFF00ll) return k4_fail(ix, K4_ERR_PARAMS, "at most 2^32-256 reads x instances per call");
-  if ((pe && !d_pe) || (!pe && (!d_rr || !d_hits || max_ml < 1)) || !d_reads || !d_offs || !d_lens || !names->d_text[0] ||
-      !names->d_name_off[0] || !names->d_name_len[0] || (pe && (!names->d_text[1] || !names->d_name_off[1] || !names->d_name_len[1])))
-    return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
+  K4SamArgs a;
+  memset(&a, 0, sizeof(a));
+  K4_TRY(k4s_read_set(ix, pe, n_reads, d_rr, d_hits, max_ml, d_pe, d_seg2, d_reads, d_offs, d_lens, K4RS_HITS | K4RS_READS, &a.rs));
+  if (!sam_names_given(names, pe)) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
   PoolStream pool_scope(st);
@@ -1191,10 +1185,6 @@ int k4i_format_records(k4_index* ix, int bam, int sq_all, int pe, int64_t n_unit
     K4_HIP(ix, hipMemcpy(cn.p, hn.data(), hn.size(), hipMemcpyHostToDevice));
     K4_HIP(ix, hipMemcpy(cl.p, hl.data(), hl.size(), hipMemcpyHostToDevice));
   }
-  K4SamArgs a;
-  memset(&a, 0, sizeof(a));
-  a.pe = pe ? 1 : 0; a.n_reads = n_reads; a.rr = (const k4_read_result*)d_rr; a.hits = (const k4_hit*)d_hits; a.max_ml = max_ml;
-  a.pr = (const k4_pe_read*)d_pe; a.seg2 = pe ? nullptr : (const k4_seg2*)d_seg2; a.reads = (const uint8_t*)d_reads; a.offs = (const uint64_t*)d_offs; a.lens = (const uint32_t*)d_lens;
   for (int w = 0; w < 2; w++) {
     a.text[w] = (const uint8_t*)names->d_text[w]; a.name_off[w] = (const uint64_t*)names->d_name_off[w];
     a.name_len[w] = (const uint32_t*)names->d_name_len[w];

@@ -111,26 +111,23 @@ extern "C" int k4_pba_run_dev(k4_index* ix, int pe, int64_t n_units, const void*
   if (!ix || !out) return K4_ERR_PARAMS;
   memset(out, 0, sizeof(*out));
   if (n_units < 0 || !experiment_id || !readset_id) return k4_fail(ix, K4_ERR_PARAMS, "packed base alleles: parameters out of range");
-  if (n_units > 0 && ((pe && !d_pe) || (!pe && (!d_rr || !d_hits || max_ml < 1)) || !d_reads || !d_offs || !d_lens))
-    return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
-  K4_HIP(ix, hipSetDevice(ix->device));
-  hipStream_t st = (hipStream_t)stream;
   SnpArgs a;
   memset(&a, 0, sizeof(a));
-  a.ix = ix->d; a.pe = pe ? 1 : 0; a.n_reads = pe ? 2 * n_units : n_units;
-  a.rr = (const k4_read_result*)d_rr; a.hits = (const k4_hit*)d_hits; a.max_ml = max_ml; a.pr = (const k4_pe_read*)d_pe;
-  a.reads = (const uint8_t*)d_reads; a.offs = (const uint64_t*)d_offs; a.lens = (const uint32_t*)d_lens;
+  a.ix = ix->d;
+  K4_TRY(k4s_read_set(ix, pe, n_units, d_rr, d_hits, max_ml, d_pe, nullptr, d_reads, d_offs, d_lens, K4RS_HITS | K4RS_READS | K4RS_UNITS, &a.rs));
+  K4_HIP(ix, hipSetDevice(ix->device));
+  hipStream_t st = (hipStream_t)stream;
   uint32_t max_len = 0;
   for (const k4_entry& e : ix->entries) max_len = std::max(max_len, e.seq_len);
   const size_t S = (size_t)max_len + 16;
   std::vector<uint8_t> chrom_hit((size_t)ix->d.n_entries + 1, 0);
   std::vector<uint64_t> ent_start_h((size_t)ix->d.n_entries, 0);
   K4DevBuf cnt, tot, pbab, covb, covmax;
-  if (a.n_reads > 0 && ix->d.n_entries) {
+  if (a.rs.n_reads > 0 && ix->d.n_entries) {
     K4DevBuf flags;
     K4_HIP(ix, flags.alloc(chrom_hit.size()));
     K4_HIP(ix, hipMemsetAsync(flags.p, 0, chrom_hit.size(), st));
-    hipLaunchKernelGGL(k4k_snp_mark, dim3((unsigned)std::min<int64_t>((a.n_reads + 255) / 256, 2048)), dim3(256), 0, st, a, flags.as<uint8_t>(), ix->d.n_entries);
+    hipLaunchKernelGGL(k4k_snp_mark, dim3((unsigned)std::min<int64_t>((a.rs.n_reads + 255) / 256, 2048)), dim3(256), 0, st, a, flags.as<uint8_t>(), ix->d.n_entries);
     K4_HIP(ix, hipMemcpyAsync(chrom_hit.data(), flags.p, chrom_hit.size(), hipMemcpyDeviceToHost, st));
     K4_HIP(ix, hipMemcpyAsync(ent_start_h.data(), ix->ent_start.p, ent_start_h.size() * 8, hipMemcpyDeviceToHost, st));
     K4_HIP(ix, hipStreamSynchronize(st));
@@ -147,7 +144,7 @@ extern "C" int k4_pba_run_dev(k4_index* ix, int pe, int64_t n_units, const void*
   struct EvGuard { hipEvent_t* ev; ~EvGuard() { for (int k = 0; k < 3; k++) if (ev[k]) (void)hipEventDestroy(ev[k]); } } ev_guard{ev};
   std::vector<std::future<WigOut>> wig_jobs;  // (behind the trace file: the walks are waited for before it closes)
   auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-  for (uint32_t chrom = 1; chrom <= ix->d.n_entries && a.n_reads > 0; chrom++) {
+  for (uint32_t chrom = 1; chrom <= ix->d.n_entries && a.rs.n_reads > 0; chrom++) {
     if (!chrom_hit[chrom]) continue;
     if (!cnt.p) {
       K4_HIP(ix, cnt.alloc(7 * S * 4));

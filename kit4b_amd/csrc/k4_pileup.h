@@ -14,15 +14,7 @@ namespace {
 
 struct SnpArgs {
   K4DevIndex ix;
-  int pe;
-  int64_t n_reads;
-  const k4_read_result* rr;
-  const k4_hit* hits;
-  int max_ml;
-  const k4_pe_read* pr;
-  const uint8_t* reads;
-  const uint64_t* offs;
-  const uint32_t* lens;
+  K4ReadSet rs;      // (read only: no kernel of the two files writes a record)
   uint32_t chrom_id;
   uint64_t cs;       // concat offset of the chromosome
   uint32_t clen;
@@ -36,16 +28,15 @@ __global__ void __launch_bounds__(256) k4k_snp_pileup(SnpArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * 256) >> 6;
   unsigned long long m = 0, mm = 0, nr = 0, nb = 0;
-  for (int64_t i = wave0; i < a.n_reads; i += n_waves) {
-    const int nar = a.pe ? a.pr[i].nar : a.rr[i].nar;
-    if (nar != K4_NAR_ACCEPTED) continue;
-    const k4_hit h = a.pe ? a.pr[i].hit : a.hits[i * a.max_ml];
+  for (int64_t i = wave0; i < a.rs.n_reads; i += n_waves) {
+    if (a.rs.nar(i) != K4_NAR_ACCEPTED) continue;
+    const k4_hit h = a.rs.hit(i);
     if (h.chrom_id != a.chrom_id || (h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE))) continue;
     const uint32_t tl = K4_HIT_TRIM_LEFT(h);
     uint32_t match_len = k4d_adj_len(h);
     const uint32_t loci0 = k4d_adj_start(h);
     if ((uint64_t)loci0 + match_len > a.clen) continue;                  // (GetSeq comes back short: the read is skipped, :8420)
-    const uint8_t* src = a.reads + a.offs[i] + tl;
+    const uint8_t* src = a.rs.reads + a.rs.offs[i] + tl;
     if (lane == 0) { nr++; nb += match_len; }
     for (uint32_t q = lane; q < match_len; q += 64) {
       const uint32_t ref = k4d_ref_base(a.ix, a.cs + loci0 + q);
@@ -73,10 +64,9 @@ __global__ void __launch_bounds__(256) k4k_snp_pileup(SnpArgs a) {
 // an assembly of 10^5 contigs costs its hit contigs, not its contigs (the reference walks its sorted reads once)
 __global__ void __launch_bounds__(256) k4k_snp_mark(SnpArgs a, uint8_t* __restrict__ flags, uint32_t n_entries) {
   const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n_reads; i += stride) {
-    const int nar = a.pe ? a.pr[i].nar : a.rr[i].nar;
-    if (nar != K4_NAR_ACCEPTED) continue;
-    const k4_hit h = a.pe ? a.pr[i].hit : a.hits[i * a.max_ml];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.rs.n_reads; i += stride) {
+    if (a.rs.nar(i) != K4_NAR_ACCEPTED) continue;
+    const k4_hit h = a.rs.hit(i);
     if ((h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE)) || h.chrom_id < 1 || h.chrom_id > n_entries) continue;
     flags[h.chrom_id] = 1;
   }

@@ -24,25 +24,23 @@ K4_DEV uint32_t k4d_targ_in_read_sense(const K4DevIndex& ix, uint64_t base, uint
 // AutoTrimFlanks, one thread per read: walk in from the 5' end until min_flank_exacts consecutive bases match, the same
 // from the 3' end; what is outside becomes TrimLeft / TrimRight.  SE: a read that cannot keep (len+1)/2 (>= 15) bases
 // between two such flanks is eliminated (eNARTrim).  One-segment, non-chimeric hits only (:1748).
-__global__ void __launch_bounds__(256) k4k_auto_trim(K4DevIndex ix, int mfe, int pe, int64_t n, int max_ml, k4_read_result* __restrict__ rr,
-                                                     k4_pe_read* __restrict__ pr, k4_hit* __restrict__ hits,
-                                                     const uint8_t* __restrict__ reads, const uint64_t* __restrict__ offs,
-                                                     const uint32_t* __restrict__ lens, unsigned long long* __restrict__ n_elim) {
+__global__ void __launch_bounds__(256) k4k_auto_trim(K4DevIndex ix, int mfe, K4ReadSet rs, unsigned long long* __restrict__ n_elim) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  k4_hit* hp = pr ? &pr[i].hit : &hits[i * max_ml];
-  const int nar = pr ? pr[i].nar : rr[i].nar;
+  if (i >= rs.n_reads) return;
+  const bool pe = rs.pe();
+  k4_hit* hp = rs.hit_ptr(i);
+  const int nar = rs.nar(i);
   k4_hit h = *hp;
   if (nar != K4_NAR_ACCEPTED || (h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE | K4_EXT_CHIMERIC))) return;
-  const uint32_t match_len = h.match_len, read_len = lens[i];
-  if (match_len != read_len) {  // :1751-1759 (cannot happen for a one-segment hit; NumHits 0, NAR stays)
-    if (pr) pr[i].num_hits = 0; else rr[i].num_hits = 0;
+  const uint32_t match_len = h.match_len, read_len = rs.lens[i];
+  if (match_len != read_len) {  // :1751-1759 (cannot happen for a one-segment hit; NumHits 0, NAR stays: :1753)
+    rs.drop_hits(i);
     atomicAdd(n_elim, 1ull);
     return;
   }
   int min_trimmed = (int)(match_len + 1) / 2;
   if (min_trimmed < 15) min_trimmed = 15;
-  const uint8_t* rd = reads + offs[i];
+  const uint8_t* rd = rs.reads + rs.offs[i];
   const uint64_t base = ix.ent_start[h.chrom_id - 1] + h.match_loci;
   const bool minus = h.strand == '-';
   int exact = 0;
@@ -52,8 +50,8 @@ __global__ void __launch_bounds__(256) k4k_auto_trim(K4DevIndex ix, int mfe, int
     if ((uint32_t)(rd[idx] & 7) != k4d_targ_in_read_sense(ix, base, match_len, minus, idx)) { exact = 0; continue; }
     if (++exact == mfe) break;
   }
-  if (!pe && ((idx + (uint32_t)min_trimmed) > match_len || exact < mfe)) {  // :1830-1843
-    rr[i].num_hits = 0; rr[i].nar = K4_NAR_TRIM;
+  if (!pe && ((idx + (uint32_t)min_trimmed) > match_len || exact < mfe)) {  // :1830-1843, NAR and NumHits (:1835-1836)
+    rs.reject(i, K4_NAR_TRIM, false);
     atomicAdd(n_elim, 1ull);
     return;
   }
@@ -64,8 +62,8 @@ __global__ void __launch_bounds__(256) k4k_auto_trim(K4DevIndex ix, int mfe, int
     if ((uint32_t)(rd[idx] & 7) != k4d_targ_in_read_sense(ix, base, match_len, minus, idx)) { exact = 0; continue; }
     if (++exact == mfe) break;
   }
-  if (!pe && (exact != mfe || idx < (uint32_t)(left_ofs + min_trimmed))) {  // :1868-1881
-    rr[i].num_hits = 0; rr[i].nar = K4_NAR_TRIM;
+  if (!pe && (exact != mfe || idx < (uint32_t)(left_ofs + min_trimmed))) {  // :1868-1881, NAR and NumHits (:1873-1874)
+    rs.reject(i, K4_NAR_TRIM, false);
     atomicAdd(n_elim, 1ull);
     return;
   }
@@ -75,45 +73,44 @@ __global__ void __launch_bounds__(256) k4k_auto_trim(K4DevIndex ix, int mfe, int
 }
 
 // ---- orphan junctions ---------------------------------------------------------------------------------------------------
+// SE only (the PE records carry no second segment): these kernels take the view and read its SE side, rr and hits, directly.
 struct IsJunct {
-  const k4_read_result* rr;
-  const k4_hit* hits;
-  int max_ml;
+  K4ReadSet rs;
   uint32_t which;
-  __device__ bool operator()(uint32_t i) const { return rr[i].nar == K4_NAR_ACCEPTED && (hits[(int64_t)i * max_ml].ext & which) != 0; }
+  __device__ bool operator()(uint32_t i) const { return rs.rr[i].nar == K4_NAR_ACCEPTED && (rs.hits[(int64_t)i * rs.max_ml].ext & which) != 0; }
 };
 
 // Starts = AdjEndLoci(Seg[0]), Ends = AdjStartLoci(Seg[1]) (:2446-2447; a two-segment hit carries no trimming)
-__global__ void __launch_bounds__(256) k4k_junct_keys(uint64_t m, const uint32_t* __restrict__ idx, const k4_hit* __restrict__ hits, int max_ml,
-                                                      const k4_seg2* __restrict__ seg2, uint64_t* __restrict__ major, uint32_t* __restrict__ minor) {
+__global__ void __launch_bounds__(256) k4k_junct_keys(uint64_t m, const uint32_t* __restrict__ idx, const K4ReadSet rs,
+                                                      uint64_t* __restrict__ major, uint32_t* __restrict__ minor) {
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= m) return;
   const uint32_t i = idx[j];
-  const k4_hit h = hits[(int64_t)i * max_ml];
+  const k4_hit h = rs.hits[(int64_t)i * rs.max_ml];
   const uint32_t starts = h.match_loci + ((uint32_t)h.match_len - 1u);
   major[j] = ((uint64_t)h.chrom_id << 32) | starts;
-  minor[j] = seg2[i].match_loci;
+  minor[j] = rs.seg2[i].match_loci;
 }
 // neighbours in (chrom, start, end) order that agree within 3 bp at both ends support each other (:2456-2465; 32-bit
 // unsigned arithmetic as there)
 __global__ void __launch_bounds__(256) k4k_junct_mark(uint64_t m, const uint32_t* __restrict__ order, const uint64_t* __restrict__ major,
-                                                      const uint32_t* __restrict__ minor, k4_hit* __restrict__ hits, int max_ml) {
+                                                      const uint32_t* __restrict__ minor, K4ReadSet rs) {
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (j + 1 >= m) return;
   const uint32_t ca = (uint32_t)(major[j] >> 32), cb = (uint32_t)(major[j + 1] >> 32);
   const uint32_t sa = (uint32_t)major[j], sb = (uint32_t)major[j + 1], ea = minor[j], eb = minor[j + 1];
   if (ca == cb && sa <= (uint32_t)(sb + 3u) && sa >= (uint32_t)(sb - 3u) && ea <= (uint32_t)(eb + 3u) && ea >= (uint32_t)(eb - 3u)) {
-    atomicOr(&hits[(int64_t)order[j] * max_ml].ext, K4_EXT_NONORPHAN);
-    atomicOr(&hits[(int64_t)order[j + 1] * max_ml].ext, K4_EXT_NONORPHAN);
+    atomicOr(&rs.hits[(int64_t)order[j] * rs.max_ml].ext, K4_EXT_NONORPHAN);
+    atomicOr(&rs.hits[(int64_t)order[j + 1] * rs.max_ml].ext, K4_EXT_NONORPHAN);
   }
 }
-__global__ void __launch_bounds__(256) k4k_junct_drop(uint64_t m, const uint32_t* __restrict__ order, const k4_hit* __restrict__ hits, int max_ml,
-                                                      k4_read_result* __restrict__ rr, int nar, unsigned long long* __restrict__ n_removed) {
+__global__ void __launch_bounds__(256) k4k_junct_drop(uint64_t m, const uint32_t* __restrict__ order, K4ReadSet rs, int nar,
+                                                      unsigned long long* __restrict__ n_removed) {
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= m) return;
   const uint32_t i = order[j];
-  if (!(hits[(int64_t)i * max_ml].ext & K4_EXT_NONORPHAN)) {
-    rr[i].nar = nar; rr[i].num_hits = 0; rr[i].inst = 0;
+  if (!(rs.hits[(int64_t)i * rs.max_ml].ext & K4_EXT_NONORPHAN)) {
+    rs.rr[i].nar = nar; rs.rr[i].num_hits = 0; rs.rr[i].inst = 0;  // NAR, NumHits and LowHitInstances (:2472-2474, :2485-2487; :2568-2570, :2581-2583)
     atomicAdd(n_removed, 1ull);
   }
 }
@@ -126,16 +123,14 @@ extern "C" int k4_auto_trim_flanks_dev(k4_index* ix, int32_t min_flank_exacts, i
   if (!ix) return K4_ERR_PARAMS;
   if (n_eliminated) *n_eliminated = 0;
   if (min_flank_exacts <= 0 || n_reads <= 0) return K4_OK;
-  if (!d_rr || (!pe && (!d_hits || max_ml < 1)) || !d_reads || !d_offs || !d_lens) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
+  K4ReadSet rs;  // PE: d_rr holds k4_pe_read records (hit inside); SE: k4_read_result + the hit slots
+  K4_TRY(k4s_read_set(ix, pe, n_reads, d_rr, d_hits, max_ml, d_rr, nullptr, d_reads, d_offs, d_lens, K4RS_HITS | K4RS_READS, &rs));
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
   K4DevBuf cnt;
   K4_HIP(ix, cnt.alloc(8));
   K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 8, st));
-  // PE: d_rr holds k4_pe_read records (hit inside); SE: k4_read_result + the hit slots
-  hipLaunchKernelGGL(k4k_auto_trim, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, st, ix->d, (int)min_flank_exacts, pe ? 1 : 0,
-                     n_reads, (int)max_ml, pe ? (k4_read_result*)nullptr : (k4_read_result*)d_rr, pe ? (k4_pe_read*)d_rr : (k4_pe_read*)nullptr,
-                     (k4_hit*)d_hits, (const uint8_t*)d_reads, (const uint64_t*)d_offs, (const uint32_t*)d_lens,
+  hipLaunchKernelGGL(k4k_auto_trim, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, st, ix->d, (int)min_flank_exacts, rs,
                      cnt.as<unsigned long long>());
   K4_HIP(ix, hipGetLastError());
   unsigned long long c = 0;
@@ -150,7 +145,8 @@ extern "C" int k4_remove_orphan_juncts_dev(k4_index* ix, uint32_t which, int64_t
   if (n_removed) *n_removed = 0;
   if (which != K4_EXT_SPLICE && which != K4_EXT_INDEL) return k4_fail(ix, K4_ERR_PARAMS, "which must be K4_EXT_SPLICE or K4_EXT_INDEL");
   if (n_reads <= 0) return K4_OK;
-  if (!d_rr || !d_hits || !d_seg2 || max_ml < 1) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
+  K4ReadSet rs;  // (SE only)
+  K4_TRY(k4s_read_set(ix, 0, n_reads, d_rr, d_hits, max_ml, nullptr, d_seg2, nullptr, nullptr, nullptr, K4RS_HITS | K4RS_SEG2, &rs));
   if (n_reads >= 0xFFFFFF00ll) return k4_fail(ix, K4_ERR_PARAMS, "at most 2^32-256 reads per call");
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
@@ -158,7 +154,7 @@ extern "C" int k4_remove_orphan_juncts_dev(k4_index* ix, uint32_t which, int64_t
   K4_HIP(ix, cnt.alloc(8));
   K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 8, st));
   uint64_t m = 0;
-  K4_TRY(k4s_select_indices(ix, idx0, (size_t)n_reads, IsJunct{(const k4_read_result*)d_rr, (const k4_hit*)d_hits, (int)max_ml, which}, st, &m));
+  K4_TRY(k4s_select_indices(ix, idx0, (size_t)n_reads, IsJunct{rs, which}, st, &m));
   if (m == 0) return K4_OK;
   const unsigned nb = (unsigned)((m + 255) / 256);
   const uint32_t* order = idx0.as<uint32_t>();
@@ -170,24 +166,20 @@ extern "C" int k4_remove_orphan_juncts_dev(k4_index* ix, uint32_t which, int64_t
     K4_HIP(ix, mb2.alloc(m * 4));
     // SortSegJuncts (KAligner.cpp:11104): chrom, start, end -- two stable radix sorts, the minor key first; the keys travel
     // with the values so that they are in sorted order for the neighbour test
-    hipLaunchKernelGGL(k4k_junct_keys, dim3(nb), dim3(256), 0, st, m, idx0.as<uint32_t>(), (const k4_hit*)d_hits, (int)max_ml,
-                       (const k4_seg2*)d_seg2, ka.as<uint64_t>(), ma.as<uint32_t>());
+    hipLaunchKernelGGL(k4k_junct_keys, dim3(nb), dim3(256), 0, st, m, idx0.as<uint32_t>(), rs, ka.as<uint64_t>(), ma.as<uint32_t>());
     rocprim::double_buffer<uint32_t> mk(ma.as<uint32_t>(), mb2.as<uint32_t>());
     rocprim::double_buffer<uint32_t> vb(idx0.as<uint32_t>(), idx1.as<uint32_t>());
     K4_TRY(k4s_sort_pairs<K4DevBuf>(ix, mk, vb, (size_t)m, 0u, 32u, st));
     // keys of the values in their new order
-    hipLaunchKernelGGL(k4k_junct_keys, dim3(nb), dim3(256), 0, st, m, vb.current(), (const k4_hit*)d_hits, (int)max_ml,
-                       (const k4_seg2*)d_seg2, ka.as<uint64_t>(), mk.alternate());
+    hipLaunchKernelGGL(k4k_junct_keys, dim3(nb), dim3(256), 0, st, m, vb.current(), rs, ka.as<uint64_t>(), mk.alternate());
     rocprim::double_buffer<uint64_t> kk(ka.as<uint64_t>(), kb.as<uint64_t>());
     K4_TRY(k4s_sort_pairs<K4DevBuf>(ix, kk, vb, (size_t)m, 0u, 64u, st));
     order = vb.current();
     uint32_t* minor_sorted = mk.alternate();
-    hipLaunchKernelGGL(k4k_junct_keys, dim3(nb), dim3(256), 0, st, m, order, (const k4_hit*)d_hits, (int)max_ml, (const k4_seg2*)d_seg2,
-                       kk.alternate(), minor_sorted);
-    hipLaunchKernelGGL(k4k_junct_mark, dim3(nb), dim3(256), 0, st, m, order, (const uint64_t*)kk.alternate(), (const uint32_t*)minor_sorted,
-                       (k4_hit*)d_hits, (int)max_ml);
+    hipLaunchKernelGGL(k4k_junct_keys, dim3(nb), dim3(256), 0, st, m, order, rs, kk.alternate(), minor_sorted);
+    hipLaunchKernelGGL(k4k_junct_mark, dim3(nb), dim3(256), 0, st, m, order, (const uint64_t*)kk.alternate(), (const uint32_t*)minor_sorted, rs);
   }
-  hipLaunchKernelGGL(k4k_junct_drop, dim3(nb), dim3(256), 0, st, m, order, (const k4_hit*)d_hits, (int)max_ml, (k4_read_result*)d_rr,
+  hipLaunchKernelGGL(k4k_junct_drop, dim3(nb), dim3(256), 0, st, m, order, rs,
                      which == K4_EXT_SPLICE ? K4_NAR_SPLICEJCTN : K4_NAR_MICROINDEL, cnt.as<unsigned long long>());
   K4_HIP(ix, hipGetLastError());
   unsigned long long c = 0;

@@ -27,10 +27,7 @@
 
 namespace {
 
-__global__ void __launch_bounds__(256) k4k_primer_correct(K4DevIndex ix, int max_subs, int klen, int64_t n_reads, int max_ml,
-                                                          k4_read_result* __restrict__ rr, k4_hit* __restrict__ hits,
-                                                          k4_pe_read* __restrict__ pr, uint8_t* __restrict__ reads,
-                                                          const uint64_t* __restrict__ offs, const uint32_t* __restrict__ lens,
+__global__ void __launch_bounds__(256) k4k_primer_correct(K4DevIndex ix, int max_subs, int klen, K4ReadSet rs,
                                                           unsigned long long* __restrict__ totals) {
   __shared__ uint32_t s_tot[3];
   if (threadIdx.x < 3) s_tot[threadIdx.x] = 0;
@@ -41,10 +38,9 @@ __global__ void __launch_bounds__(256) k4k_primer_correct(K4DevIndex ix, int max
   k4_hit h = {0, 0, 0, 0, 0, 0};
   int low_mm = 0, max_mms = 0;
   uint32_t rlen = 0;
-  if (i < n_reads && (pr ? pr[i].nar : rr[i].nar) == K4_NAR_ACCEPTED) {
-    h = pr ? pr[i].hit : hits[i * max_ml];
-    rlen = lens[i];
-    low_mm = pr ? pr[i].low_mm : rr[i].low_mm;
+  if (i < rs.n_reads && rs.accepted(i, h)) {
+    rlen = rs.lens[i];
+    low_mm = rs.low_mm(i);
     max_mms = (int)(((int64_t)max_subs * rlen + 50) / 100);
     todo = !(h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE)) && low_mm > max_mms && (uint32_t)h.match_len == rlen && rlen > 0 &&
            h.chrom_id >= 1 && h.chrom_id <= ix.n_entries;
@@ -79,7 +75,7 @@ __global__ void __launch_bounds__(256) k4k_primer_correct(K4DevIndex ix, int max
           tn |= b << (4 * j);
         }
       }
-      uint8_t* rd = reads + offs[i];
+      uint8_t* rd = rs.reads + rs.offs[i];
       uint32_t rb[K4_PRIMER_KLEN];
       uint32_t mm_mask = 0;
 #pragma unroll
@@ -102,13 +98,12 @@ __global__ void __launch_bounds__(256) k4k_primer_correct(K4DevIndex ix, int max
 #pragma unroll
         for (int j = 0; j < K4_PRIMER_KLEN; j++)
           if ((fix >> j) & 1u) rd[j] = (uint8_t)((rb[j] & 0xF8u) | (uint32_t)((tn >> (4 * j)) & 0xFu));
-        if (pr) { pr[i].low_mm = cur; pr[i].hit.mismatches = (uint8_t)cur; }
-        else { rr[i].low_mm = cur; hits[i * max_ml].mismatches = (uint8_t)cur; }
+        rs.set_low_mm(i, cur);
+        rs.hit_ptr(i)->mismatches = (uint8_t)cur;
         corrected = true;
         n_fixed = (uint32_t)__popc(fix);
-      } else {  // (:2202-2207)
-        if (pr) { pr[i].nar = K4_NAR_NOHIT; pr[i].num_hits = 0; }
-        else { rr[i].nar = K4_NAR_NOHIT; rr[i].num_hits = 0; }
+      } else {  // NAR and NumHits; LowHitInstances stays (:2202-2207)
+        rs.reject(i, K4_NAR_NOHIT, false);
         rejected = true;
       }
     }
@@ -138,7 +133,8 @@ extern "C" int k4_pcr5_primer_correct_dev(k4_index* ix, int32_t max_subs, int32_
   if (max_subs < 0 || max_subs > 15) return k4_fail(ix, K4_ERR_PARAMS, "substitutions per 100bp %d outside of range 0..15", (int)max_subs);
   if (klen > K4_PRIMER_KLEN) return k4_fail(ix, K4_ERR_PARAMS, "primer correction over %d bases, at most %d", (int)klen, K4_PRIMER_KLEN);
   if (klen < 1 || n_reads <= 0) return K4_OK;  // (KLen < 1: :2138)
-  if (!d_rr_or_pe || !d_reads || !d_offs || !d_lens || (!pe && (!d_hits || max_ml < 1))) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
+  K4ReadSet rs;
+  K4_TRY(k4s_read_set(ix, pe, n_reads, d_rr_or_pe, d_hits, max_ml, d_rr_or_pe, nullptr, d_reads, d_offs, d_lens, K4RS_HITS | K4RS_READS, &rs));
   const int64_t blocks = (n_reads + 255) / 256;
   if (blocks > 0x7FFFFFFFll) return k4_fail(ix, K4_ERR_PARAMS, "at most 2^39 reads per call");
   K4_HIP(ix, hipSetDevice(ix->device));
@@ -146,9 +142,8 @@ extern "C" int k4_pcr5_primer_correct_dev(k4_index* ix, int32_t max_subs, int32_
   K4DevBuf cnt;
   K4_HIP(ix, cnt.alloc(8 * 3));
   K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 8 * 3, st));
-  hipLaunchKernelGGL(k4k_primer_correct, dim3((unsigned)blocks), dim3(256), 0, st, ix->d, (int)max_subs, (int)klen, n_reads, (int)max_ml,
-                     pe ? nullptr : (k4_read_result*)d_rr_or_pe, pe ? nullptr : (k4_hit*)d_hits, pe ? (k4_pe_read*)d_rr_or_pe : nullptr,
-                     (uint8_t*)d_reads, (const uint64_t*)d_offs, (const uint32_t*)d_lens, cnt.as<unsigned long long>());
+  hipLaunchKernelGGL(k4k_primer_correct, dim3((unsigned)blocks), dim3(256), 0, st, ix->d, (int)max_subs, (int)klen, rs,
+                     cnt.as<unsigned long long>());
   K4_HIP(ix, hipGetLastError());
   unsigned long long c[3];
   K4_TRY(k4s_read_back(ix, &c, cnt.p, st));

@@ -35,35 +35,26 @@
 
 namespace {
 
-struct SiteSrc {
-  const k4_read_result* rr;
-  const k4_hit* hits;
-  const k4_pe_read* pr;
-  int max_ml;
-  uint32_t n_entries;
-};
-K4_DEV k4_hit k4d_site_hit(const SiteSrc& s, int64_t i) { return s.pr ? s.pr[i].hit : s.hits[i * s.max_ml]; }
-
 struct IsSiteRead {  // accepted (:8752); a two-segment read is sorted along and comes out uncounted
-  SiteSrc s;
+  K4ReadSet s;
+  uint32_t n_entries;
   __device__ bool operator()(uint32_t i) const {
-    if ((s.pr ? s.pr[i].nar : s.rr[i].nar) != K4_NAR_ACCEPTED) return false;
-    const k4_hit h = k4d_site_hit(s, i);
-    return h.chrom_id >= 1 && h.chrom_id <= s.n_entries;
+    k4_hit h;
+    return s.accepted(i, h) && h.chrom_id >= 1 && h.chrom_id <= n_entries;
   }
 };
 
 // the formatter's keys (k4_io.hip): AdjHitLen, strand, mismatches; then chrom, AdjStartLoci
-__global__ void __launch_bounds__(256) k4k_site_key_minor(SiteSrc s, uint32_t m, const uint32_t* __restrict__ idx, uint32_t* __restrict__ key) {
+__global__ void __launch_bounds__(256) k4k_site_key_minor(const K4ReadSet s, uint32_t m, const uint32_t* __restrict__ idx, uint32_t* __restrict__ key) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= m) return;
-  const k4_hit h = k4d_site_hit(s, idx[j]);
+  const k4_hit h = s.hit(idx[j]);
   key[j] = (k4d_adj_len(h) << 16) | ((uint32_t)h.strand << 8) | h.mismatches;
 }
-__global__ void __launch_bounds__(256) k4k_site_key_major(SiteSrc s, uint32_t m, const uint32_t* __restrict__ idx, uint64_t* __restrict__ key) {
+__global__ void __launch_bounds__(256) k4k_site_key_major(const K4ReadSet s, uint32_t m, const uint32_t* __restrict__ idx, uint64_t* __restrict__ key) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= m) return;
-  const k4_hit h = k4d_site_hit(s, idx[j]);
+  const k4_hit h = s.hit(idx[j]);
   key[j] = ((uint64_t)h.chrom_id << 32) | k4d_adj_start(h);
 }
 
@@ -77,11 +68,11 @@ K4_DEV uint32_t k4d_revcomp8(uint32_t x) {
 }
 
 // :8757-8808.  key[j] = strand << 16 | octamer, or K4_SITE_UNCOUNTED; site[j] = chrom << 32 | HitLoci
-__global__ void __launch_bounds__(256) k4k_site_octamers(K4DevIndex ix, SiteSrc s, uint32_t m, const uint32_t* __restrict__ order, int32_t ofs,
+__global__ void __launch_bounds__(256) k4k_site_octamers(K4DevIndex ix, const K4ReadSet s, uint32_t m, const uint32_t* __restrict__ order, int32_t ofs,
                                                          uint32_t* __restrict__ key, uint64_t* __restrict__ site) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= m) return;
-  const k4_hit h = k4d_site_hit(s, order[j]);
+  const k4_hit h = s.hit(order[j]);
   const bool minus = h.strand != '+';
   uint32_t hl = h.match_loci;
   if (minus) hl = hl + (uint32_t)h.match_len - 1u - (uint32_t)ofs - 7u;
@@ -173,7 +164,8 @@ extern "C" int k4_site_prefs_dev(k4_index* ix, int pe, int64_t n_reads, int32_t 
   memset(out, 0, sizeof(*out));
   if (ofs < -100 || ofs > 100) return k4_fail(ix, K4_ERR_PARAMS, "site preferences offset %d outside of range -100..100", (int)ofs);
   if (n_reads < 0) return k4_fail(ix, K4_ERR_PARAMS, "read count out of range");
-  if (n_reads > 0 && (pe ? !d_pe : (!d_rr || !d_hits || max_ml < 1))) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
+  K4ReadSet s;
+  K4_TRY(k4s_read_set(ix, pe, n_reads, d_rr, d_hits, max_ml, d_pe, nullptr, nullptr, nullptr, nullptr, K4RS_HITS, &s));
   if (n_reads >= 0xFFFFFF00ll) return k4_fail(ix, K4_ERR_PARAMS, "at most 2^32-256 reads per call");
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
@@ -186,12 +178,10 @@ extern "C" int k4_site_prefs_dev(k4_index* ix, int pe, int64_t n_reads, int32_t 
   out->num_sites[1] = blk + 3 * K4_SITE_OCTS;
   auto run = [&]() -> int {
     if (n_reads == 0) return k4_check_hip(ix, hipStreamSynchronize(st), "stream");
-    SiteSrc s = {pe ? nullptr : (const k4_read_result*)d_rr, pe ? nullptr : (const k4_hit*)d_hits, pe ? (const k4_pe_read*)d_pe : nullptr,
-                 (int)max_ml, ix->d.n_entries};
     // 1. the walk order
     K4DevBuf idx0, idx1, mk0, mk1, kk0, kk1;
     uint64_t m64 = 0;
-    K4_TRY(k4s_select_indices(ix, idx0, (size_t)n_reads, IsSiteRead{s}, st, &m64));
+    K4_TRY(k4s_select_indices(ix, idx0, (size_t)n_reads, IsSiteRead{s, ix->d.n_entries}, st, &m64));
     out->n_accepted = m64;
     if (m64 == 0) return K4_OK;
     const uint32_t m = (uint32_t)m64;
@@ -210,7 +200,7 @@ extern "C" int k4_site_prefs_dev(k4_index* ix, int pe, int64_t n_reads, int32_t 
     K4_HIP(ix, hipGetLastError());
     rocprim::double_buffer<uint64_t> kk(kk0.as<uint64_t>(), kk1.as<uint64_t>());
     unsigned top = 33;  // key = chrom << 32 | start: only the bits chromosome ids can reach are sorted on
-    while (top < 64 && (s.n_entries >> (top - 32)) != 0) top++;
+    while (top < 64 && (ix->d.n_entries >> (top - 32)) != 0) top++;
     K4_TRY(k4s_sort_pairs<K4DevBuf>(ix, kk, vb, (size_t)m, 0u, top, st));
     // 2. octamer and locus per sorted read (the sort's buffers are done with: the keys and loci go where they were)
     uint32_t* key = mk0.as<uint32_t>();

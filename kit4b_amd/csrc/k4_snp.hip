@@ -206,10 +206,9 @@ struct HapArgs {
   uint32_t* tri;            // [n_tri][65]
 };
 __global__ void __launch_bounds__(256) k4k_snp_haplotypes(SnpArgs a, HapArgs hp) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n_reads; i += (int64_t)gridDim.x * 256) {
-    const int nar = a.pe ? a.pr[i].nar : a.rr[i].nar;
-    if (nar != K4_NAR_ACCEPTED) continue;
-    const k4_hit h = a.pe ? a.pr[i].hit : a.hits[i * a.max_ml];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.rs.n_reads; i += (int64_t)gridDim.x * 256) {
+    if (a.rs.nar(i) != K4_NAR_ACCEPTED) continue;
+    const k4_hit h = a.rs.hit(i);
     if (h.chrom_id != a.chrom_id || (h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE))) continue;
     const uint32_t match_len = k4d_adj_len(h);
     const uint32_t start = k4d_adj_start(h);  // AdjStartLoci .. AdjEndLoci
@@ -220,7 +219,7 @@ __global__ void __launch_bounds__(256) k4k_snp_haplotypes(SnpArgs a, HapArgs hp)
       const uint32_t mid = (lo + hi) >> 1;
       if (hp.loci[mid] < start) lo = mid + 1; else hi = mid;
     }
-    const uint8_t* bases = a.reads + a.offs[i];
+    const uint8_t* bases = a.rs.reads + a.rs.offs[i];
     const bool anti = h.strand != '+';
     uint32_t b1 = 7, b2 = 7;  // the read's bases at the two loci before this one
     for (uint32_t k = lo; k < hp.n_loci; k++) {
@@ -453,8 +452,10 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
   if (n_units < 0 || min_snp_reads < 1 || qvalue < 0.0 || snp_nonref_pcnt < 0.0) return k4_fail(ix, K4_ERR_PARAMS, "SNP parameters out of range");
   if (marker_len != 0 && (marker_len < 25 || marker_len > 500 || !(extra->poly_thres >= 0.0 && extra->poly_thres <= 0.5)))  // cMinMarkerLen .. cMaxMarkerLen
     return k4_fail(ix, K4_ERR_PARAMS, "marker length must be 0 or 25..500 and the marker polymorphism threshold 0.0..0.5");
-  if (n_units > 0 && ((pe && !d_pe) || (!pe && (!d_rr || !d_hits || max_ml < 1)) || !d_reads || !d_offs || !d_lens))
-    return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
+  SnpArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ix = ix->d;
+  K4_TRY(k4s_read_set(ix, pe, n_units, d_rr, d_hits, max_ml, d_pe, nullptr, d_reads, d_offs, d_lens, K4RS_HITS | K4RS_READS | K4RS_UNITS, &a.rs));
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
   std::string text =
@@ -464,11 +465,6 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
     text = "##fileformat=VCFv4.1\n##source=k4align1.0\n##reference=" + ix->dataset +
            "\n##INFO=<ID=AF,Number=A,Type=Float,Description=\"Allele Frequency\">\n##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Read Depth\">\n"
            "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
-  SnpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.ix = ix->d; a.pe = pe ? 1 : 0; a.n_reads = pe ? 2 * n_units : n_units;
-  a.rr = (const k4_read_result*)d_rr; a.hits = (const k4_hit*)d_hits; a.max_ml = max_ml; a.pr = (const k4_pe_read*)d_pe;
-  a.reads = (const uint8_t*)d_reads; a.offs = (const uint64_t*)d_offs; a.lens = (const uint32_t*)d_lens;
   uint32_t max_len = 0;
   for (const k4_entry& e : ix->entries) max_len = std::max(max_len, e.seq_len);
   const size_t S = (size_t)max_len + 16;
@@ -502,16 +498,16 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
   char alts[100] = "", freq[100] = "";  // VCF: ALT and AF of the last SNP that had any (see below)
   std::vector<uint8_t> chrom_hit((size_t)ix->d.n_entries + 1, 0);
   std::vector<uint64_t> ent_start_h((size_t)ix->d.n_entries, 0);
-  if (a.n_reads > 0 && ix->d.n_entries) {
+  if (a.rs.n_reads > 0 && ix->d.n_entries) {
     K4DevBuf flags;
     K4_HIP(ix, flags.alloc(chrom_hit.size()));
     K4_HIP(ix, hipMemsetAsync(flags.p, 0, chrom_hit.size(), st));
-    hipLaunchKernelGGL(k4k_snp_mark, dim3((unsigned)std::min<int64_t>((a.n_reads + 255) / 256, 2048)), dim3(256), 0, st, a, flags.as<uint8_t>(), ix->d.n_entries);
+    hipLaunchKernelGGL(k4k_snp_mark, dim3((unsigned)std::min<int64_t>((a.rs.n_reads + 255) / 256, 2048)), dim3(256), 0, st, a, flags.as<uint8_t>(), ix->d.n_entries);
     K4_HIP(ix, hipMemcpyAsync(chrom_hit.data(), flags.p, chrom_hit.size(), hipMemcpyDeviceToHost, st));
     K4_HIP(ix, hipMemcpyAsync(ent_start_h.data(), ix->ent_start.p, ent_start_h.size() * 8, hipMemcpyDeviceToHost, st));
     K4_HIP(ix, hipStreamSynchronize(st));
   }
-  for (uint32_t chrom = 1; chrom <= ix->d.n_entries && a.n_reads > 0; chrom++) {  // the sorted reads: one chromosome after the other
+  for (uint32_t chrom = 1; chrom <= ix->d.n_entries && a.rs.n_reads > 0; chrom++) {  // the sorted reads: one chromosome after the other
     if (!chrom_hit[chrom]) continue;  // (nothing the pile-up would take: no device work, no synchronisation for it)
     const k4_entry& e = ix->entries[chrom - 1];
     a.chrom_id = chrom; a.clen = e.seq_len; a.cnt = cnt.as<uint32_t>(); a.tot = tot.as<unsigned long long>();
@@ -658,7 +654,7 @@ static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const vo
         HapArgs hp;
         hp.loci = dl.as<uint32_t>(); hp.di_slot = ds.as<int32_t>(); hp.tri_slot = ds.as<int32_t>() + n_acc; hp.n_loci = (uint32_t)n_acc;
         hp.di = dd.as<uint32_t>(); hp.tri = dt.as<uint32_t>();
-        const int64_t nb = std::min<int64_t>((a.n_reads + 255) / 256, 8192);
+        const int64_t nb = std::min<int64_t>((a.rs.n_reads + 255) / 256, 8192);
         hipLaunchKernelGGL(k4k_snp_haplotypes, dim3((unsigned)nb), dim3(256), 0, st, a, hp);
         std::vector<uint32_t> hd((size_t)n_di * 17), ht((size_t)n_tri * 65);
         K4_HIP(ix, hipMemcpyAsync(hd.data(), dd.p, hd.size() * 4, hipMemcpyDeviceToHost, st));

@@ -1,5 +1,7 @@
-// kit4b_amd/csrc/k4_stage.h -- what a device stage needs on the host side: its scratch buffers, the rocPRIM calls with their
-// temporary, the list of the reads a predicate accepts, a counter brought down.  A new stage starts from here.
+// kit4b_amd/csrc/k4_stage.h -- what a device stage needs on the host side: the view of the records it works on, its scratch
+// buffers, the rocPRIM calls with their temporary, the list of the reads a predicate accepts, a counter brought down.
+// A new stage starts from here: k4s_read_set checks its record arguments and fills the K4ReadSet (k4_device.h) its kernels take by
+// value; they ask the view whether a read was accepted and where its hit is, and take a read out of the report with its reject().
 //
 // The helpers are templates over the buffer type B: K4DevBuf (k4_pool.h), or the pool-backed Buf of k4_io.hip (k4_pool.h says why the
 // ingest / emit stages free nothing).  B needs `p`, `hipError_t alloc(size_t)` (which lets go of what it held) and `as<T>()`;
@@ -10,6 +12,7 @@
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
+#include "k4_device.h"
 #include "k4_internal.h"
 #include "k4_pool.h"
 
@@ -25,6 +28,31 @@ int k4s_read_back(k4_index* ix, T* host, const void* dev, hipStream_t st) {
   static_assert(std::is_trivially_copyable<T>::value, "k4s_read_back copies bytes");
   K4_HIP(ix, hipMemcpyAsync(host, dev, sizeof(T), hipMemcpyDeviceToHost, st));
   K4_HIP(ix, hipStreamSynchronize(st));
+  return K4_OK;
+}
+
+// What a stage needs of its record arguments besides the records themselves (SE: d_rr, PE: d_pe): the SE hit slots, the read
+// bytes with their offsets and lengths, the SE second segments.  K4RS_UNITS: the count is in SE reads or PE pairs, not in reads.
+enum : unsigned { K4RS_HITS = 1u, K4RS_READS = 2u, K4RS_SEG2 = 4u, K4RS_UNITS = 8u };
+
+// The record arguments of a C ABI entry point, checked and made into the view.  An entry point that takes one d_rr_or_pe hands it
+// in as d_rr and as d_pe.  What the stage does not need may be null and is carried along as it came; the side of the other record
+// form is left out of the view.  An empty call (n <= 0) is not refused.
+inline int k4s_read_set(k4_index* ix, int pe, int64_t n, const void* d_rr, const void* d_hits, int32_t max_ml, const void* d_pe,
+                        const void* d_seg2, const void* d_reads, const void* d_offs, const void* d_lens, unsigned need, K4ReadSet* rs) {
+  const bool records = pe ? d_pe != nullptr : (d_rr && (!(need & K4RS_HITS) || (d_hits && max_ml >= 1)));
+  const bool bytes = !(need & K4RS_READS) || (d_reads && d_offs && d_lens);
+  const bool segs = !(need & K4RS_SEG2) || d_seg2;
+  if (n > 0 && !(records && bytes && segs)) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
+  rs->rr = pe ? nullptr : (k4_read_result*)d_rr;
+  rs->hits = pe ? nullptr : (k4_hit*)d_hits;
+  rs->max_ml = (int)max_ml;
+  rs->pr = pe ? (k4_pe_read*)d_pe : nullptr;
+  rs->seg2 = pe ? nullptr : (const k4_seg2*)d_seg2;
+  rs->reads = (uint8_t*)d_reads;
+  rs->offs = (const uint64_t*)d_offs;
+  rs->lens = (const uint32_t*)d_lens;
+  rs->n_reads = (pe && (need & K4RS_UNITS)) ? 2 * n : n;
   return K4_OK;
 }
 

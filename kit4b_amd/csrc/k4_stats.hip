@@ -38,30 +38,11 @@
 
 namespace {
 
-// where the reported alignment of read i lives: SE results + hit slot 0, or the PE records
-struct StatSrc {
-  const k4_read_result* rr;
-  const k4_hit* hits;
-  const k4_pe_read* pr;
-  int max_ml;
-};
-K4_DEV bool k4d_stat_accepted(const StatSrc& s, int64_t i, k4_hit& h) {
-  if (s.pr) {
-    if (s.pr[i].nar != K4_NAR_ACCEPTED) return false;
-    h = s.pr[i].hit;
-    return true;
-  }
-  if (s.rr[i].nar != K4_NAR_ACCEPTED) return false;
-  h = s.hits[i * s.max_ml];
-  return true;
-}
-
 // WriteSubDist (:6469-6525).  The read is walked in read orientation from ReadOfs + TrimLeft (Seg[0].ReadOfs is 0) to
 // ReadLen - TrimRight; the target window is AdjHitLen bases from AdjStartLoci, reverse complemented for a '-' hit, and is walked
 // from its first element.
-__global__ void __launch_bounds__(256) k4k_sub_dist(K4DevIndex ix, StatSrc s, int64_t n, const uint8_t* __restrict__ reads,
-                                                    const uint64_t* __restrict__ offs, const uint32_t* __restrict__ lens, uint32_t Lt,
-                                                    uint32_t L, unsigned long long* __restrict__ g_insts,
+__global__ void __launch_bounds__(256) k4k_sub_dist(K4DevIndex ix, const K4ReadSet s, uint32_t Lt, uint32_t L,
+                                                    unsigned long long* __restrict__ g_insts,
                                                     unsigned long long* __restrict__ g_subs, unsigned long long* __restrict__ g_msub,
                                                     uint32_t* __restrict__ g_maxlen) {
   extern __shared__ uint32_t lds[];
@@ -74,13 +55,13 @@ __global__ void __launch_bounds__(256) k4k_sub_dist(K4DevIndex ix, StatSrc s, in
   uint32_t wmax = 0;
   // An untrimmed read puts positions lane and 64 + lane on this lane every time: those are counted in registers (per band, no
   // atomic at all) and added to the LDS table once, behind the loop.  Trimmed reads and positions from 128 on go to LDS directly.
-  uint32_t ri[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, rs[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-  for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n; i += (int64_t)gridDim.x * 4) {
+  uint32_t ri[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, rsub[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+  for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < s.n_reads; i += (int64_t)gridDim.x * 4) {
     k4_hit h;
-    if (!k4d_stat_accepted(s, i, h)) continue;
+    if (!s.accepted(i, h)) continue;
     if (h.ext & (K4_EXT_INDEL | K4_EXT_SPLICE)) continue;  // FlagSegs: a two-segment read is sloughed (:6480)
     if (h.chrom_id == 0 || h.chrom_id > ix.n_entries) continue;
-    const uint32_t len = lens[i];
+    const uint32_t len = s.lens[i];
     const uint32_t tl = K4_HIT_TRIM_LEFT(h), tr = K4_HIT_TRIM_RIGHT(h);
     wmax = max(wmax, len);
     const bool minus = h.strand == '-';
@@ -92,7 +73,7 @@ __global__ void __launch_bounds__(256) k4k_sub_dist(K4DevIndex ix, StatSrc s, in
     if (adj_len <= 0) end = 0;
     else if (end > start + (uint32_t)adj_len) end = start + (uint32_t)adj_len;
     if (end > L) end = L;
-    const uint8_t* rd = reads + offs[i];
+    const uint8_t* rd = s.reads + s.offs[i];
     const uint64_t base = ix.ent_start[h.chrom_id - 1] + adj_start;
     // position p of the read: its quality band, and whether it differs from the target
     auto look = [&](uint32_t p, uint32_t& band) -> bool {
@@ -115,7 +96,7 @@ __global__ void __launch_bounds__(256) k4k_sub_dist(K4DevIndex ix, StatSrc s, in
 #pragma unroll
           for (uint32_t q = 0; q < 4; q++) {
             ri[c][q] += band == q ? 1u : 0u;
-            rs[c][q] += (band == q && mm) ? 1u : 0u;
+            rsub[c][q] += (band == q && mm) ? 1u : 0u;
           }
           nm += mm ? 1u : 0u;
         }
@@ -147,7 +128,7 @@ __global__ void __launch_bounds__(256) k4k_sub_dist(K4DevIndex ix, StatSrc s, in
 #pragma unroll
     for (uint32_t q = 0; q < 4; q++) {
       if (ri[c][q] && p < Lt) atomicAdd(tab + ((size_t)q * Lt + p) * 2, ri[c][q]);  // (p < end <= L <= Lt whenever it was counted)
-      if (rs[c][q] && p < Lt) atomicAdd(tab + ((size_t)q * Lt + p) * 2 + 1, rs[c][q]);
+      if (rsub[c][q] && p < Lt) atomicAdd(tab + ((size_t)q * Lt + p) * 2 + 1, rsub[c][q]);
     }
   }
   if (lane == 0 && wmax) atomicMax(smax, wmax);
@@ -165,24 +146,22 @@ __global__ void __launch_bounds__(256) k4k_sub_dist(K4DevIndex ix, StatSrc s, in
 }
 
 // ReportTargHitCnts (:5586-5612): per accepted read the leading trimer of the read as loaded, and AdjAlignStartLoci
-__global__ void __launch_bounds__(256) k4k_targ_counts(uint32_t n_entries, StatSrc s, int64_t n, const uint8_t* __restrict__ reads,
-                                                       const uint64_t* __restrict__ offs, const uint32_t* __restrict__ lens, int use_lds,
-                                                       uint64_t* __restrict__ keys, uint32_t* __restrict__ g_ent,
+__global__ void __launch_bounds__(256) k4k_targ_counts(uint32_t n_entries, const K4ReadSet s, int use_lds, uint64_t* __restrict__ keys, uint32_t* __restrict__ g_ent,
                                                        unsigned long long* __restrict__ g_nacc) {
   extern __shared__ uint32_t lds[];
   const uint32_t n_cnt = use_lds ? n_entries * K4_STATS_ENT_W : 0u;
   for (uint32_t k = threadIdx.x; k < n_cnt; k += 256) lds[k] = 0;
   __syncthreads();
   uint32_t mine = 0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < s.n_reads; i += (int64_t)gridDim.x * 256) {
     k4_hit h;
-    const bool acc = k4d_stat_accepted(s, i, h) && h.chrom_id >= 1 && h.chrom_id <= n_entries;
+    const bool acc = s.accepted(i, h) && h.chrom_id >= 1 && h.chrom_id <= n_entries;
     if (!acc) { keys[i] = ~0ull; continue; }
     keys[i] = ((uint64_t)h.chrom_id << 32) | k4d_adj_start(h);
     mine++;
     uint32_t slot = 0, tri = 0;
-    if (lens[i] >= 3) {  // (no read is that short behind the length filter; one that were counts as indeterminate)
-      const uint8_t* rd = reads + offs[i];
+    if (s.lens[i] >= 3) {  // (no read is that short behind the length filter; one that were counts as indeterminate)
+      const uint8_t* rd = s.reads + s.offs[i];
       bool indet = false;
       for (int q = 0; q < 3 && !indet; q++) {
         const uint32_t b = rd[q] & 7u;
@@ -274,8 +253,8 @@ extern "C" int k4_align_stats_dev(k4_index* ix, int pe, int64_t n_reads, int32_t
   if (!ix || !out) return K4_ERR_PARAMS;
   memset(out, 0, sizeof(*out));
   if (n_reads < 0 || max_read_len < 0 || max_read_len > K4_MAX_READ_LEN) return k4_fail(ix, K4_ERR_PARAMS, "read count / length out of range");
-  if (n_reads > 0 && ((pe ? !d_pe : (!d_rr || !d_hits || max_ml < 1)) || !d_reads || !d_offs || !d_lens))
-    return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
+  K4ReadSet src;
+  K4_TRY(k4s_read_set(ix, pe, n_reads, d_rr, d_hits, max_ml, d_pe, nullptr, d_reads, d_offs, d_lens, K4RS_HITS | K4RS_READS, &src));
   if (n_reads >= 0xFFFFFF00ll) return k4_fail(ix, K4_ERR_PARAMS, "at most 2^32-256 reads per call");
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
@@ -318,17 +297,15 @@ extern "C" int k4_align_stats_dev(k4_index* ix, int pe, int64_t n_reads, int32_t
   uint32_t* g_maxlen = (uint32_t*)(g_nacc + 1);
   uint32_t* g_ent = g_maxlen + 2;
   uint32_t* g_uniq = g_ent + (size_t)ne * K4_STATS_ENT_W;
-  StatSrc src = {pe ? nullptr : (const k4_read_result*)d_rr, pe ? nullptr : (const k4_hit*)d_hits, pe ? (const k4_pe_read*)d_pe : nullptr,
-                 (int)max_ml};
   const uint32_t Lt = std::min<uint32_t>((L + 63u) & ~63u, K4_STATS_LDS_LEN);
-  hipLaunchKernelGGL(k4k_sub_dist, dim3(grid_for(4 * 64, n_reads)), dim3(256), (8 * Lt + K4_STATS_LDS_MSUB + 1) * 4, st, ix->d, src, n_reads,
-                     (const uint8_t*)d_reads, (const uint64_t*)d_offs, (const uint32_t*)d_lens, Lt, L, g_insts, g_subs, g_msub, g_maxlen);
+  hipLaunchKernelGGL(k4k_sub_dist, dim3(grid_for(4 * 64, n_reads)), dim3(256), (8 * Lt + K4_STATS_LDS_MSUB + 1) * 4, st, ix->d, src, Lt, L,
+                     g_insts, g_subs, g_msub, g_maxlen);
   if ((rc = k4_check_hip(ix, hipGetLastError(), "k4k_sub_dist")) != K4_OK) return fail(rc);
   if ((rc = k4_check_hip(ix, k0.alloc((size_t)n_reads * 8), "hipMalloc(stats keys)")) != K4_OK) return fail(rc);
   if ((rc = k4_check_hip(ix, k1.alloc((size_t)n_reads * 8), "hipMalloc(stats keys)")) != K4_OK) return fail(rc);
   const int use_lds = (size_t)ne * K4_STATS_ENT_W <= K4_STATS_LDS_ENT ? 1 : 0;
   hipLaunchKernelGGL(k4k_targ_counts, dim3(grid_for(256 * 16, n_reads)), dim3(256), use_lds ? (size_t)ne * K4_STATS_ENT_W * 4 : 0, st, ne, src,
-                     n_reads, (const uint8_t*)d_reads, (const uint64_t*)d_offs, (const uint32_t*)d_lens, use_lds, k0.as<uint64_t>(), g_ent, g_nacc);
+                     use_lds, k0.as<uint64_t>(), g_ent, g_nacc);
   if ((rc = k4_check_hip(ix, hipGetLastError(), "k4k_targ_counts")) != K4_OK) return fail(rc);
   rocprim::double_buffer<uint64_t> kk(k0.as<uint64_t>(), k1.as<uint64_t>());
   if ((rc = k4s_sort_keys<K4DevBuf>(ix, kk, (size_t)n_reads, 0u, 64u, st)) != K4_OK) return fail(rc);

@@ -21,7 +21,7 @@
 //                                                                                  -> k4_pipeline_site_prefs, k4_write_site_prefs
 //   chromosome filters   CKAligner::FiltByChroms :4025-4091 (kalign -Z / -z; here --chromexclude / --chromeinclude)
 //                                                                                  -> k4_chrom_accept_mask, k4_filter_chroms_dev
-// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k -6 -O -5 -8 -9 (plus -g <gpu>, -S <i/N> read slice);
+// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k -6 -O -5 -8 -9 -g (plus -@ <gpu>, -S <i/N> read slice);
 // kalign's -Z / -z go by their long names --chromexclude / --chromeinclude (the letters mean something else here).
 #include <errno.h>
 #include <fcntl.h>
@@ -99,12 +99,18 @@ struct Opts {
   int bam_level = 6;                // -z <0..9>: BGZF deflate level of a .bam output (WriteBAMReadHits is called with 6, KAligner.cpp:759)
 };
 
+// a device block of the program's own: freed when its holder goes, whatever way the function that allocated it is left
+struct DevFree { void operator()(void* p) const { k4_free_device(p); } };
+typedef std::unique_ptr<void, DevFree> DevBlock;
+int alloc_dev(k4_index* ix, uint64_t bytes, DevBlock& b) {
+  void* p = nullptr;
+  const int rc = k4_alloc_device(ix, bytes, &p);
+  b.reset(p);
+  return rc;
+}
+
 struct Parsed {  // one reads file after k4_parse_fastx_dev: everything lives in HBM
-  void* d_text = nullptr;
-  void* d_offs = nullptr;
-  void* d_lens = nullptr;
-  void* d_noff = nullptr;
-  void* d_nlen = nullptr;
+  DevBlock text, offs, lens, noff, nlen;
   uint64_t n = 0, bases = 0;
   uint32_t max_len = 0;
 };
@@ -118,6 +124,10 @@ struct Parsed {  // one reads file after k4_parse_fastx_dev: everything lives in
     }                                                                     \
   } while (0)
 
+typedef std::chrono::steady_clock::time_point TimePoint;
+TimePoint now() { return std::chrono::steady_clock::now(); }
+double secs(TimePoint a, TimePoint b) { return std::chrono::duration<double>(b - a).count(); }
+
 // upload the text and parse it on the device, in pieces below the 4 GiB limit of one call; at most max_records records;
 // *consumed = text bytes that belonged to them (the rest is resubmitted in front of the next batch)
 int load_reads(k4_index* ix, const uint8_t* text, uint64_t T, int final_text, int64_t max_records, void* d_reads, uint64_t reads_base,
@@ -127,12 +137,12 @@ int load_reads(k4_index* ix, const uint8_t* text, uint64_t T, int final_text, in
   const bool fastq = text[0] == '@';
   const uint64_t nl = (uint64_t)std::count(text, text + T, (uint8_t)'\n');
   const int64_t cap = std::min<int64_t>((int64_t)((nl + 1) / (fastq ? 4 : 2) + 4), max_records > 0 ? max_records : INT64_MAX);
-  CK(k4_alloc_device(ix, T + 16, &P.d_text));
-  CK(k4_copy_to_device(ix, P.d_text, text, T));
-  CK(k4_alloc_device(ix, (uint64_t)cap * 8, &P.d_offs));
-  CK(k4_alloc_device(ix, (uint64_t)cap * 4, &P.d_lens));
-  CK(k4_alloc_device(ix, (uint64_t)cap * 8, &P.d_noff));
-  CK(k4_alloc_device(ix, (uint64_t)cap * 4, &P.d_nlen));
+  CK(alloc_dev(ix, T + 16, P.text));
+  CK(k4_copy_to_device(ix, P.text.get(), text, T));
+  CK(alloc_dev(ix, (uint64_t)cap * 8, P.offs));
+  CK(alloc_dev(ix, (uint64_t)cap * 4, P.lens));
+  CK(alloc_dev(ix, (uint64_t)cap * 8, P.noff));
+  CK(alloc_dev(ix, (uint64_t)cap * 4, P.nlen));
   uint64_t pos = 0;
   const uint64_t piece = 3ull << 30;
   int fmt = 0;
@@ -140,9 +150,9 @@ int load_reads(k4_index* ix, const uint8_t* text, uint64_t T, int final_text, in
     const uint64_t len = std::min(piece, T - pos);
     const int final_chunk = final_text && pos + len == T;
     k4_parse_info info;
-    CK(k4_parse_fastx_dev(ix, (const uint8_t*)P.d_text + pos, len, pos, final_chunk, fmt, cap - (int64_t)P.n, d_reads,
-                          reads_base + P.bases, (uint8_t*)P.d_offs + 8 * P.n, (uint8_t*)P.d_lens + 4 * P.n,
-                          (uint8_t*)P.d_noff + 8 * P.n, (uint8_t*)P.d_nlen + 4 * P.n, &info, nullptr));
+    CK(k4_parse_fastx_dev(ix, (const uint8_t*)P.text.get() + pos, len, pos, final_chunk, fmt, cap - (int64_t)P.n, d_reads,
+                          reads_base + P.bases, (uint8_t*)P.offs.get() + 8 * P.n, (uint8_t*)P.lens.get() + 4 * P.n,
+                          (uint8_t*)P.noff.get() + 8 * P.n, (uint8_t*)P.nlen.get() + 4 * P.n, &info, nullptr));
     if (info.format) fmt = (int)info.format;
     if (info.consumed == 0) break;  // nothing but an incomplete tail
     P.n += info.n_records;
@@ -152,10 +162,6 @@ int load_reads(k4_index* ix, const uint8_t* text, uint64_t T, int final_text, in
   }
   *consumed = pos;
   return K4_OK;
-}
-void free_parsed(Parsed& P) {
-  for (void* q : {P.d_text, P.d_offs, P.d_lens, P.d_noff, P.d_nlen}) k4_free_device(q);
-  P = Parsed();
 }
 
 // the reads files of one end, read in portions as one text (a file that lacks its last newline gets one): buf holds the
@@ -199,6 +205,7 @@ struct Stream {
   }
   void drop(uint64_t n) { buf.erase(buf.begin(), buf.begin() + (ptrdiff_t)std::min<uint64_t>(n, buf.size())); }
   void close() { if (f) gzclose(f); f = nullptr; }
+  ~Stream() { close(); }
 };
 
 // ---- the pipelined (default) mode: one reader thread per end fills the library's pinned ring buffers ----------------------
@@ -214,101 +221,124 @@ uint64_t file_size(const std::string& path) {
   struct stat st;
   return stat(path.c_str(), &st) == 0 ? (uint64_t)st.st_size : 0;
 }
-// plain files: the range [off, off+len) by `nt` concurrent pread()s (tmpfs / page cache deliver more than one thread can take)
-bool pread_parallel(int fd, uint64_t off, uint8_t* dst, uint64_t len, int nt) {
-  if (len < (8u << 20) || nt <= 1) {
-    uint64_t done = 0;
-    while (done < len) {
-      const ssize_t g = pread(fd, dst + done, len - done, (off_t)(off + done));
-      if (g <= 0) return false;
+// [off, off + len) of a file read into, or written from, `mem` by nt threads side by side (tmpfs / the page cache deliver and
+// take more than one thread can move); less than 8 MB goes in one piece
+template <bool kWrite> bool io_parallel(int fd, uint8_t* mem, uint64_t off, uint64_t len, int nt) {
+  if (len < (8u << 20) || nt < 1) nt = 1;
+  std::atomic<bool> ok(true);
+  auto part = [&](int t) {
+    const uint64_t b = len * (uint64_t)(t + 1) / nt;
+    for (uint64_t done = len * (uint64_t)t / nt; done < b;) {
+      const ssize_t g = kWrite ? pwrite(fd, mem + done, b - done, (off_t)(off + done)) : pread(fd, mem + done, b - done, (off_t)(off + done));
+      if (g <= 0) { ok = false; return; }
       done += (uint64_t)g;
     }
-    return true;
-  }
-  std::atomic<bool> ok(true);
+  };
   std::vector<std::thread> th;
-  for (int t = 0; t < nt; t++)
-    th.emplace_back([&, t] {
-      const uint64_t a = len * t / nt, b = len * (t + 1) / nt;
-      uint64_t done = a;
-      while (done < b) {
-        const ssize_t g = pread(fd, dst + done, b - done, (off_t)(off + done));
-        if (g <= 0) { ok = false; return; }
-        done += (uint64_t)g;
-      }
-    });
+  for (int t = 1; t < nt; t++) th.emplace_back(part, t);
+  part(0);
   for (std::thread& x : th) x.join();
   return ok;
 }
-// every file of one end, in order, into the pipeline; a file that lacks its last newline gets one (as Stream does)
-int feed_end(k4_pipeline* pl, int end, const std::vector<std::string>& files, int io_threads, double* secs_read) {
+// One end's text on its way into the pipeline's pinned ring buffers: room for bytes (or put), the newline a file lacks, the
+// final chunk.  The clock is the reading time: it stands still while the writer waits for a free buffer or hands one over.
+struct ChunkWriter {
+  k4_pipeline* pl;
+  int end;
   void* buf = nullptr;
   uint64_t cap = 0, used = 0;
-  uint8_t last = '\n';
-  auto t0 = std::chrono::steady_clock::now();
+  uint8_t last = '\n';  // the last byte written
   double busy = 0;
-  auto flush = [&](int fin) -> int {
-    busy += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    int rc = k4_pipeline_submit(pl, end, used, fin);
-    buf = nullptr; used = 0;
-    t0 = std::chrono::steady_clock::now();
-    return rc;
-  };
-  for (size_t f = 0; f < files.size(); f++) {
-    const bool gz = is_gzip(files[f]);
-    gzFile g = nullptr;
-    int fd = -1;
-    uint64_t fsz = 0, fpos = 0;
-    if (gz) {
-      g = gzopen(files[f].c_str(), "rb");
-      if (!g) return K4_ERR_OPEN_FILE;
-      gzbuffer(g, 4u << 20);
-    } else {
-      fd = open(files[f].c_str(), O_RDONLY);
-      if (fd < 0) return K4_ERR_OPEN_FILE;
-      fsz = file_size(files[f]);
+  TimePoint t0 = now();
+  ChunkWriter(k4_pipeline* p, int e) : pl(p), end(e) {}
+  int room(uint8_t** p, uint64_t* n) {  // at least one free byte
+    if (!buf) {
+      busy += secs(t0, now());
+      const int rc = k4_pipeline_acquire(pl, end, &buf, &cap);
+      t0 = now();
+      used = 0;
+      if (rc != K4_OK) return rc;
     }
-    for (;;) {
-      if (!buf) {
-        busy += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        int rc = k4_pipeline_acquire(pl, end, &buf, &cap);  // (waiting for a free buffer is not reading time)
-        t0 = std::chrono::steady_clock::now();
-        if (rc != K4_OK) return rc;
-        used = 0;
-      }
-      uint64_t got = 0;
-      if (gz) {
-        const int r = gzread(g, (uint8_t*)buf + used, (unsigned)std::min<uint64_t>(cap - used, 1u << 30));
-        if (r < 0) return K4_ERR_FILE_ACCESS;
-        got = (uint64_t)r;
-      } else {
-        got = std::min<uint64_t>(cap - used, fsz - fpos);
-        if (got && !pread_parallel(fd, fpos, (uint8_t*)buf + used, got, io_threads)) return K4_ERR_FILE_ACCESS;
-        fpos += got;
-      }
-      if (got == 0) break;  // end of this file
-      used += got;
-      last = ((uint8_t*)buf)[used - 1];
-      if (used == cap) { int rc = flush(0); if (rc != K4_OK) return rc; }
-    }
-    if (gz) gzclose(g); else close(fd);
-    if (last != '\n' && f + 1 < files.size()) {  // the next file starts on a line of its own
-      if (!buf) { int rc = k4_pipeline_acquire(pl, end, &buf, &cap); if (rc != K4_OK) return rc; used = 0; }
-      ((uint8_t*)buf)[used++] = '\n';
-      last = '\n';
-      if (used == cap) { int rc = flush(0); if (rc != K4_OK) return rc; }
-    }
+    *p = (uint8_t*)buf + used;
+    *n = cap - used;
+    return K4_OK;
   }
-  if (!buf) {  // the final (possibly empty) chunk still has to be announced
-    int rc = k4_pipeline_acquire(pl, end, &buf, &cap);
-    if (rc != K4_OK) return rc;
+  int wrote(uint64_t n, int fin = 0) {  // n bytes of the room were filled; a full buffer (or the final one) goes to the pipeline
+    used += n;
+    if (n) last = ((uint8_t*)buf)[used - 1];
+    if (used < cap && !fin) return K4_OK;
+    busy += secs(t0, now());
+    const int rc = k4_pipeline_submit(pl, end, used, fin);
+    t0 = now();
+    buf = nullptr;
     used = 0;
+    return rc;
   }
-  int rc = flush(1);
-  if (secs_read) *secs_read = busy;
+  int put(const uint8_t* src, uint64_t n) {
+    while (n) {
+      uint8_t* p;
+      uint64_t free_bytes;
+      int rc = room(&p, &free_bytes);
+      if (rc != K4_OK) return rc;
+      const uint64_t take = std::min(n, free_bytes);
+      memcpy(p, src, take);
+      src += take; n -= take;
+      if ((rc = wrote(take)) != K4_OK) return rc;
+    }
+    return K4_OK;
+  }
+  int end_file(bool more) {  // text follows a file that lacks its last newline: the next record starts on a line of its own
+    const uint8_t nl = '\n';
+    return more && last != '\n' ? put(&nl, 1) : K4_OK;
+  }
+  int finish(int rc, double* secs_read) {  // the final (possibly empty) chunk still has to be announced
+    uint8_t* p;
+    uint64_t n;
+    if (rc == K4_OK && (rc = room(&p, &n)) == K4_OK) rc = wrote(0, 1);
+    if (secs_read) *secs_read = busy + secs(t0, now());
+    return rc;
+  }
+};
+
+struct FileRange { std::string path; uint64_t a, b, file_len; };  // the bytes [a, b) of an uncompressed file
+int feed_range(ChunkWriter& w, const FileRange& fr, int io_threads) {
+  const int fd = open(fr.path.c_str(), O_RDONLY);
+  if (fd < 0) return K4_ERR_OPEN_FILE;
+  int rc = K4_OK;
+  uint8_t* p;
+  uint64_t n;
+  for (uint64_t pos = fr.a; pos < fr.b && rc == K4_OK && (rc = w.room(&p, &n)) == K4_OK; pos += n) {
+    n = std::min(n, fr.b - pos);
+    rc = io_parallel<false>(fd, p, pos, n, io_threads) ? w.wrote(n) : K4_ERR_FILE_ACCESS;
+  }
+  close(fd);
   return rc;
 }
-
+int feed_gzip(ChunkWriter& w, const std::string& path) {
+  gzFile g = gzopen(path.c_str(), "rb");
+  if (!g) return K4_ERR_OPEN_FILE;
+  gzbuffer(g, 4u << 20);
+  int rc = K4_OK, got = 1;
+  uint8_t* p;
+  uint64_t n;
+  while (rc == K4_OK && got > 0 && (rc = w.room(&p, &n)) == K4_OK) {  // (0: the end of this file)
+    got = gzread(g, p, (unsigned)std::min<uint64_t>(n, 1u << 30));
+    rc = got < 0 ? K4_ERR_FILE_ACCESS : w.wrote((uint64_t)got);
+  }
+  gzclose(g);
+  return rc;
+}
+// every file of one end, in order, into the pipeline; a file that lacks its last newline gets one (as Stream does)
+int feed_end(k4_pipeline* pl, int end, const std::vector<std::string>& files, int io_threads, double* secs_read) {
+  ChunkWriter w(pl, end);
+  int rc = K4_OK;
+  for (size_t f = 0; f < files.size() && rc == K4_OK; f++) {
+    const uint64_t len = file_size(files[f]);
+    rc = is_gzip(files[f]) ? feed_gzip(w, files[f]) : feed_range(w, FileRange{files[f], 0, len, len}, io_threads);
+    if (rc == K4_OK) rc = w.end_file(f + 1 < files.size());
+  }
+  return w.finish(rc, secs_read);
+}
 
 // ---- k4align -G: one rank process per GPU ---------------------------------------------------------------------------------------
 #define K4_MAX_RANKS 64
@@ -422,48 +452,18 @@ bool slice_files(const std::vector<std::string>& files, int n_ranks, std::vector
 
 // the byte ranges [a, b) of uncompressed files, one after the other, into the pipeline; a range that ends a file which lacks its
 // last newline gets one (the next file's first record starts on a line of its own)
-struct FileRange { std::string path; uint64_t a, b, file_len; };
 int feed_ranges(k4_pipeline* pl, int end, const std::vector<FileRange>& ranges, int io_threads, double* secs_read) {
-  double busy = 0;
-  void* buf = nullptr;
-  uint64_t cap = 0, used = 0;
+  ChunkWriter w(pl, end);
   int rc = K4_OK;
-  auto flush = [&](int fin) { const int r = k4_pipeline_submit(pl, end, used, fin); buf = nullptr; used = 0; return r; };
   for (size_t k = 0; k < ranges.size() && rc == K4_OK; k++) {
     const FileRange& fr = ranges[k];
     if (fr.b <= fr.a) continue;
-    const int fd = open(fr.path.c_str(), O_RDONLY);
-    if (fd < 0) return K4_ERR_OPEN_FILE;
-    uint64_t pos = fr.a;
-    uint8_t last = '\n';
-    while (pos < fr.b && rc == K4_OK) {
-      if (!buf) { if ((rc = k4_pipeline_acquire(pl, end, &buf, &cap)) != K4_OK) break; used = 0; }
-      const uint64_t len = std::min<uint64_t>(cap - used, fr.b - pos);
-      auto t0 = std::chrono::steady_clock::now();
-      if (len && !pread_parallel(fd, pos, (uint8_t*)buf + used, len, io_threads)) { rc = K4_ERR_FILE_ACCESS; break; }
-      busy += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      pos += len;
-      used += len;
-      if (len) last = ((uint8_t*)buf)[used - 1];
-      if (used == cap) rc = flush(0);
-    }
-    close(fd);
-    if (rc == K4_OK && fr.b == fr.file_len && last != '\n') {
-      bool more = false;
-      for (size_t q = k + 1; q < ranges.size(); q++) more |= ranges[q].b > ranges[q].a;
-      if (more) {
-        if (!buf) { if ((rc = k4_pipeline_acquire(pl, end, &buf, &cap)) != K4_OK) break; used = 0; }
-        ((uint8_t*)buf)[used++] = '\n';
-        if (used == cap) rc = flush(0);
-      }
-    }
+    rc = feed_range(w, fr, io_threads);
+    bool more = false;
+    for (size_t q = k + 1; q < ranges.size(); q++) more |= ranges[q].b > ranges[q].a;
+    if (rc == K4_OK && fr.b == fr.file_len) rc = w.end_file(more);
   }
-  if (rc == K4_OK) {
-    if (!buf) { if ((rc = k4_pipeline_acquire(pl, end, &buf, &cap)) != K4_OK) return rc; used = 0; }
-    rc = flush(1);  // the final (possibly empty) chunk
-  }
-  if (secs_read) *secs_read = busy;
-  return rc;
+  return w.finish(rc, secs_read);
 }
 
 // Compressed input cannot be cut by byte offsets: every rank inflates the whole stream and keeps the record blocks dealt to it --
@@ -471,32 +471,15 @@ int feed_ranges(k4_pipeline* pl, int end, const std::vector<FileRange>& ranges, 
 // mates stay together.  (Equal sort keys then come out in block order, not in load order: the reference leaves that order open.)
 #define K4_DEAL_RECORDS (1u << 18)
 int feed_dealt(k4_pipeline* pl, int end, const std::vector<std::string>& files, int rank, int n_ranks, double* secs_read) {
-  void* buf = nullptr;
-  uint64_t cap = 0, used = 0;
+  ChunkWriter w(pl, end);
   int rc = K4_OK;
-  auto t00 = std::chrono::steady_clock::now();
-  double waited = 0;
-  auto put = [&](const uint8_t* p, uint64_t n) {  // bytes of this rank's records into the pipeline
-    while (n && rc == K4_OK) {
-      if (!buf) {
-        auto w0 = std::chrono::steady_clock::now();
-        rc = k4_pipeline_acquire(pl, end, &buf, &cap);
-        waited += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
-        used = 0;
-        if (rc != K4_OK) return;
-      }
-      const uint64_t take = std::min<uint64_t>(n, cap - used);
-      memcpy((uint8_t*)buf + used, p, take);
-      used += take; p += take; n -= take;
-      if (used == cap) { rc = k4_pipeline_submit(pl, end, used, 0); buf = nullptr; used = 0; }
-    }
-  };
   std::vector<uint8_t> chunk((size_t)16 << 20);
   uint64_t rec = 0;      // records begun so far, over all files
   uint32_t lines = 0;    // FASTQ: lines of the current record seen so far
   int fastq = -1;
   bool at_line_start = true;
   uint8_t last = '\n';
+  auto mine_is = [&](uint64_t r) { return (r / K4_DEAL_RECORDS) % (uint64_t)n_ranks == (uint64_t)rank; };
   for (size_t f = 0; f < files.size() && rc == K4_OK; f++) {
     gzFile g = gzopen(files[f].c_str(), "rb");  // (reads plain files as they are)
     if (!g) return K4_ERR_OPEN_FILE;
@@ -508,8 +491,8 @@ int feed_dealt(k4_pipeline* pl, int end, const std::vector<std::string>& files, 
       if (fastq < 0) fastq = chunk[0] == '@' ? 1 : 0;
       // runs of bytes that belong to one record block go out (or not) together
       int run_start = 0;
-      bool mine = rec ? ((rec - 1) / K4_DEAL_RECORDS) % (uint64_t)n_ranks == (uint64_t)rank : false;  // the record we are inside
-      for (int q = 0; q < got; q++) {
+      bool mine = rec ? mine_is(rec - 1) : false;  // the record we are inside
+      for (int q = 0; q < got && rc == K4_OK; q++) {
         const uint8_t ch = chunk[(size_t)q];
         bool starts = false;
         if (at_line_start) {
@@ -517,9 +500,9 @@ int feed_dealt(k4_pipeline* pl, int end, const std::vector<std::string>& files, 
           else if (ch == '>') starts = true;
         }
         if (starts) {
-          const bool m2 = (rec / K4_DEAL_RECORDS) % (uint64_t)n_ranks == (uint64_t)rank;
+          const bool m2 = mine_is(rec);
           if (m2 != mine) {
-            if (mine) put(chunk.data() + run_start, (uint64_t)(q - run_start));
+            if (mine) rc = w.put(chunk.data() + run_start, (uint64_t)(q - run_start));
             run_start = q;
             mine = m2;
           }
@@ -528,26 +511,20 @@ int feed_dealt(k4_pipeline* pl, int end, const std::vector<std::string>& files, 
         at_line_start = ch == '\n';
         if (fastq && at_line_start) lines = (lines + 1) & 3u;
       }
-      if (mine) put(chunk.data() + run_start, (uint64_t)(got - run_start));
+      if (mine && rc == K4_OK) rc = w.put(chunk.data() + run_start, (uint64_t)(got - run_start));
       last = chunk[(size_t)got - 1];
       if (rc != K4_OK) break;
     }
     gzclose(g);
     if (last != '\n' && f + 1 < files.size()) {  // the next file starts on a line of its own
-      const bool mine = rec ? ((rec - 1) / K4_DEAL_RECORDS) % (uint64_t)n_ranks == (uint64_t)rank : false;
       const uint8_t nl = '\n';
-      if (mine) put(&nl, 1);
+      if (rec && mine_is(rec - 1) && rc == K4_OK) rc = w.put(&nl, 1);
       at_line_start = true;
       if (fastq == 1) lines = (lines + 1) & 3u;
       last = '\n';
     }
   }
-  if (rc == K4_OK) {
-    if (!buf) { if ((rc = k4_pipeline_acquire(pl, end, &buf, &cap)) != K4_OK) return rc; used = 0; }
-    rc = k4_pipeline_submit(pl, end, used, 1);
-  }
-  if (secs_read) *secs_read = std::chrono::duration<double>(std::chrono::steady_clock::now() - t00).count() - waited;
-  return rc;
+  return w.finish(rc, secs_read);
 }
 
 const char* kNarAbbr[20] = {"NA", "AA", "EN", "NL", "MH", "ML", "ET", "OJ", "OM", "DP", "DS", "FC", "PR", "UI", "OI", "UP", "IS", "IT", "NP", "LC"};
@@ -602,24 +579,8 @@ static GlibcRand draws;
 
 static int run_multi_gpu(Opts& o, bool pe, int max_ml);
 
-// A run that fails after it created its output leaves no artefact behind (a SAM sized in advance and padded with NULs, a BAM
-// without its end-of-file block), and the pipeline's threads and pinned buffers are gone before main returns.
-struct RunGuard {
-  k4_pipeline** pl;
-  std::vector<std::string> made;
-  bool ok = false;
-  ~RunGuard() {
-    if (ok) return;
-    if (pl && *pl) { k4_pipeline_close(*pl); *pl = nullptr; }
-    for (const std::string& f : made) {
-      struct stat sb;
-      if (lstat(f.c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) remove(f.c_str());  // (never a device node or /dev/stdout's link)
-    }
-  }
-};
-
-// <file cut at its last '.'> + suffix (CUtility::AppendFileNameSuffix), as k4_write_align_stats names the side files
-static std::string stats_side_name(const std::string& path, const char* suffix) {
+// <file cut at its last '.'> + suffix (CUtility::AppendFileNameSuffix): the side files of -O, -S and -M3
+static std::string side_name(const std::string& path, const char* suffix) {
   std::string stem = path;
   for (size_t q = stem.size(); q > 0; q--) {
     if (stem[q - 1] == '.') { stem.resize(q - 1); break; }
@@ -627,26 +588,112 @@ static std::string stats_side_name(const std::string& path, const char* suffix) 
   }
   return stem + suffix;
 }
-
-// one process, one GPU: the whole run, or rank o.rank of a -G run
-static int run_rank(Opts& o, const bool pe, const int max_ml) {
-  auto t0 = std::chrono::steady_clock::now();
-  k4_index* ix = nullptr;
-  k4_comm* comm = nullptr;
-  int rc;
-  const bool multi = o.n_ranks > 1 || o.shared;
-  const bool chatty = o.rank == 0;  // only rank 0 of a -G run reports
-  const char* fault = multi ? getenv("K4ALIGN_FAULT") : nullptr;  // tests of run_multi_gpu: "<rank>:<stage>"
-  const int fault_rank = fault ? atoi(fault) : -1;
-  const char* fault_stage = fault && strchr(fault, ':') ? strchr(fault, ':') + 1 : "";
-  if (multi && fault) {
-    if (fault_rank == o.rank && strcmp(fault_stage, "start") == 0) { fprintf(stderr, "k4align: rank %d: injected fault at start\n", o.rank); return 3; }
-    const char* peers = getenv("K4ALIGN_FAULT_PEERS");
-    if (fault_rank != o.rank && peers && strcmp(peers, "block") == 0)
-      for (;;) pause();  // what a rank blocked in a collective looks like to the parent
+static bool ends_in(const std::string& name, const char* ext4) { return name.size() >= 4 && strcasecmp(name.c_str() + name.size() - 4, ext4) == 0; }
+static bool create_empty(const std::string& path) {  // create / truncate
+  FILE* fp = fopen(path.c_str(), "wb");
+  if (fp) fclose(fp);
+  return fp != nullptr;
+}
+// Every buffer to the file of its name.  All are tried; the first name that failed comes back (none: empty).  A `guarded` file
+// that was created is one a failed run removes again.  big_by > 0: a buffer of 64 MB or more is written by that many threads side
+// by side (the SNP coverage WIG of a genome at low coverage runs to gigabytes); everything else is written in order, pipes included.
+struct NamedBuf { std::string name; const void* p; uint64_t n; bool guarded; };
+static std::string write_files(const std::vector<NamedBuf>& files, std::vector<std::string>& made, int big_by) {
+  std::string failed;
+  for (const NamedBuf& f : files) {
+    FILE* fp = fopen(f.name.c_str(), "wb");
+    bool ok = fp != nullptr;
+    if (ok && f.guarded) made.push_back(f.name);
+    if (ok) ok = big_by > 0 && f.n >= (64u << 20) ? io_parallel<true>(fileno(fp), (uint8_t*)f.p, 0, f.n, big_by) : fwrite(f.p, 1, f.n, fp) == f.n;
+    if (fp && fclose(fp) != 0) ok = false;
+    if (!ok && failed.empty()) failed = f.name;
   }
-  if (multi) {
-    // the communicator id: rank 0 makes it, the others pick it up from the shared mapping
+  return failed;
+}
+
+// a device block into a file, 256 MB at a time; a write that failed shows in ferror(fp)
+static int download(k4_index* ix, const void* d_src, uint64_t bytes, FILE* fp) {
+  std::vector<char> piece((size_t)std::min<uint64_t>(bytes, 256ull << 20));
+  for (uint64_t off = 0; off < bytes && !ferror(fp); off += piece.size()) {
+    const uint64_t len = std::min<uint64_t>(piece.size(), bytes - off);
+    const int rc = k4_copy_to_host(ix, piece.data(), (const char*)d_src + off, len);
+    if (rc != K4_OK) return rc;
+    fwrite(piece.data(), 1, len, fp);
+  }
+  return K4_OK;
+}
+
+// What a run holds.  However the run is left, they go in this order: the pipeline (its threads and pinned buffers); the outputs
+// a failed run created (a SAM sized in advance and padded with NULs, a BAM without its end-of-file block: no artefact stays
+// behind); the index -- closing it joins the library thread that may still be loading the .sfx, so main never returns and
+// tears the runtime down under it.  The communicator goes behind the index, and only when this rank has met its peers at the
+// closing barrier: a rank that fails must not enter a collective or a destroy its peers are not in (run_multi_gpu ends them).
+struct RunHeld {
+  k4_index* ix = nullptr;
+  k4_pipeline* pl = nullptr;
+  k4_comm* comm = nullptr;
+  bool met_peers = false;
+  std::vector<std::string> made;
+  bool ok = false;
+  void reset_pipeline() { if (pl) k4_pipeline_close(pl); pl = nullptr; }
+  ~RunHeld() {
+    reset_pipeline();
+    for (const std::string& f : made) {
+      struct stat sb;
+      if (!ok && lstat(f.c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) remove(f.c_str());  // (never a device node or /dev/stdout's link)
+    }
+    if (ix) k4_close(ix);
+    if (comm && met_peers) k4_comm_close(comm);
+  }
+};
+
+// One process, one GPU: the whole run, or rank o.rank of a -G run.  The state the steps of run_rank share; what it holds is the
+// base, so the device blocks and tables below are gone before the index is.
+struct Run : RunHeld {
+  Opts& o;
+  const bool pe, multi, chatty;  // (only rank 0 of a -G run reports)
+  const int max_ml;
+  const TimePoint t0 = now();
+  TimePoint t_open;
+  k4_info_t info;
+  int mcl = 0, slides = 0;
+  std::unique_ptr<k4_loci_constraint, void (*)(void*)> loci_tbl{nullptr, k4_free_host};  // -5
+  int32_t n_loci = 0;
+  std::vector<uint8_t> chrom_accept, hit_chrom;  // per sequence of the index: --chromexclude / --chromeinclude; has alignments
+  k4_kalign_params kp;
+  k4_pe_params pp;
+  bool two_seg = false, pipelined = false, bam_out = false;
+  k4_sam_stats tot;
+  uint64_t n_under = 0, n_over = 0, n_units = 0, my_lines = 0;
+  double s_read = 0, s_parse = 0, s_align = 0, s_write = 0;
+  k4_pipeline_view v;        // the pipelined modes: all reads of the run, aligned
+  uint64_t pl_sam_bytes = 0;
+  DevBlock keep_sam;         // -Z, -S i/N: the SAM body of the single batch stays on the device
+  uint64_t keep_bytes = 0;
+  std::vector<std::string> parts;  // -b: the batches' sorted bodies
+
+  Run(Opts& opts, bool paired, int ml) : o(opts), pe(paired), multi(opts.n_ranks > 1 || opts.shared), chatty(opts.rank == 0), max_ml(ml) {
+    memset(&tot, 0, sizeof(tot));
+    memset(&v, 0, sizeof(v));
+  }
+  bool few_seqs() const { return info.n_entries <= (uint32_t)o.rpt_sq_thres; }  // m_MaxRptSAMSeqsThres, KAligner.cpp:5785-5821
+  double index_secs() const { return std::max(secs(t0, t_open), k4_open_seconds(ix)); }
+
+  // ---- the index: one GPU, or a rank of a -G run ---------------------------------------------------------------------------------
+  // RCCL bring-up: rank 0 makes the communicator id, the others pick it up from the shared mapping; rank 0 reads the .sfx once;
+  // sequence + suffix array reach the peers over xGMI; every rank builds its own tables.  K4ALIGN_FAULT=<rank>:<stage> is for the
+  // tests of run_multi_gpu (see there)
+  int open_rank_index() {
+    int rc;
+    const char* fault = getenv("K4ALIGN_FAULT");
+    const int fault_rank = fault ? atoi(fault) : -1;
+    const char* fault_stage = fault && strchr(fault, ':') ? strchr(fault, ':') + 1 : "";
+    if (fault) {
+      if (fault_rank == o.rank && strcmp(fault_stage, "start") == 0) { fprintf(stderr, "k4align: rank %d: injected fault at start\n", o.rank); return 3; }
+      const char* peers = getenv("K4ALIGN_FAULT_PEERS");
+      if (fault_rank != o.rank && peers && strcmp(peers, "block") == 0)
+        for (;;) pause();  // what a rank blocked in a collective looks like to the parent
+    }
     MultiShared* sh = o.shared;
     if (o.rank == 0) {
       if ((rc = k4_comm_unique_id(sh->id)) != K4_OK) { fprintf(stderr, "k4align: ncclGetUniqueId failed\n"); sh->failed = 1; return 2; }
@@ -654,82 +701,173 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
     } else
       while (!sh->id_ready.load()) { if (sh->failed.load()) return 2; usleep(1000); }
     if ((rc = k4_comm_init(o.gpu, o.rank, o.n_ranks, sh->id, &comm)) != K4_OK) { fprintf(stderr, "k4align: rank %d: RCCL communicator failed (%d)\n", o.rank, rc); sh->failed = 1; return 2; }
-    // rank 0 reads the .sfx once; sequence + suffix array reach the peers over xGMI; every rank builds its own tables
     rc = k4_comm_open_index(comm, o.rank == 0 ? o.sfx.c_str() : nullptr, 0, &ix);
     if (rc != K4_OK) { fprintf(stderr, "k4align: rank %d: index broadcast failed: %s (%d)\n", o.rank, k4_comm_last_error(comm), rc); sh->failed = 1; return 2; }
     if (fault_rank == o.rank && strcmp(fault_stage, "index") == 0) { fprintf(stderr, "k4align: rank %d: injected fault behind the index broadcast\n", o.rank); return 3; }
-  } else {
-    // (the arrays load on a thread of the library while the reads are read: k4_open_wait below, or the pipeline's own)
-    rc = k4_open_async(o.sfx.c_str(), o.gpu, 0, &ix);
-    if (rc != K4_OK) { fprintf(stderr, "k4align: unable to load '%s': %s (%d)\n", o.sfx.c_str(), k4_global_error(), rc); return 2; }
+    return 0;
   }
-  k4_info_t info;
-  k4_info(ix, &info);
-  if (o.q_method != 3) CK(k4_set_fastq_quality(ix, o.q_method));
-  // SetMaxIter by sensitivity, KAligner.cpp:373-388
-  k4_set_max_iter(ix, o.pmode == 2 ? 20000 : o.pmode == 1 ? 10000 : o.pmode == 0 ? 5000 : 2500);
-  int slides = 0;
-  const int mcl = k4_min_core_len(ix, o.pmode, &slides);
-  if (chatty)
-    fprintf(stderr, "k4align: index '%s' %u sequences, %llu bp; minimum core size %dbp%s\n", info.dataset, info.n_entries,
-            (unsigned long long)info.tot_seqs_len, mcl, multi ? " (read once, sent to the other GPUs over xGMI)" : "");
-  auto t_open = std::chrono::steady_clock::now();
-  // -5: the constraints are checked against the index's sequences before any read is loaded (KAligner.cpp:4619-4628)
-  std::unique_ptr<k4_loci_constraint, void (*)(void*)> loci_tbl(nullptr, k4_free_host);
-  int32_t n_loci = 0;
-  if (!o.loci_file.empty()) {
-    k4_loci_constraint* t = nullptr;
-    if ((rc = k4_load_loci_constraints(ix, o.loci_file.c_str(), &t, &n_loci, nullptr)) != K4_OK) {
-      fprintf(stderr, "k4align: %s (%d)\n", k4_last_error(ix), rc);
-      k4_close(ix);  // (joins the thread that is still loading the index)
-      return rc == K4_ERR_OPEN_FILE ? 2 : 1;
+  int open_index() {
+    int rc;
+    if (multi) {
+      if ((rc = open_rank_index()) != 0) return rc;
+    } else {
+      // (the arrays load on a thread of the library while the reads are read: k4_open_wait in derive_params, or the pipeline's own)
+      rc = k4_open_async(o.sfx.c_str(), o.gpu, 0, &ix);
+      if (rc != K4_OK) { fprintf(stderr, "k4align: unable to load '%s': %s (%d)\n", o.sfx.c_str(), k4_global_error(), rc); return 2; }
     }
-    loci_tbl.reset(t);
-    if (chatty) fprintf(stderr, "k4align: %d loci base constraints loaded from '%s'\n", (int)n_loci, o.loci_file.c_str());
+    k4_info(ix, &info);
+    hit_chrom.assign(info.n_entries + 1, 0);
+    if (o.q_method != 3) CK(k4_set_fastq_quality(ix, o.q_method));
+    // SetMaxIter by sensitivity, KAligner.cpp:373-388
+    k4_set_max_iter(ix, o.pmode == 2 ? 20000 : o.pmode == 1 ? 10000 : o.pmode == 0 ? 5000 : 2500);
+    mcl = k4_min_core_len(ix, o.pmode, &slides);
+    if (chatty)
+      fprintf(stderr, "k4align: index '%s' %u sequences, %llu bp; minimum core size %dbp%s\n", info.dataset, info.n_entries,
+              (unsigned long long)info.tot_seqs_len, mcl, multi ? " (read once, sent to the other GPUs over xGMI)" : "");
+    t_open = now();
+    return 0;
   }
-  // --chromexclude / --chromeinclude: one decision per sequence of the index, made here once
-  std::vector<uint8_t> chrom_accept;
-  if (!o.chrom_excl.empty() || !o.chrom_incl.empty()) {
-    std::vector<const char*> inc, exc;
-    for (const std::string& q : o.chrom_incl) inc.push_back(q.c_str());
-    for (const std::string& q : o.chrom_excl) exc.push_back(q.c_str());
-    chrom_accept.assign((size_t)info.n_entries + 1, 0);
-    if ((rc = k4_chrom_accept_mask(ix, (int32_t)inc.size(), inc.data(), (int32_t)exc.size(), exc.data(), chrom_accept.data())) != K4_OK) {
-      fprintf(stderr, "k4align: %s (%d)\n", k4_last_error(ix), rc);
-      k4_close(ix);
+  // -5 and --chromexclude / --chromeinclude, checked against the index's sequences before any read is loaded (KAligner.cpp:4619-4628)
+  int load_constraints() {
+    int rc;
+    if (!o.loci_file.empty()) {
+      k4_loci_constraint* t = nullptr;
+      if ((rc = k4_load_loci_constraints(ix, o.loci_file.c_str(), &t, &n_loci, nullptr)) != K4_OK) {
+        fprintf(stderr, "k4align: %s (%d)\n", k4_last_error(ix), rc);
+        return rc == K4_ERR_OPEN_FILE ? 2 : 1;
+      }
+      loci_tbl.reset(t);
+      if (chatty) fprintf(stderr, "k4align: %d loci base constraints loaded from '%s'\n", (int)n_loci, o.loci_file.c_str());
+    }
+    if (!o.chrom_excl.empty() || !o.chrom_incl.empty()) {  // one decision per sequence of the index, made here once
+      std::vector<const char*> inc, exc;
+      for (const std::string& q : o.chrom_incl) inc.push_back(q.c_str());
+      for (const std::string& q : o.chrom_excl) exc.push_back(q.c_str());
+      chrom_accept.assign((size_t)info.n_entries + 1, 0);
+      if ((rc = k4_chrom_accept_mask(ix, (int32_t)inc.size(), inc.data(), (int32_t)exc.size(), exc.data(), chrom_accept.data())) != K4_OK) {
+        fprintf(stderr, "k4align: %s (%d)\n", k4_last_error(ix), rc);
+        return 1;
+      }
+    }
+    return 0;
+  }
+  // the combinations that need the run's mode, the parameters of the alignment, and which input and output path this run takes
+  int derive_params() {
+    if ((o.ml_mode == 3 || o.ml_mode == 4) && (o.batch_mb > 0 || o.n_shards > 1)) {
+      fprintf(stderr, "k4align: -r3 / -r4 cluster over all reads of the run; they cannot be combined with -b or -S\n");
       return 1;
     }
+    if (o.batch_mb > 0 && o.n_shards > 1) { fprintf(stderr, "k4align: -S slices the whole input; it cannot be combined with -b\n"); return 1; }
+    if ((o.micro_indel || o.splice_junct) && (o.batch_mb > 0 || o.n_shards > 1)) {
+      fprintf(stderr, "k4align: -a / -A drop junctions no second read of the RUN supports; they cannot be combined with -b or -S\n");
+      return 1;
+    }
+    // -6: the reads are aligned with m_InitalAlignSubs (KAligner.cpp:245-248, :504, :607); everything else keeps the user's -s
+    const int align_subs = o.primer_subs > 0 ? std::min(o.max_subs + o.primer_subs, 15) : o.max_subs;
+    kp = {align_subs, o.min_edit, o.max_ns, o.pmode, o.align_strand /* K4_STRAND_*: the same codes as eALStrand */, max_ml,
+          o.ml_mode == 5 ? (o.best ? 4 : o.clamp ? 3 : 2) : o.ml_mode == 2 ? 2 : o.ml_mode != 0 ? 1 : 0,
+          mcl, slides, o.min_chimeric, o.micro_indel, o.splice_junct};
+    two_seg = o.micro_indel > 0 || o.splice_junct > 0;
+    pp = {o.pe_mode, o.pair_min, o.pair_max, o.pair_strand};
+    // default: the overlapped pipeline (k4_pipeline_*): reader threads -> pinned ring -> copy stream || parse + align on the
+    // compute stream; one global sort + SAM body at the end, handed out while its next pieces come down.
+    // -b <MB>: bounded memory, coordinate-sorted parts merged on the host; -S i/N: one slice of the reads (one process per GPU)
+    pipelined = o.batch_mb <= 0 && o.n_shards == 1 && !o.legacy;
+    bam_out = o.rank_bam || ends_in(o.out, ".bam");  // "-o x.bam": BGZF compressed BAM, any other extension SAM (KAlignerCL.cpp:857-866)
+    int rc;
+    if (!pipelined && !multi && (rc = k4_open_wait(ix)) != K4_OK) { fprintf(stderr, "k4align: unable to load '%s': %s (%d)\n", o.sfx.c_str(), k4_global_error(), rc); return 2; }
+    if (bam_out && (!pipelined || (multi && !o.rank_bam))) { fprintf(stderr, "k4align: BAM output is written by the pipelined modes (not with -b, -S, -Z)\n"); return 3; }
+    return 0;
   }
 
-  if ((o.ml_mode == 3 || o.ml_mode == 4) && (o.batch_mb > 0 || o.n_shards > 1)) {
-    fprintf(stderr, "k4align: -r3 / -r4 cluster over all reads of the run; they cannot be combined with -b or -S\n");
-    return 1;
+  // ---- the input, pipelined ------------------------------------------------------------------------------------------------------
+  int open_pipeline() {
+    for (const std::vector<std::string>* fs : {&o.in1, &o.in2})
+      for (const std::string& q : *fs) {
+        FILE* t = fopen(q.c_str(), "rb");
+        if (!t) { fprintf(stderr, "k4align: unable to open '%s'\n", q.c_str()); return 2; }
+        fclose(t);
+      }
+    k4_pipeline_params pp2;
+    memset(&pp2, 0, sizeof(pp2));
+    pp2.paired = pe ? 1 : 0; pp2.kp = kp; pp2.pe = pp; pp2.min_len = o.min_len; pp2.max_len = o.max_len;
+    pp2.chunk_bytes = (uint64_t)o.chunk_mb << 20;
+    for (int e = 0; e < (pe ? 2 : 1); e++) {
+      bool plain = true;
+      uint64_t tot_sz = 0;
+      for (const std::string& q : e ? o.in2 : o.in1) { plain &= !is_gzip(q); tot_sz += file_size(q) + 1; }
+      pp2.expect_text_bytes[e] = plain ? tot_sz : 0;
+    }
+    if (!o.stats_file.empty()) {  // created / truncated before the reads are loaded (KAligner.cpp:4705-4730); a failed run leaves none of the three
+      if (!create_empty(o.stats_file)) { fprintf(stderr, "k4align: unable to create/truncate output stats file '%s'\n", o.stats_file.c_str()); return 5; }
+      made.push_back(o.stats_file);
+      made.push_back(side_name(o.stats_file, ".AlignCntsDist.csv"));
+      if (pe) made.push_back(side_name(o.stats_file, ".GlobalPEInsertDist.csv"));
+      CK(k4_align_stats_collect(ix, 1));
+    }
+    if (!o.site_file.empty()) {  // created / truncated with the other outputs (KAligner.cpp:4471-4491); it stays empty when no read is accepted
+      if (!create_empty(o.site_file)) { fprintf(stderr, "k4align: unable to create/truncate site preferencing file '%s'\n", o.site_file.c_str()); return 5; }
+      made.push_back(o.site_file);
+    }
+    CK(k4_pipeline_open(ix, &pp2, &pl));
+    CK(k4_pipeline_set_trims(pl, o.trim5, o.trim3));
+    CK(k4_pipeline_set_sampling(pl, o.sample_nth));
+    return 0;
   }
-  if (o.batch_mb > 0 && o.n_shards > 1) { fprintf(stderr, "k4align: -S slices the whole input; it cannot be combined with -b\n"); return 1; }
-  if ((o.micro_indel || o.splice_junct) && (o.batch_mb > 0 || o.n_shards > 1)) {
-    fprintf(stderr, "k4align: -a / -A drop junctions no second read of the RUN supports; they cannot be combined with -b or -S\n");
-    return 1;
+  // -G over uncompressed files: reads are independent units, rank r aligns the r-th contiguous slice of the records (pairs stay
+  // together).  Rank 0 finds the slice boundaries (one pass over the files), every rank then reads only its own byte range
+  int rank_ranges(std::vector<FileRange> fr[2]) {
+    MultiShared* sh = o.shared;
+    if (o.rank == 0) {
+      uint64_t R = 0, R2 = 0;
+      std::vector<uint64_t> counts;
+      std::string why;
+      bool ok = slice_files(o.in1, o.n_ranks, counts, false, sh->slice_off[0], &R, o.io_threads, &why);
+      if (ok && pe) ok = o.in2.size() == o.in1.size() ? slice_files(o.in2, o.n_ranks, counts, true, sh->slice_off[1], &R2, o.io_threads, &why)
+                                                      : (why = "as many -u files as -i files are needed", false);
+      if (!ok) { fprintf(stderr, "k4align: unable to cut the reads into slices: %s\n", why.c_str()); sh->failed = 1; return 2; }
+      sh->n_records = R;
+      sh->slices_ready = 1;
+    } else
+      while (!sh->slices_ready.load()) { if (sh->failed.load()) return 2; usleep(1000); }
+    for (int e = 0; e < (pe ? 2 : 1); e++) {
+      const std::vector<std::string>& fl = e ? o.in2 : o.in1;
+      for (size_t f = 0; f < fl.size(); f++)
+        fr[e].push_back(FileRange{fl[f], sh->slice_off[e][f][o.rank], sh->slice_off[e][f][o.rank + 1], file_size(fl[f])});
+    }
+    return 0;
   }
-  // -6: the reads are aligned with m_InitalAlignSubs (KAligner.cpp:245-248, :504, :607); everything else keeps the user's -s
-  const int align_subs = o.primer_subs > 0 ? std::min(o.max_subs + o.primer_subs, 15) : o.max_subs;
-  k4_kalign_params kp = {align_subs, o.min_edit, o.max_ns, o.pmode, o.align_strand /* K4_STRAND_*: the same codes as eALStrand */, max_ml,
-                         o.ml_mode == 5 ? (o.best ? 4 : o.clamp ? 3 : 2) : o.ml_mode == 2 ? 2 : o.ml_mode != 0 ? 1 : 0,
-                         mcl, slides, o.min_chimeric, o.micro_indel, o.splice_junct};
-  const bool two_seg = o.micro_indel > 0 || o.splice_junct > 0;
-  k4_pe_params pp = {o.pe_mode, o.pair_min, o.pair_max, o.pair_strand};
-  k4_sam_stats tot;
-  memset(&tot, 0, sizeof(tot));
-  std::vector<uint8_t> hit_chrom(info.n_entries + 1, 0);
-  uint64_t n_under = 0, n_over = 0, n_units = 0;
-  double s_read = 0, s_parse = 0, s_align = 0, s_write = 0;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double>(b - a).count();
-  };
+  // one reader per end fills the pipeline (the second end on a thread of its own); then all reads of the run are aligned
+  int feed_pipeline() {
+    bool any_gz = false;  // a -G run: no byte offsets into a compressed stream, record blocks are dealt to the ranks
+    for (const std::string& q : o.in1) any_gz |= is_gzip(q);
+    for (const std::string& q : o.in2) any_gz |= is_gzip(q);
+    std::vector<FileRange> fr[2];
+    auto tr = now();
+    int rc;
+    if (multi && !any_gz && (rc = rank_ranges(fr)) != 0) return rc;
+    int rc_end[2] = {K4_OK, K4_OK};
+    double rd[2] = {0, 0};
+    auto feed = [&](int e) {
+      const std::vector<std::string>& files = e ? o.in2 : o.in1;
+      rc_end[e] = !multi  ? feed_end(pl, e, files, o.io_threads, &rd[e])
+                  : any_gz ? feed_dealt(pl, e, files, o.rank, o.n_ranks, &rd[e])
+                           : feed_ranges(pl, e, fr[e], o.io_threads, &rd[e]);
+    };
+    std::thread t2;
+    if (pe) t2 = std::thread(feed, 1);
+    feed(0);
+    if (pe) t2.join();
+    s_read = std::max(rd[0], rd[1]);
+    for (int e = 0; e < 2; e++)
+      if (rc_end[e] != K4_OK) { fprintf(stderr, "k4align: error reading the input (%d): %s\n", rc_end[e], k4_last_error(ix)); return 2; }
+    CK(k4_pipeline_wait_aligned(pl, &v));
+    s_parse = secs(tr, now()) - s_read;  // what the device side added behind the reading
+    return 0;
+  }
 
-  // the stages between alignment and report, over ALL reads of the run (CKAligner::Align, KAligner.cpp:615-686)
-  auto global_stages = [&](int64_t n, uint32_t max_len, void* d_rr, void* d_hits, void* d_seg2, void* d_pe, void* d_reads, void* d_offs,
-                           void* d_lens) -> int {
+  // ---- the stages between alignment and report, over ALL reads of the run (CKAligner::Align, KAligner.cpp:615-686) -----------------
+  int global_stages(int64_t n, uint32_t max_len, void* d_rr, void* d_hits, void* d_seg2, void* d_pe, void* d_reads, void* d_offs, void* d_lens) {
     if (n <= 0 || max_len == 0) return K4_OK;
     if (!pe) {
       if (o.ml_mode == 3 || o.ml_mode == 4) {  // AssignMultiMatches (KAligner.cpp:5092): clusters over all reads of the run
@@ -746,11 +884,10 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
         CK(k4_copy_to_host(ix, rr.data(), d_rr, (uint64_t)n * sizeof(k4_read_result)));
         for (int64_t i = 0; i < n; i++)
           if (rr[i].nar == K4_NAR_ACCEPTED && rr[i].num_hits >= 1) choice[i] = (uint32_t)(draws.next() % rr[i].num_hits);
-        void* d_choice = nullptr;
-        CK(k4_alloc_device(ix, (uint64_t)n * 4, &d_choice));
-        CK(k4_copy_to_device(ix, d_choice, choice.data(), (uint64_t)n * 4));
-        CK(k4_select_hits_dev(ix, n, max_ml, d_rr, d_hits, d_choice, nullptr));
-        k4_free_device(d_choice);
+        DevBlock d_choice;
+        CK(alloc_dev(ix, (uint64_t)n * 4, d_choice));
+        CK(k4_copy_to_device(ix, d_choice.get(), choice.data(), (uint64_t)n * 4));
+        CK(k4_select_hits_dev(ix, n, max_ml, d_rr, d_hits, d_choice.get(), nullptr));
       }
     }
     int64_t cnt = 0;
@@ -784,549 +921,347 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
       fprintf(stderr, "k4align: %lld orphan microInDel reads removed\n", (long long)cnt);
     }
     if (!chrom_accept.empty()) {  // FiltByChroms: behind the autotrim and the orphan filters, in front of every report (KAligner.cpp:693)
-      void* d_accept = nullptr;
-      CK(k4_alloc_device(ix, chrom_accept.size(), &d_accept));
-      CK(k4_copy_to_device(ix, d_accept, chrom_accept.data(), chrom_accept.size()));
-      rc = k4_filter_chroms_dev(ix, d_accept, pe ? 1 : 0, pe ? 2 * n : n, max_ml, pe ? d_pe : d_rr, d_hits, &cnt, nullptr);
-      k4_free_device(d_accept);
-      CK(rc);
+      DevBlock d_accept;
+      CK(alloc_dev(ix, chrom_accept.size(), d_accept));
+      CK(k4_copy_to_device(ix, d_accept.get(), chrom_accept.data(), chrom_accept.size()));
+      CK(k4_filter_chroms_dev(ix, d_accept.get(), pe ? 1 : 0, pe ? 2 * n : n, max_ml, pe ? d_pe : d_rr, d_hits, &cnt, nullptr));
       fprintf(stderr, "k4align: %lld matches removed by chromosome filtering\n", (long long)cnt);
     }
     return K4_OK;
-  };
+  }
 
+  // ---- the reports of the pipelined modes, in front of the alignments' own ---------------------------------------------------------
+  int write_unaligned() {  // ReportNoneAligned / ReportMultiAlign (KAligner.cpp:709-733)
+    for (int which = 0; which < 2; which++) {
+      const std::string& fn = which ? o.multi_file : o.none_file;
+      if (fn.empty()) continue;
+      char* txt = nullptr;
+      uint64_t nb = 0, nl = 0;
+      CK(k4_unaligned_fasta_dev(ix, pe ? 1 : 0, v.n_units, v.d_rr, v.d_pe, v.d_reads, v.d_offs, v.d_lens, &v.names, which, &txt, &nb, &nl, nullptr));
+      const std::string failed = write_files({{fn, txt, nb, false}}, made, 0);
+      k4_free_host(txt);
+      if (!failed.empty()) { fprintf(stderr, "k4align: unable to write %s\n", fn.c_str()); return 5; }
+      if (chatty) fprintf(stderr, "k4align: %llu %s reads written to %s\n", (unsigned long long)nl, which ? "multi-aligned" : "unalignable", fn.c_str());
+    }
+    return 0;
+  }
+  int write_pba() {  // genpba: ProcessSNPs in PBA mode is the report (KAligner.cpp:741-790); no SAM is written
+    auto ts = now();
+    k4_pba_files pf;
+    CK(k4_pba_run_dev(ix, pe ? 1 : 0, v.n_units, v.d_rr, v.d_hits, v.max_ml, v.d_pe, v.d_reads, v.d_offs, v.d_lens, o.experiment_id.c_str(),
+                      o.readset_id.c_str(), &pf, nullptr));
+    const std::string wig = side_name(o.out, ".covsegs.wig");  // (KAligner.cpp:4341)
+    const std::string failed = write_files({{o.out, pf.pba, pf.pba_bytes, true}, {wig, pf.wig, pf.wig_bytes, true}}, made, 0);
+    k4_free_host(pf.pba); k4_free_host(pf.wig);
+    if (!failed.empty()) { fprintf(stderr, "k4align: unable to write %s\n", failed.c_str()); return 5; }
+    if (chatty) fprintf(stderr, "k4align: packed base alleles of %llu sequences (%llu bytes) written to %s, coverage to %s in %.2fs\n",
+                        (unsigned long long)pf.n_chroms, (unsigned long long)pf.pba_bytes, o.out.c_str(), wig.c_str(), secs(ts, now()));
+    ok = true;
+    return 0;
+  }
+  int write_snps() {  // ProcessSNPs (KAligner.cpp:768-790 calls it behind the alignment report): the SNP file and its side files
+    auto ts = now();
+    const bool vcf = ends_in(o.snp_file, ".vcf");  // VCF instead of the CSV (KAligner.cpp:186-187)
+    k4_snp_files sf;
+    k4_snp_files2 sf2;
+    memset(&sf2, 0, sizeof(sf2));
+    const bool more = o.marker_len != 0 || !o.cent_file.empty();  // the marker and centroid files out of the same counts
+    if (more) {
+      k4_snp_opts so;
+      so.marker_len = o.marker_len; so.want_centroids = o.cent_file.empty() ? 0 : 1; so.marker_poly_thres = o.marker_poly_thres;
+      CK(k4_snp_run2_dev(ix, vcf ? 1 : 0, pe ? 1 : 0, v.n_units, v.d_rr, v.d_hits, v.max_ml, v.d_pe, v.d_reads, v.d_offs, v.d_lens, o.min_snp_reads,
+                         o.qvalue, o.snp_nonref_pcnt, &so, &sf2, nullptr));
+      sf = sf2.files;
+    } else
+      CK(k4_snp_run_dev(ix, vcf ? 1 : 0, pe ? 1 : 0, v.n_units, v.d_rr, v.d_hits, v.max_ml, v.d_pe, v.d_reads, v.d_offs, v.d_lens, o.min_snp_reads,
+                        o.qvalue, o.snp_nonref_pcnt, &sf, nullptr));
+    // (the side files: KAligner.cpp:4512, 4553-4554)
+    std::vector<NamedBuf> files = {{side_name(o.snp_file, ".covsegs.wig"), sf.wig, sf.wig_bytes, false},
+                                   {side_name(o.snp_file, ".disnp.csv"), sf.disnp, sf.disnp_bytes, false},
+                                   {side_name(o.snp_file, ".trisnp.csv"), sf.trisnp, sf.trisnp_bytes, false},
+                                   {o.snp_file, sf.snp, sf.snp_bytes, false}};
+    if (o.marker_len) files.push_back({o.snp_file + ".markers", sf2.markers, sf2.markers_bytes, true});  // (the name is appended, KAlignerCL.cpp:957-959)
+    if (!o.cent_file.empty()) files.push_back({o.cent_file, sf2.centroids, sf2.centroids_bytes, true});
+    const std::string failed = write_files(files, made, std::max(o.io_threads, 1));
+    k4_free_host(sf.snp); k4_free_host(sf.wig); k4_free_host(sf.disnp); k4_free_host(sf.trisnp);
+    k4_free_host(sf2.markers); k4_free_host(sf2.centroids);
+    if (!failed.empty()) { fprintf(stderr, "k4align: unable to write %s\n", failed.c_str()); return 5; }
+    if (chatty) fprintf(stderr, "k4align: SNP processing completed with %llu putative SNPs discovered, written to %s in %.2fs\n",
+                        (unsigned long long)sf.n_snps, o.snp_file.c_str(), secs(ts, now()));
+    if (chatty && o.marker_len) fprintf(stderr, "k4align: %llu marker sequences of %d bases written to %s.markers\n", (unsigned long long)sf2.n_markers,
+                                        o.marker_len, o.snp_file.c_str());
+    if (chatty && !o.cent_file.empty()) fprintf(stderr, "k4align: SNP centroid distribution written to %s\n", o.cent_file.c_str());
+    return 0;
+  }
+  int write_align_stats() {  // -O, behind every stage that can still drop a read: the counted reads are the reported ones
+    auto ts = now();
+    k4_align_stats as;
+    CK(k4_pipeline_align_stats(pl, &as));
+    const uint64_t loaded = (uint64_t)(pe ? 2 : 1) * ((uint64_t)v.n_units - v.n_under - v.n_over);
+    if (o.splice_junct > 0) {
+      // with -A and SAM output the reference has its splice junction file open (KAligner.cpp:4446), so WriteReadHits runs in front
+      // of WriteBAMReadHits (:745-757) and calls WriteSubDist for every read too (:6835): those counts come out doubled
+      for (uint64_t q = 0; q < 4ull * as.len_stride; q++) { as.q_insts[q] *= 2; as.q_subs[q] *= 2; }
+      for (uint64_t q = 0; q <= as.len_stride; q++) as.m_sub[q] *= 2;
+    }
+    const int rc = k4_write_align_stats(ix, &as, loaded, o.ml_mode, max_ml, pe ? 1 : 0, o.stats_file.c_str());
+    k4_free_align_stats(&as);
+    if (rc != K4_OK) { fprintf(stderr, "k4align: %s\n", k4_last_error(ix)); return 5; }
+    if (chatty) fprintf(stderr, "k4align: alignment statistics written to %s in %.2fs\n", o.stats_file.c_str(), secs(ts, now()));
+    return 0;
+  }
+  int write_site_prefs() {  // -8: ProcessSiteProbabilites runs in front of the writer (KAligner.cpp:743), over the reads it will report
+    auto ts = now();
+    k4_site_prefs sp;
+    CK(k4_pipeline_site_prefs(pl, o.site_ofs, &sp));
+    const int rc = k4_write_site_prefs(&sp, o.site_file.c_str());
+    k4_free_site_prefs(&sp);
+    if (rc != K4_OK) { fprintf(stderr, "k4align: %s\n", k4_global_error()); return 5; }
+    if (chatty) fprintf(stderr, "k4align: start site octamer preferences written to %s in %.2fs\n", o.site_file.c_str(), secs(ts, now()));
+    return 0;
+  }
+  int format_records() {  // the global sort and the SAM body / BAM records of all reads, on the device
+    // (a rank of a -G run numbers every sequence: the parent renumbers when it knows which ones any rank has hit)
+    const int bam_all_sq = (few_seqs() || o.rank_bam) ? 1 : 0;
+    if (bam_out && o.fmode == 1) CK(k4_pipeline_format_bam_all(pl, bam_all_sq, &tot, hit_chrom.data(), &pl_sam_bytes));
+    else if (bam_out) CK(k4_pipeline_format_bam(pl, bam_all_sq, &tot, hit_chrom.data(), &pl_sam_bytes));
+    else if (o.fmode == 1) CK(k4_pipeline_format_all(pl, &tot, hit_chrom.data(), &pl_sam_bytes));
+    else CK(k4_pipeline_format(pl, &tot, hit_chrom.data(), &pl_sam_bytes));
+    n_under = v.n_under; n_over = v.n_over; n_units = (uint64_t)v.n_units;
+    return 0;
+  }
+
+  // ---- the input, streamed (-b) or whole (-Z, -S i/N) -------------------------------------------------------------------------------
   // One batch: text holding whole records (the last one possibly cut when more text follows) -> records -> alignments ->
   // SAM body.  The body goes to `body` (a part file) or, for the single batch of the whole-input mode, stays on the device.
-  void* keep_sam = nullptr;
-  uint64_t keep_bytes = 0;
-  auto run_batch = [&](const uint8_t* t1, uint64_t T1, int fin1, const uint8_t* t2, uint64_t T2, int fin2, FILE* body,
-                       uint64_t* used1, uint64_t* used2) -> int {
+  int run_batch(const uint8_t* t1, uint64_t T1, int fin1, const uint8_t* t2, uint64_t T2, int fin2, FILE* body, uint64_t* used1, uint64_t* used2) {
     *used1 = *used2 = 0;
     auto ta = now();
-    void* d_reads = nullptr;
-    CK(k4_alloc_device(ix, T1 + T2 + 64, &d_reads));
+    DevBlock d_reads, d_offs, d_lens, d_rr, d_hits, d_pe, d_seg2;
+    CK(alloc_dev(ix, T1 + T2 + 64, d_reads));
     Parsed p1, p2;
-    CK(load_reads(ix, t1, T1, fin1, 0, d_reads, 0, p1, used1));
+    CK(load_reads(ix, t1, T1, fin1, 0, d_reads.get(), 0, p1, used1));
     if (pe) {
-      CK(load_reads(ix, t2, T2, fin2, (int64_t)std::max<uint64_t>(p1.n, 1), d_reads, p1.bases, p2, used2));
+      CK(load_reads(ix, t2, T2, fin2, (int64_t)std::max<uint64_t>(p1.n, 1), d_reads.get(), p1.bases, p2, used2));
       if (p2.n < p1.n) {  // this portion of the mates' file holds fewer records: keep the pairs both files delivered
         if (fin2 && fin1) { fprintf(stderr, "k4align: fewer PE2 than PE1 reads\n"); return 3; }
         const int64_t n2 = (int64_t)p2.n;
-        free_parsed(p1);
-        free_parsed(p2);
-        if (n2 == 0) { k4_free_device(d_reads); *used1 = *used2 = 0; return K4_OK; }
-        CK(load_reads(ix, t1, T1, fin1, n2, d_reads, 0, p1, used1));
-        CK(load_reads(ix, t2, T2, fin2, n2, d_reads, p1.bases, p2, used2));
+        p1 = Parsed();
+        p2 = Parsed();
+        if (n2 == 0) { *used1 = *used2 = 0; return K4_OK; }
+        CK(load_reads(ix, t1, T1, fin1, n2, d_reads.get(), 0, p1, used1));
+        CK(load_reads(ix, t2, T2, fin2, n2, d_reads.get(), p1.bases, p2, used2));
       }
     }
-    const Parsed a1 = p1, a2 = p2;  // the allocations (p1 / p2 are narrowed to this process's slice below)
     // -S i/N: reads (pairs) are independent units; every process parses the whole input -- that is cheap
     // on the device -- and keeps its contiguous slice, so that the shards' SAM files merge back into load order (k4merge)
     const int64_t r0 = (int64_t)p1.n * o.shard / o.n_shards, r1 = (int64_t)p1.n * (o.shard + 1) / o.n_shards;
-    for (Parsed* q : {&p1, &p2}) {
-      if (!q->d_offs) continue;
-      q->d_offs = (uint8_t*)q->d_offs + 8 * r0; q->d_lens = (uint8_t*)q->d_lens + 4 * r0;
-      q->d_noff = (uint8_t*)q->d_noff + 8 * r0; q->d_nlen = (uint8_t*)q->d_nlen + 4 * r0;
-    }
+    auto from_r0 = [r0](const DevBlock& b, int width) -> void* { return b ? (uint8_t*)b.get() + width * r0 : nullptr; };
     const int64_t n = r1 - r0;
     const int64_t n_reads = pe ? 2 * n : n;
     uint64_t under = 0, over = 0;
     uint32_t max_len = 0;
-    void *d_offs = nullptr, *d_lens = nullptr;
-    CK(k4_alloc_device(ix, (uint64_t)(n_reads + 1) * 8, &d_offs));
-    CK(k4_alloc_device(ix, (uint64_t)(n_reads + 1) * 4, &d_lens));
-    CK(k4_prepare_reads_trim_dev(ix, pe ? 1 : 0, n, o.min_len, o.max_len, o.trim5, o.trim3, 1, 0, p1.d_offs, p1.d_lens, p2.d_offs, p2.d_lens, 0, d_offs, d_lens,
-                            &under, &over, &max_len, nullptr));
+    CK(alloc_dev(ix, (uint64_t)(n_reads + 1) * 8, d_offs));
+    CK(alloc_dev(ix, (uint64_t)(n_reads + 1) * 4, d_lens));
+    CK(k4_prepare_reads_trim_dev(ix, pe ? 1 : 0, n, o.min_len, o.max_len, o.trim5, o.trim3, 1, 0, from_r0(p1.offs, 8), from_r0(p1.lens, 4),
+                                 from_r0(p2.offs, 8), from_r0(p2.lens, 4), 0, d_offs.get(), d_lens.get(), &under, &over, &max_len, nullptr));
     auto tb = now();
-    // ---- align (ProcCoredApprox / ProcessPairedEnds) ---------------------------------------------------------------
-    void *d_rr = nullptr, *d_hits = nullptr, *d_pe = nullptr, *d_seg2 = nullptr;
-    if (n > 0 && max_len > 0) {
-      if (!pe) {
-        CK(k4_alloc_device(ix, (uint64_t)n * sizeof(k4_read_result), &d_rr));
-        CK(k4_alloc_device(ix, (uint64_t)n * max_ml * sizeof(k4_hit), &d_hits));
-        if (two_seg) CK(k4_alloc_device(ix, (uint64_t)n * sizeof(k4_seg2), &d_seg2));
-        CK(k4_reserve(ix, n, (int32_t)max_len, max_ml));
-        CK(k4_kalign_ext_batch_dev(ix, &kp, n, (int32_t)max_len, d_reads, d_offs, d_lens, d_rr, d_hits, d_seg2, nullptr));
-      } else {
-        CK(k4_alloc_device(ix, (uint64_t)2 * n * sizeof(k4_pe_read), &d_pe));
-        CK(k4_kalign_pe_batch_dev(ix, &kp, &pp, n, (int32_t)max_len, d_reads, d_offs, d_lens, d_pe, nullptr));
-      }
-      CK(global_stages(n, max_len, d_rr, d_hits, d_seg2, d_pe, d_reads, d_offs, d_lens));
-    }
-    // ---- SAM body on the device (k4_format_sam_dev) ------------------------------------------------------------------
+    // ---- align (ProcCoredApprox / ProcessPairedEnds), the global stages, the SAM body on the device (k4_format_sam_dev) ----------
     k4_sam_names nm;
     memset(&nm, 0, sizeof(nm));
-    nm.d_text[0] = p1.d_text; nm.d_name_off[0] = p1.d_noff; nm.d_name_len[0] = p1.d_nlen;
-    nm.d_text[1] = p2.d_text; nm.d_name_off[1] = p2.d_noff; nm.d_name_len[1] = p2.d_nlen;
+    nm.d_text[0] = p1.text.get(); nm.d_name_off[0] = from_r0(p1.noff, 8); nm.d_name_len[0] = from_r0(p1.nlen, 4);
+    nm.d_text[1] = p2.text.get(); nm.d_name_off[1] = from_r0(p2.noff, 8); nm.d_name_len[1] = from_r0(p2.nlen, 4);
     void* d_sam = nullptr;
     uint64_t sam_bytes = 0;
     k4_sam_stats stt;
     memset(&stt, 0, sizeof(stt));
     std::vector<uint8_t> hc(info.n_entries + 1, 0);
-    if (n > 0 && max_len > 0)
-      CK(k4_format_sam_ext_dev(ix, pe ? 1 : 0, n, d_rr, d_hits, max_ml, d_pe, d_seg2, d_reads, d_offs, d_lens, &nm, &d_sam, &sam_bytes,
-                               &stt, hc.data(), nullptr));
+    if (n > 0 && max_len > 0) {
+      if (!pe) {
+        CK(alloc_dev(ix, (uint64_t)n * sizeof(k4_read_result), d_rr));
+        CK(alloc_dev(ix, (uint64_t)n * max_ml * sizeof(k4_hit), d_hits));
+        if (two_seg) CK(alloc_dev(ix, (uint64_t)n * sizeof(k4_seg2), d_seg2));
+        CK(k4_reserve(ix, n, (int32_t)max_len, max_ml));
+        CK(k4_kalign_ext_batch_dev(ix, &kp, n, (int32_t)max_len, d_reads.get(), d_offs.get(), d_lens.get(), d_rr.get(), d_hits.get(), d_seg2.get(), nullptr));
+      } else {
+        CK(alloc_dev(ix, (uint64_t)2 * n * sizeof(k4_pe_read), d_pe));
+        CK(k4_kalign_pe_batch_dev(ix, &kp, &pp, n, (int32_t)max_len, d_reads.get(), d_offs.get(), d_lens.get(), d_pe.get(), nullptr));
+      }
+      const int rc = global_stages(n, max_len, d_rr.get(), d_hits.get(), d_seg2.get(), d_pe.get(), d_reads.get(), d_offs.get(), d_lens.get());
+      if (rc != K4_OK) return rc;
+      CK(k4_format_sam_ext_dev(ix, pe ? 1 : 0, n, d_rr.get(), d_hits.get(), max_ml, d_pe.get(), d_seg2.get(), d_reads.get(), d_offs.get(), d_lens.get(), &nm,
+                               &d_sam, &sam_bytes, &stt, hc.data(), nullptr));
+    }
+    keep_sam.reset(d_sam);
+    keep_bytes = sam_bytes;
     auto tc = now();
     for (int k = 0; k < 20; k++) tot.nar[k] += stt.nar[k];
     tot.plus += stt.plus; tot.minus += stt.minus; tot.n_lines += stt.n_lines;
     for (size_t c = 0; c < hc.size(); c++) hit_chrom[c] |= hc[c];
     n_under += under; n_over += over; n_units += (uint64_t)n;
     if (body) {
-      std::vector<char> piece((size_t)std::min<uint64_t>(sam_bytes, 256ull << 20));
-      for (uint64_t off = 0; off < sam_bytes; off += piece.size()) {
-        const uint64_t len = std::min<uint64_t>(piece.size(), sam_bytes - off);
-        CK(k4_copy_to_host(ix, piece.data(), (const char*)d_sam + off, len));
-        if (fwrite(piece.data(), 1, len, body) != len) { fprintf(stderr, "k4align: write failed\n"); return 5; }
-      }
-      k4_free_device(d_sam);
-    } else {
-      keep_sam = d_sam;
-      keep_bytes = sam_bytes;
+      CK(download(ix, d_sam, sam_bytes, body));
+      if (ferror(body)) { fprintf(stderr, "k4align: write failed\n"); return 5; }
+      keep_sam.reset();
     }
-    for (void* q : {d_reads, d_offs, d_lens, d_rr, d_hits, d_pe, d_seg2, a1.d_text, a1.d_offs, a1.d_lens, a1.d_noff, a1.d_nlen, a2.d_text,
-                    a2.d_offs, a2.d_lens, a2.d_noff, a2.d_nlen})
-      k4_free_device(q);
-    auto td = now();
-    s_parse += secs(ta, tb); s_align += secs(tb, tc); s_write += secs(tc, td);
+    s_parse += secs(ta, tb); s_align += secs(tb, tc); s_write += secs(tc, now());
     return K4_OK;
-  };
-
-  // ---- the input ---------------------------------------------------------------------------------------------------------------
-  // default: the overlapped pipeline (k4_pipeline_*): reader threads -> pinned ring -> copy stream || parse + align on the
-  // compute stream; one global sort + SAM body at the end, handed out while its next pieces come down.
-  // -b <MB>: bounded memory, coordinate-sorted parts merged on the host; -S i/N: one slice of the reads (one process per GPU)
-  k4_pipeline* pl = nullptr;
-  RunGuard guard{&pl};
-  uint64_t pl_sam_bytes = 0;
-  const bool pipelined = o.batch_mb <= 0 && o.n_shards == 1 && !o.legacy;
-  // "-o x.bam": BGZF compressed BAM, any other extension SAM (KAlignerCL.cpp:857-866)
-  const bool bam_out = o.rank_bam || (o.out.size() >= 4 && strcasecmp(o.out.c_str() + o.out.size() - 4, ".bam") == 0);
-  if (!pipelined && !multi && (rc = k4_open_wait(ix)) != K4_OK) { fprintf(stderr, "k4align: unable to load '%s': %s (%d)\n", o.sfx.c_str(), k4_global_error(), rc); return 2; }
-  if (bam_out && (!pipelined || (multi && !o.rank_bam))) { fprintf(stderr, "k4align: BAM output is written by the pipelined modes (not with -b, -S, -Z)\n"); return 3; }
-  if (pipelined) {
-    for (const std::vector<std::string>* fs : {&o.in1, &o.in2})
-      for (const std::string& q : *fs) {
-        FILE* t = fopen(q.c_str(), "rb");
-        if (!t) { fprintf(stderr, "k4align: unable to open '%s'\n", q.c_str()); return 2; }
-        fclose(t);
-      }
-    k4_pipeline_params pp2;
-    memset(&pp2, 0, sizeof(pp2));
-    pp2.paired = pe ? 1 : 0; pp2.kp = kp; pp2.pe = pp; pp2.min_len = o.min_len; pp2.max_len = o.max_len;
-    pp2.chunk_bytes = (uint64_t)o.chunk_mb << 20;
-    for (int e = 0; e < (pe ? 2 : 1); e++) {
-      bool plain = true;
-      uint64_t tot_sz = 0;
-      for (const std::string& q : e ? o.in2 : o.in1) { plain &= !is_gzip(q); tot_sz += file_size(q) + 1; }
-      pp2.expect_text_bytes[e] = plain ? tot_sz : 0;
-    }
-    if (!o.stats_file.empty()) {  // created / truncated before the reads are loaded (KAligner.cpp:4705-4730); a failed run leaves none of the three
-      FILE* fp = fopen(o.stats_file.c_str(), "wb");
-      if (!fp) { fprintf(stderr, "k4align: unable to create/truncate output stats file '%s'\n", o.stats_file.c_str()); return 5; }
-      fclose(fp);
-      guard.made.push_back(o.stats_file);
-      guard.made.push_back(stats_side_name(o.stats_file, ".AlignCntsDist.csv"));
-      if (pe) guard.made.push_back(stats_side_name(o.stats_file, ".GlobalPEInsertDist.csv"));
-      CK(k4_align_stats_collect(ix, 1));
-    }
-    if (!o.site_file.empty()) {  // created / truncated with the other outputs (KAligner.cpp:4471-4491); it stays empty when no read is accepted
-      FILE* fp = fopen(o.site_file.c_str(), "wb");
-      if (!fp) { fprintf(stderr, "k4align: unable to create/truncate site preferencing file '%s'\n", o.site_file.c_str()); return 5; }
-      fclose(fp);
-      guard.made.push_back(o.site_file);
-    }
-    CK(k4_pipeline_open(ix, &pp2, &pl));
-    CK(k4_pipeline_set_trims(pl, o.trim5, o.trim3));
-    CK(k4_pipeline_set_sampling(pl, o.sample_nth));
-    auto tr = now();
-    int rc_end[2] = {K4_OK, K4_OK};
-    double rd[2] = {0, 0};
-    std::thread t2;
-    std::vector<FileRange> fr[2];  // (outlive the reader thread of the second end)
-    if (multi) {
-      // reads are independent units: rank r aligns the r-th contiguous slice of the records (pairs stay together).  Rank 0
-      // finds the slice boundaries (one pass over the files), every rank then reads only its own byte range
-      MultiShared* sh = o.shared;
-      bool any_gz = false;
-      for (const std::string& q : o.in1) any_gz |= is_gzip(q);
-      for (const std::string& q : o.in2) any_gz |= is_gzip(q);
-      if (any_gz) {  // no byte offsets into a compressed stream: record blocks are dealt to the ranks
-        if (pe) t2 = std::thread([&] { rc_end[1] = feed_dealt(pl, 1, o.in2, o.rank, o.n_ranks, &rd[1]); });
-        rc_end[0] = feed_dealt(pl, 0, o.in1, o.rank, o.n_ranks, &rd[0]);
-      } else {
-        if (o.rank == 0) {
-          uint64_t R = 0, R2 = 0;
-          std::vector<uint64_t> counts;
-          std::string why;
-          bool ok = slice_files(o.in1, o.n_ranks, counts, false, sh->slice_off[0], &R, o.io_threads, &why);
-          if (ok && pe) ok = o.in2.size() == o.in1.size() ? slice_files(o.in2, o.n_ranks, counts, true, sh->slice_off[1], &R2, o.io_threads, &why)
-                                                          : (why = "as many -u files as -i files are needed", false);
-          if (!ok) { fprintf(stderr, "k4align: unable to cut the reads into slices: %s\n", why.c_str()); sh->failed = 1; return 2; }
-          sh->n_records = R;
-          sh->slices_ready = 1;
-        } else
-          while (!sh->slices_ready.load()) { if (sh->failed.load()) return 2; usleep(1000); }
-        for (int e = 0; e < (pe ? 2 : 1); e++) {
-          const std::vector<std::string>& fl = e ? o.in2 : o.in1;
-          for (size_t f = 0; f < fl.size(); f++)
-            fr[e].push_back(FileRange{fl[f], sh->slice_off[e][f][o.rank], sh->slice_off[e][f][o.rank + 1], file_size(fl[f])});
-        }
-        if (pe) t2 = std::thread([&] { rc_end[1] = feed_ranges(pl, 1, fr[1], o.io_threads, &rd[1]); });
-        rc_end[0] = feed_ranges(pl, 0, fr[0], o.io_threads, &rd[0]);
-      }
-    } else {
-      if (pe) t2 = std::thread([&] { rc_end[1] = feed_end(pl, 1, o.in2, o.io_threads, &rd[1]); });
-      rc_end[0] = feed_end(pl, 0, o.in1, o.io_threads, &rd[0]);
-    }
-    if (pe) t2.join();
-    s_read = std::max(rd[0], rd[1]);
-    for (int e = 0; e < 2; e++)
-      if (rc_end[e] != K4_OK) { fprintf(stderr, "k4align: error reading the input (%d): %s\n", rc_end[e], k4_last_error(ix)); return 2; }
-    k4_pipeline_view v;
-    CK(k4_pipeline_wait_aligned(pl, &v));
-    s_parse = secs(tr, now()) - s_read;  // what the device side added behind the reading
-    auto tg = now();
-    CK(global_stages(v.n_units, v.max_read_len, v.d_rr, v.d_hits, v.d_seg2, v.d_pe, v.d_reads, v.d_offs, v.d_lens));
-    for (int which = 0; which < 2; which++) {  // ReportNoneAligned / ReportMultiAlign (KAligner.cpp:709-733): before the alignments are reported
-      const std::string& fn = which ? o.multi_file : o.none_file;
-      if (fn.empty()) continue;
-      char* txt = nullptr;
-      uint64_t nb = 0, nl = 0;
-      CK(k4_unaligned_fasta_dev(ix, pe ? 1 : 0, v.n_units, v.d_rr, v.d_pe, v.d_reads, v.d_offs, v.d_lens, &v.names, which, &txt, &nb, &nl, nullptr));
-      FILE* fp = fopen(fn.c_str(), "wb");
-      bool ok = fp && fwrite(txt, 1, nb, fp) == nb;
-      if (fp && fclose(fp) != 0) ok = false;
-      k4_free_host(txt);
-      if (!ok) { fprintf(stderr, "k4align: unable to write %s\n", fn.c_str()); return 5; }
-      if (chatty) fprintf(stderr, "k4align: %llu %s reads written to %s\n", (unsigned long long)nl, which ? "multi-aligned" : "unalignable", fn.c_str());
-    }
-    if (o.fmode == 3) {  // genpba: ProcessSNPs in PBA mode is the report (KAligner.cpp:741-790); no SAM is written
-      auto ts = now();
-      k4_pba_files pf;
-      CK(k4_pba_run_dev(ix, pe ? 1 : 0, v.n_units, v.d_rr, v.d_hits, v.max_ml, v.d_pe, v.d_reads, v.d_offs, v.d_lens, o.experiment_id.c_str(),
-                        o.readset_id.c_str(), &pf, nullptr));
-      // the WIG's name: <-o cut at its last '.'> + .covsegs.wig (CUtility::AppendFileNameSuffix, KAligner.cpp:4341)
-      const struct { std::string name; const void* p; uint64_t n; } files[2] = {{o.out, pf.pba, pf.pba_bytes},
-                                                                                {stats_side_name(o.out, ".covsegs.wig"), pf.wig, pf.wig_bytes}};
-      std::string failed;
-      for (const auto& f : files) {
-        FILE* fp = fopen(f.name.c_str(), "wb");
-        bool ok = fp != nullptr;
-        if (ok) guard.made.push_back(f.name);
-        if (ok) ok = fwrite(f.p, 1, f.n, fp) == f.n;
-        if (fp && fclose(fp) != 0) ok = false;
-        if (!ok && failed.empty()) failed = f.name;
-      }
-      k4_free_host(pf.pba); k4_free_host(pf.wig);
-      if (!failed.empty()) { fprintf(stderr, "k4align: unable to write %s\n", failed.c_str()); return 5; }
-      if (chatty) fprintf(stderr, "k4align: packed base alleles of %llu sequences (%llu bytes) written to %s, coverage to %s in %.2fs\n",
-                          (unsigned long long)pf.n_chroms, (unsigned long long)pf.pba_bytes, o.out.c_str(), files[1].name.c_str(), secs(ts, now()));
-      k4_pipeline_close(pl);
-      pl = nullptr;
-      guard.ok = true;
-      k4_close(ix);
-      return 0;
-    }
-    if (o.min_snp_reads > 0) {  // ProcessSNPs (KAligner.cpp:768-790 calls it behind the alignment report): the SNP file and its side files
-      auto ts = now();
-      // a file name ending in .vcf: VCF instead of the CSV (KAligner.cpp:186-187)
-      const bool vcf = o.snp_file.size() >= 4 && strcasecmp(o.snp_file.c_str() + o.snp_file.size() - 4, ".vcf") == 0;
-      k4_snp_files sf;
-      k4_snp_files2 sf2;
-      memset(&sf2, 0, sizeof(sf2));
-      const bool more = o.marker_len != 0 || !o.cent_file.empty();  // the marker and centroid files out of the same counts
-      if (more) {
-        k4_snp_opts so;
-        so.marker_len = o.marker_len; so.want_centroids = o.cent_file.empty() ? 0 : 1; so.marker_poly_thres = o.marker_poly_thres;
-        CK(k4_snp_run2_dev(ix, vcf ? 1 : 0, pe ? 1 : 0, v.n_units, v.d_rr, v.d_hits, v.max_ml, v.d_pe, v.d_reads, v.d_offs, v.d_lens, o.min_snp_reads,
-                           o.qvalue, o.snp_nonref_pcnt, &so, &sf2, nullptr));
-        sf = sf2.files;
-      } else
-        CK(k4_snp_run_dev(ix, vcf ? 1 : 0, pe ? 1 : 0, v.n_units, v.d_rr, v.d_hits, v.max_ml, v.d_pe, v.d_reads, v.d_offs, v.d_lens, o.min_snp_reads,
-                          o.qvalue, o.snp_nonref_pcnt, &sf, nullptr));
-      // side files: <snp file cut at its last '.'> + suffix (CUtility::AppendFileNameSuffix, KAligner.cpp:4512, 4553-4554)
-      std::string stem = o.snp_file;
-      for (size_t q = stem.size(); q > 0; q--) {
-        if (stem[q - 1] == '.') { stem.resize(q - 1); break; }
-        if (stem[q - 1] == '/' || stem[q - 1] == '\\') break;
-      }
-      struct SnpOut { std::string name; const char* p; uint64_t n; bool guarded; };
-      std::vector<SnpOut> files = {{stem + ".covsegs.wig", sf.wig, sf.wig_bytes, false},
-                                   {stem + ".disnp.csv", sf.disnp, sf.disnp_bytes, false},
-                                   {stem + ".trisnp.csv", sf.trisnp, sf.trisnp_bytes, false},
-                                   {o.snp_file, sf.snp, sf.snp_bytes, false}};
-      if (o.marker_len) files.push_back({o.snp_file + ".markers", sf2.markers, sf2.markers_bytes, true});  // (the name is appended, KAlignerCL.cpp:957-959)
-      if (!o.cent_file.empty()) files.push_back({o.cent_file, sf2.centroids, sf2.centroids_bytes, true});
-      std::string failed;
-      for (const auto& f : files) {  // (the coverage WIG of a genome at low coverage runs to gigabytes: pwrite()s side by side)
-        FILE* fp = fopen(f.name.c_str(), "wb");
-        bool ok = fp != nullptr;
-        if (ok && f.guarded) guard.made.push_back(f.name);
-        if (ok && f.n >= (64u << 20)) {
-          const int fd = fileno(fp);
-          const int nt = std::max(o.io_threads, 1);
-          std::atomic<bool> good(true);
-          std::vector<std::thread> th;
-          for (int t = 0; t < nt; t++)
-            th.emplace_back([&, t] {
-              const uint64_t a = f.n * (uint64_t)t / nt, b = f.n * (uint64_t)(t + 1) / nt;
-              uint64_t done = a;
-              while (done < b) {
-                const ssize_t g = pwrite(fd, f.p + done, b - done, (off_t)done);
-                if (g <= 0) { good = false; return; }
-                done += (uint64_t)g;
-              }
-            });
-          for (std::thread& x : th) x.join();
-          ok = good;
-        } else if (ok)
-          ok = fwrite(f.p, 1, f.n, fp) == f.n;
-        if (fp && fclose(fp) != 0) ok = false;
-        if (!ok && failed.empty()) failed = f.name;
-      }
-      k4_free_host(sf.snp); k4_free_host(sf.wig); k4_free_host(sf.disnp); k4_free_host(sf.trisnp);
-      k4_free_host(sf2.markers); k4_free_host(sf2.centroids);
-      if (!failed.empty()) { fprintf(stderr, "k4align: unable to write %s\n", failed.c_str()); return 5; }
-      if (chatty) fprintf(stderr, "k4align: SNP processing completed with %llu putative SNPs discovered, written to %s in %.2fs\n",
-                          (unsigned long long)sf.n_snps, o.snp_file.c_str(), secs(ts, now()));
-      if (chatty && o.marker_len) fprintf(stderr, "k4align: %llu marker sequences of %d bases written to %s.markers\n", (unsigned long long)sf2.n_markers,
-                                          o.marker_len, o.snp_file.c_str());
-      if (chatty && !o.cent_file.empty()) fprintf(stderr, "k4align: SNP centroid distribution written to %s\n", o.cent_file.c_str());
-    }
-    if (!o.stats_file.empty()) {  // behind every stage that can still drop a read: the counted reads are the reported ones
-      auto ts = now();
-      k4_align_stats as;
-      CK(k4_pipeline_align_stats(pl, &as));
-      const uint64_t loaded = (uint64_t)(pe ? 2 : 1) * ((uint64_t)v.n_units - v.n_under - v.n_over);
-      if (o.splice_junct > 0) {
-        // with -A and SAM output the reference has its splice junction file open (KAligner.cpp:4446), so WriteReadHits runs in front
-        // of WriteBAMReadHits (:745-757) and calls WriteSubDist for every read too (:6835): those counts come out doubled
-        for (uint64_t q = 0; q < 4ull * as.len_stride; q++) { as.q_insts[q] *= 2; as.q_subs[q] *= 2; }
-        for (uint64_t q = 0; q <= as.len_stride; q++) as.m_sub[q] *= 2;
-      }
-      rc = k4_write_align_stats(ix, &as, loaded, o.ml_mode, max_ml, pe ? 1 : 0, o.stats_file.c_str());
-      k4_free_align_stats(&as);
-      if (rc != K4_OK) { fprintf(stderr, "k4align: %s\n", k4_last_error(ix)); return 5; }
-      if (chatty) fprintf(stderr, "k4align: alignment statistics written to %s in %.2fs\n", o.stats_file.c_str(), secs(ts, now()));
-    }
-    if (!o.site_file.empty()) {  // ProcessSiteProbabilites runs in front of the writer (KAligner.cpp:743), over the reads it will report
-      auto ts = now();
-      k4_site_prefs sp;
-      CK(k4_pipeline_site_prefs(pl, o.site_ofs, &sp));
-      rc = k4_write_site_prefs(&sp, o.site_file.c_str());
-      k4_free_site_prefs(&sp);
-      if (rc != K4_OK) { fprintf(stderr, "k4align: %s\n", k4_global_error()); return 5; }
-      if (chatty) fprintf(stderr, "k4align: start site octamer preferences written to %s in %.2fs\n", o.site_file.c_str(), secs(ts, now()));
-    }
-    // (a rank of a -G run numbers every sequence: the parent renumbers when it knows which ones any rank has hit)
-    const int bam_all_sq = (info.n_entries <= (uint32_t)o.rpt_sq_thres || o.rank_bam) ? 1 : 0;
-    if (bam_out && o.fmode == 1) CK(k4_pipeline_format_bam_all(pl, bam_all_sq, &tot, hit_chrom.data(), &pl_sam_bytes));
-    else if (bam_out) CK(k4_pipeline_format_bam(pl, bam_all_sq, &tot, hit_chrom.data(), &pl_sam_bytes));
-    else if (o.fmode == 1) CK(k4_pipeline_format_all(pl, &tot, hit_chrom.data(), &pl_sam_bytes));
-    else CK(k4_pipeline_format(pl, &tot, hit_chrom.data(), &pl_sam_bytes));
-    s_align = secs(tg, now());
-    n_under = v.n_under; n_over = v.n_over; n_units = (uint64_t)v.n_units;
   }
-  Stream f1, f2;
-  if (!pipelined && (!f1.open(o.in1) || (pe && !f2.open(o.in2)))) { fprintf(stderr, "k4align: unable to open reads\n"); return 2; }
-  std::vector<std::string> parts;
-  const uint64_t want0 = o.batch_mb > 0 ? std::max<uint64_t>((uint64_t)(o.batch_mb * 1048576.0), 4096) : UINT64_MAX;
-  uint64_t want = want0;
-  for (; !pipelined;) {
-    auto tr = now();
-    if (!f1.fill(want) || (pe && !f2.fill(want))) { fprintf(stderr, "k4align: error reading the input\n"); return 2; }
-    s_read += secs(tr, now());
-    if (f1.buf.empty()) break;
+  int stream_batches() {
+    Stream f1, f2;
+    if (!f1.open(o.in1) || (pe && !f2.open(o.in2))) { fprintf(stderr, "k4align: unable to open reads\n"); return 2; }
     const bool whole = o.batch_mb <= 0;
-    FILE* body = nullptr;
-    if (!whole) {
-      parts.push_back(o.out + ".part" + std::to_string(parts.size()));
-      body = fopen(parts.back().c_str(), "wb");
-      if (!body) { fprintf(stderr, "k4align: unable to create %s\n", parts.back().c_str()); return 5; }
+    const uint64_t want0 = whole ? UINT64_MAX : std::max<uint64_t>((uint64_t)(o.batch_mb * 1048576.0), 4096);
+    uint64_t want = want0;
+    for (;;) {
+      auto tr = now();
+      if (!f1.fill(want) || (pe && !f2.fill(want))) { fprintf(stderr, "k4align: error reading the input\n"); return 2; }
+      s_read += secs(tr, now());
+      if (f1.buf.empty()) break;
+      FILE* body = nullptr;
+      if (!whole) {
+        parts.push_back(o.out + ".part" + std::to_string(parts.size()));
+        body = fopen(parts.back().c_str(), "wb");
+        if (!body) { fprintf(stderr, "k4align: unable to create %s\n", parts.back().c_str()); return 5; }
+      }
+      uint64_t u1 = 0, u2 = 0;
+      const int rc = run_batch(f1.buf.data(), f1.buf.size(), f1.eof, f2.buf.data(), f2.buf.size(), f2.eof, body, &u1, &u2);
+      if (body) fclose(body);
+      if (rc != K4_OK) return rc;
+      if (u1 == 0) {  // not one whole record (pair) in this much text
+        if (!whole) { remove(parts.back().c_str()); parts.pop_back(); }
+        if (f1.eof && (!pe || f2.eof)) break;
+        want *= 2;
+        continue;
+      }
+      want = want0;
+      f1.drop(u1);
+      f2.drop(u2);
+      if (whole) break;
     }
-    uint64_t u1 = 0, u2 = 0;
-    rc = run_batch(f1.buf.data(), f1.buf.size(), f1.eof, f2.buf.data(), f2.buf.size(), f2.eof, body, &u1, &u2);
-    if (body) fclose(body);
-    if (rc != K4_OK) return rc;
-    if (u1 == 0) {  // not one whole record (pair) in this much text
-      if (!whole) { remove(parts.back().c_str()); parts.pop_back(); }
-      if (f1.eof && (!pe || f2.eof)) break;
-      want *= 2;
-      continue;
-    }
-    want = want0;
-    f1.drop(u1);
-    f2.drop(u2);
-    if (whole) break;
-  }
-  f1.close();
-  f2.close();
-
-  // ---- statistics (ReportAlignStats) ------------------------------------------------------------------------------
-  const uint64_t my_lines = tot.n_lines;
-  if (n_loci > 0) {  // the EN line is m_NumSloughedNs, counted while the reads are aligned (KAligner.cpp:3732): a PE mate marked LC since stays in it
-    uint64_t prior[20];
-    CK(k4_filter_marked_prior(ix, prior));
-    tot.nar[K4_NAR_NS] += prior[K4_NAR_NS];
-  }
-  if (comm) {  // the final aligned-read count/merge: one all-reduce of the tallies (north_star: the only collective on the path)
-    uint64_t t[26];
-    for (int k = 0; k < 20; k++) t[k] = tot.nar[k];
-    t[20] = tot.plus; t[21] = tot.minus; t[22] = tot.n_lines; t[23] = n_under; t[24] = n_over; t[25] = n_units;
-    if ((rc = k4_comm_allreduce_sum_u64(comm, t, 26)) != K4_OK) { fprintf(stderr, "k4align: rank %d: all-reduce failed: %s\n", o.rank, k4_comm_last_error(comm)); return 2; }
-    for (int k = 0; k < 20; k++) tot.nar[k] = t[k];
-    tot.plus = t[20]; tot.minus = t[21]; tot.n_lines = t[22]; n_under = t[23]; n_over = t[24]; n_units = t[25];
-  }
-  const uint64_t n_loaded = (uint64_t)(pe ? 2 : 1) * (n_units - n_under - n_over);
-  if (chatty) {
-    fprintf(stderr, "k4align: From %llu source reads there are %llu accepted alignments, %llu on '+' strand, %llu on '-' strand\n",
-            (unsigned long long)n_loaded, (unsigned long long)tot.nar[1], (unsigned long long)tot.plus, (unsigned long long)tot.minus);
-    if (n_under || n_over)
-      fprintf(stderr, "k4align: %llu under length and %llu over length reads were sloughed\n", (unsigned long long)n_under,
-              (unsigned long long)n_over);
-    for (int k = 0; k < 20; k++) fprintf(stderr, "k4align:    %llu (%s)\n", (unsigned long long)tot.nar[k], kNarAbbr[k]);
+    return 0;
   }
 
-  // ---- SAM file: header here, body as formatted on the device ----------------------------------------------------------
-  auto tw = now();
-  if (bam_out && o.rank_bam) {
-    // ---- a rank of a -G run: its coordinate-sorted BAM records as they are (refID = sequence number - 1), and beside them the
-    // dictionary with this rank's hit flags; the parent merges the ranks' streams into the one BAM file (run_multi_gpu) ----------
-    FILE* fp = fopen(o.out.c_str(), "wb");
-    if (!fp) { fprintf(stderr, "k4align: unable to create %s\n", o.out.c_str()); return 5; }
-    guard.made.push_back(o.out);
-    guard.made.push_back(o.out + ".sq");
-    uint64_t nbytes = 0;
+  // ---- statistics (ReportAlignStats) ------------------------------------------------------------------------------------------
+  int tally() {
+    my_lines = tot.n_lines;
+    if (n_loci > 0) {  // the EN line is m_NumSloughedNs, counted while the reads are aligned (KAligner.cpp:3732): a PE mate marked LC since stays in it
+      uint64_t prior[20];
+      CK(k4_filter_marked_prior(ix, prior));
+      tot.nar[K4_NAR_NS] += prior[K4_NAR_NS];
+    }
+    if (comm) {  // the final aligned-read count/merge: one all-reduce of the tallies (north_star: the only collective on the path)
+      uint64_t t[26];
+      for (int k = 0; k < 20; k++) t[k] = tot.nar[k];
+      t[20] = tot.plus; t[21] = tot.minus; t[22] = tot.n_lines; t[23] = n_under; t[24] = n_over; t[25] = n_units;
+      if (k4_comm_allreduce_sum_u64(comm, t, 26) != K4_OK) { fprintf(stderr, "k4align: rank %d: all-reduce failed: %s\n", o.rank, k4_comm_last_error(comm)); return 2; }
+      for (int k = 0; k < 20; k++) tot.nar[k] = t[k];
+      tot.plus = t[20]; tot.minus = t[21]; tot.n_lines = t[22]; n_under = t[23]; n_over = t[24]; n_units = t[25];
+    }
+    const uint64_t n_loaded = (uint64_t)(pe ? 2 : 1) * (n_units - n_under - n_over);
+    if (chatty) {
+      fprintf(stderr, "k4align: From %llu source reads there are %llu accepted alignments, %llu on '+' strand, %llu on '-' strand\n",
+              (unsigned long long)n_loaded, (unsigned long long)tot.nar[1], (unsigned long long)tot.plus, (unsigned long long)tot.minus);
+      if (n_under || n_over)
+        fprintf(stderr, "k4align: %llu under length and %llu over length reads were sloughed\n", (unsigned long long)n_under,
+                (unsigned long long)n_over);
+      for (int k = 0; k < 20; k++) fprintf(stderr, "k4align:    %llu (%s)\n", (unsigned long long)tot.nar[k], kNarAbbr[k]);
+    }
+    return 0;
+  }
+
+  // ---- the output ----------------------------------------------------------------------------------------------------------------
+  // the formatted records come down piece by piece (the previous piece is written meanwhile); a sink that fails has said why
+  template <class Sink> int drain_sam(Sink sink) {
     for (;;) {
       const void* ptr = nullptr;
       uint64_t len = 0;
       CK(k4_pipeline_next_sam(pl, &ptr, &len));
-      if (len == 0) break;
-      if (fwrite(ptr, 1, (size_t)len, fp) != (size_t)len) { fprintf(stderr, "k4align: unable to write %s\n", o.out.c_str()); fclose(fp); return 5; }
-      nbytes += len;
+      if (len == 0) return 0;
+      if (!sink(ptr, len)) return 5;
     }
-    if (fclose(fp) != 0) { fprintf(stderr, "k4align: unable to write %s\n", o.out.c_str()); return 5; }
+  }
+  // every sequence of the index in turn, and whether the header declares it: all of them, or only the ones with alignments
+  template <class Each> void walk_dictionary(bool all, Each each) {
+    for (uint32_t c = 1; c <= info.n_entries; c++) {
+      k4_entry e;
+      k4_get_entry(ix, c, &e);
+      each(c, e, all || hit_chrom[c]);
+    }
+  }
+  // A rank of a -G run whose output is BAM: its coordinate-sorted BAM records as they are (refID = sequence number - 1), and beside
+  // them the dictionary with this rank's hit flags; the parent merges the ranks' streams into the one BAM file (run_multi_gpu)
+  int write_rank_bam() {
+    FILE* fp = fopen(o.out.c_str(), "wb");
+    if (!fp) { fprintf(stderr, "k4align: unable to create %s\n", o.out.c_str()); return 5; }
+    made.push_back(o.out);
+    made.push_back(o.out + ".sq");
+    uint64_t nbytes = 0;
+    int rc = drain_sam([&](const void* ptr, uint64_t len) { nbytes += len; return fwrite(ptr, 1, (size_t)len, fp) == (size_t)len; });
+    if (fclose(fp) != 0 && rc == 0) rc = 5;
+    if (rc == 5) fprintf(stderr, "k4align: unable to write %s\n", o.out.c_str());
+    if (rc != 0) return rc;
     FILE* fd = fopen((o.out + ".sq").c_str(), "wb");
     if (!fd) { fprintf(stderr, "k4align: unable to create %s.sq\n", o.out.c_str()); return 5; }
     fprintf(fd, "%s\n", info.dataset);
-    for (uint32_t c = 1; c <= info.n_entries; c++) {
-      k4_entry e;
-      k4_get_entry(ix, c, &e);
-      fprintf(fd, "%s\t%u\t%d\n", e.name, e.seq_len, hit_chrom[c] ? 1 : 0);
-    }
+    walk_dictionary(false, [&](uint32_t, const k4_entry& e, bool hit) { fprintf(fd, "%s\t%u\t%d\n", e.name, e.seq_len, hit ? 1 : 0); });
     if (fclose(fd) != 0) { fprintf(stderr, "k4align: unable to write %s.sq\n", o.out.c_str()); return 5; }
-    k4_pipeline_close(pl);
-    pl = nullptr;
-    guard.ok = true;
+    ok = true;
     if (chatty) fprintf(stderr, "k4align: rank %d: %llu alignments as BAM records (%llu bytes) for the merge\n", o.rank, (unsigned long long)my_lines, (unsigned long long)nbytes);
-    k4_close(ix);
     return 0;
   }
-  if (bam_out) {
-    // ---- BAM (+ .bai): dictionary and BGZF blocks here (include/k4_bam.hpp), the records as packed on the device ------------
+  // BAM (+ .bai): dictionary and BGZF blocks here (include/k4_bam.hpp), the records as packed on the device
+  int write_bam() {
+    auto tw = now();
     std::string hdr = "@HD\tVN:1.4\tSO:coordinate\n";
     std::vector<k4bam::RefSeq> refs;
-    const bool all_sq = info.n_entries <= (uint32_t)o.rpt_sq_thres;  // m_MaxRptSAMSeqsThres, KAligner.cpp:5785-5821
-    for (uint32_t c = 1; c <= info.n_entries; c++) {
-      k4_entry e;
-      k4_get_entry(ix, c, &e);
-      if (!(all_sq || hit_chrom[c])) continue;
+    walk_dictionary(few_seqs(), [&](uint32_t, const k4_entry& e, bool declared) {
+      if (!declared) return;
       hdr += std::string("@SQ\tAS:") + info.dataset + "\tSN:" + e.name + "\tLN:" + std::to_string(e.seq_len) + "\n";
       refs.push_back({e.name, e.seq_len});
-    }
+    });
     hdr += "@PG\tID:k4align\tVN:1.0\n";
     k4bam::Writer bw;
     if (!bw.open(o.out, hdr, refs, o.bam_level, std::max(o.io_threads, 1))) { fprintf(stderr, "k4align: %s\n", bw.error().c_str()); return 5; }
-    guard.made.push_back(o.out);
-    guard.made.push_back(o.out + ".bai");
-    for (;;) {  // the records come down piece by piece; the previous piece is deflated and written meanwhile
-      const void* ptr = nullptr;
-      uint64_t len = 0;
-      CK(k4_pipeline_next_sam(pl, &ptr, &len));
-      if (len == 0) break;
-      if (!bw.write(ptr, (size_t)len)) { fprintf(stderr, "k4align: %s\n", bw.error().c_str()); return 5; }
-    }
-    if (!bw.close()) { fprintf(stderr, "k4align: %s\n", bw.error().c_str()); return 5; }
+    made.push_back(o.out);
+    made.push_back(o.out + ".bai");
+    const int rc = drain_sam([&](const void* ptr, uint64_t len) { return bw.write(ptr, (size_t)len); });  // (deflated and written meanwhile)
+    if (rc == 5 || (rc == 0 && !bw.close())) { fprintf(stderr, "k4align: %s\n", bw.error().c_str()); return 5; }
+    if (rc != 0) return rc;
     if (!bw.indexed() && chatty) fprintf(stderr, "k4align: a sequence of 512 Mbp or more: no .bai written (the reference writes a CSI index there)\n");
     if (bw.n_records() != my_lines) { fprintf(stderr, "k4align: internal error: %llu BAM records for %llu alignments\n", (unsigned long long)bw.n_records(), (unsigned long long)my_lines); return 5; }
-    k4_pipeline_close(pl);
-    pl = nullptr;
-    guard.ok = true;
+    reset_pipeline();
+    ok = true;
     const double s_write_bam = secs(tw, now());
     if (chatty)
       fprintf(stderr, "k4align: %llu alignments reported to %s (%llu bytes) + .bai; index %.2fs, reads %.2fs, device side behind the reads %.2fs, "
                       "global stages + sort + records %.2fs, deflate + write %.2fs\n", (unsigned long long)bw.n_records(), o.out.c_str(),
-              (unsigned long long)bw.compressed_bytes() + 28, std::max(secs(t0, t_open), k4_open_seconds(ix)), s_read, s_parse, s_align, s_write_bam);
-    k4_close(ix);
+              (unsigned long long)bw.compressed_bytes() + 28, index_secs(), s_read, s_parse, s_align, s_write_bam);
     return 0;
   }
-  FILE* fp = fopen(o.out.c_str(), "wb");
-  if (!fp) { fprintf(stderr, "k4align: unable to create %s\n", o.out.c_str()); return 5; }
-  guard.made.push_back(o.out);
-  static char iobuf[1 << 22];
-  setvbuf(fp, iobuf, _IOFBF, sizeof(iobuf));
-  fprintf(fp, "@HD\tVN:1.4\tSO:coordinate\n");
-  // m_MaxRptSAMSeqsThres, KAligner.cpp:5785-5821: with more sequences only those that were hit are declared -- a shard (-S, -G)
-  // declares all of them and leaves that rule to the merge, which sees every shard's records
-  const bool all_chroms = info.n_entries <= (uint32_t)o.rpt_sq_thres || o.n_shards > 1 || multi;
-  std::map<std::string, long> order;
-  for (uint32_t c = 1; c <= info.n_entries; c++) {
-    k4_entry e;
-    k4_get_entry(ix, c, &e);
-    order.emplace(e.name, (long)c);
-    if (all_chroms || hit_chrom[c]) fprintf(fp, "@SQ\tAS:%s\tSN:%s\tLN:%u\n", info.dataset, e.name, e.seq_len);
-  }
-  fprintf(fp, "@PG\tID:k4align\tVN:1.0\n");
-  if (pl) {  // the body comes down piece by piece while the previous piece is written
+  // the SAM body out of the pipeline; a seekable file takes every piece by concurrent writes at its place
+  int sam_body_from_pipeline(FILE* fp) {
     fflush(fp);
     const int fd = fileno(fp);
     const bool seekable = lseek(fd, 0, SEEK_CUR) != (off_t)-1;  // (-o /dev/stdout, a pipe: written in order by one thread)
     uint64_t fpos = seekable ? (uint64_t)ftello(fp) : 0;
     if (seekable && ftruncate(fd, (off_t)(fpos + pl_sam_bytes)) != 0) { /* (the size is only a hint for the file system) */ }
-    for (;;) {
-      const void* ptr = nullptr;
-      uint64_t len = 0;
-      CK(k4_pipeline_next_sam(pl, &ptr, &len));
-      if (len == 0) break;
-      if (!seekable) {
-        if (fwrite(ptr, 1, (size_t)len, fp) != (size_t)len) { fprintf(stderr, "k4align: write to %s failed\n", o.out.c_str()); return 5; }
-        continue;
-      }
-      // (several pwrite()s side by side: one thread does not saturate tmpfs / the page cache)
-      const int nt = len >= (8u << 20) ? std::max(o.io_threads, 1) : 1;
-      std::atomic<bool> ok(true);
-      std::vector<std::thread> th;
-      for (int t = 0; t < nt; t++)
-        th.emplace_back([&, t] {
-          const uint64_t a = len * t / nt, b = len * (t + 1) / nt;
-          uint64_t done = a;
-          while (done < b) {
-            const ssize_t g = pwrite(fd, (const char*)ptr + done, b - done, (off_t)(fpos + done));
-            if (g <= 0) { ok = false; return; }
-            done += (uint64_t)g;
-          }
-        });
-      for (std::thread& x : th) x.join();
-      if (!ok) { fprintf(stderr, "k4align: write to %s failed\n", o.out.c_str()); return 5; }
+    const int rc = drain_sam([&](const void* ptr, uint64_t len) {
+      const bool done = seekable ? io_parallel<true>(fd, (uint8_t*)ptr, fpos, len, o.io_threads)
+                                 : fwrite(ptr, 1, (size_t)len, fp) == (size_t)len;
+      if (!done) fprintf(stderr, "k4align: write to %s failed\n", o.out.c_str());
       fpos += len;
-    }
+      return done;
+    });
+    if (rc != 0) return rc;
     if (seekable) fseeko(fp, (off_t)fpos, SEEK_SET);
-    {
-      auto tc0 = now();
-      k4_pipeline_close(pl);
-      pl = nullptr;
-      if (getenv("K4_TRACE")) fprintf(stderr, "[k4 trace] pipeline closed in %.2fs\n", secs(tc0, now()));
-    }
-  } else if (keep_sam) {
-    std::vector<char> piece((size_t)std::min<uint64_t>(keep_bytes, 256ull << 20));
-    for (uint64_t off = 0; off < keep_bytes; off += piece.size()) {
-      const uint64_t len = std::min<uint64_t>(piece.size(), keep_bytes - off);
-      CK(k4_copy_to_host(ix, piece.data(), (const char*)keep_sam + off, len));
-      if (fwrite(piece.data(), 1, len, fp) != len) { fprintf(stderr, "k4align: write to %s failed\n", o.out.c_str()); return 5; }
-    }
-    k4_free_device(keep_sam);
-  } else if (!parts.empty()) {
-    // every part is coordinate sorted; merge by (chromosome, position), equal keys in batch order = load order
+    auto tc0 = now();
+    reset_pipeline();
+    if (getenv("K4_TRACE")) fprintf(stderr, "[k4 trace] pipeline closed in %.2fs\n", secs(tc0, now()));
+    return 0;
+  }
+  // -b: every part is coordinate sorted; merge by (chromosome, position), equal keys in batch order = load order
+  int merge_parts(FILE* fp, const std::map<std::string, long>& order) {
     struct Src { FILE* f; std::string line; long chrom, pos; };
     std::vector<Src> src(parts.size());
     auto next = [&](Src& x) -> bool {
@@ -1359,19 +1294,72 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
       if (next(src[i])) pq.push({{src[i].chrom, src[i].pos}, i});
     }
     for (size_t i = 0; i < parts.size(); i++) { fclose(src[i].f); remove(parts[i].c_str()); }
+    return 0;
   }
-  fflush(fp);
-  const bool wfail = ferror(fp) != 0;
-  if (fclose(fp) != 0 || wfail) { fprintf(stderr, "k4align: write to %s failed\n", o.out.c_str()); return 5; }
-  s_write += secs(tw, now());
-  fprintf(stderr, "k4align: %s%llu alignments written to %s (%zu batch%s); index %.2fs, read files %.2fs, upload+parse %.2fs, align+format %.2fs, write %.2fs\n",
-          multi ? ("rank " + std::to_string(o.rank) + ": ").c_str() : "", (unsigned long long)my_lines, o.out.c_str(),
-          parts.empty() ? (size_t)1 : parts.size(), parts.size() > 1 ? "es" : "", std::max(secs(t0, t_open), k4_open_seconds(ix)), s_read, s_parse, s_align, s_write);
-  guard.ok = true;
-  if (comm) { k4_comm_barrier(comm); }
-  k4_close(ix);
-  if (comm) k4_comm_close(comm);
-  return 0;
+  // SAM: header here; the body as formatted on the device -- from the pipeline, the kept block of the single batch, or the parts
+  int write_sam() {
+    auto tw = now();
+    FILE* fp = fopen(o.out.c_str(), "wb");
+    if (!fp) { fprintf(stderr, "k4align: unable to create %s\n", o.out.c_str()); return 5; }
+    made.push_back(o.out);
+    static char iobuf[1 << 22];
+    setvbuf(fp, iobuf, _IOFBF, sizeof(iobuf));
+    fprintf(fp, "@HD\tVN:1.4\tSO:coordinate\n");
+    // a shard (-S, -G) declares every sequence and leaves the rule to the merge, which sees every shard's records
+    std::map<std::string, long> order;
+    walk_dictionary(few_seqs() || o.n_shards > 1 || multi, [&](uint32_t c, const k4_entry& e, bool declared) {
+      order.emplace(e.name, (long)c);
+      if (declared) fprintf(fp, "@SQ\tAS:%s\tSN:%s\tLN:%u\n", info.dataset, e.name, e.seq_len);
+    });
+    fprintf(fp, "@PG\tID:k4align\tVN:1.0\n");
+    int rc = 0;
+    if (pl) rc = sam_body_from_pipeline(fp);
+    else if (keep_sam) CK(download(ix, keep_sam.get(), keep_bytes, fp));
+    else if (!parts.empty()) rc = merge_parts(fp, order);
+    if (rc != 0) return rc;
+    fflush(fp);
+    const bool wfail = ferror(fp) != 0;
+    if (fclose(fp) != 0 || wfail) { fprintf(stderr, "k4align: write to %s failed\n", o.out.c_str()); return 5; }
+    s_write += secs(tw, now());
+    fprintf(stderr, "k4align: %s%llu alignments written to %s (%zu batch%s); index %.2fs, read files %.2fs, upload+parse %.2fs, align+format %.2fs, write %.2fs\n",
+            multi ? ("rank " + std::to_string(o.rank) + ": ").c_str() : "", (unsigned long long)my_lines, o.out.c_str(),
+            parts.empty() ? (size_t)1 : parts.size(), parts.size() > 1 ? "es" : "", index_secs(), s_read, s_parse, s_align, s_write);
+    ok = true;
+    if (comm) {  // (closed behind the index: RunHeld)
+      k4_comm_barrier(comm);
+      met_peers = true;
+    }
+    return 0;
+  }
+};
+
+// CKAligner::Align's steps (KAligner.cpp:391-800) in its order: index, parameters, reads + alignment, the stages over all reads,
+// the reports, the statistics, the alignments
+static int run_rank(Opts& o, const bool pe, const int max_ml) {
+  Run r(o, pe, max_ml);
+  int rc;
+#define STEP(call) if ((rc = r.call) != 0) return rc
+  STEP(open_index());
+  STEP(load_constraints());
+  STEP(derive_params());
+  if (r.pipelined) {
+    STEP(open_pipeline());
+    STEP(feed_pipeline());
+    auto tg = now();
+    const k4_pipeline_view& v = r.v;
+    STEP(global_stages(v.n_units, v.max_read_len, v.d_rr, v.d_hits, v.d_seg2, v.d_pe, v.d_reads, v.d_offs, v.d_lens));
+    STEP(write_unaligned());                                 // -j / -J: before the alignments are reported
+    if (o.fmode == 3) return r.write_pba();                  // -M3: that is the report
+    if (o.min_snp_reads > 0) STEP(write_snps());             // -p, -S, -K, -7
+    if (!o.stats_file.empty()) STEP(write_align_stats());    // -O
+    if (!o.site_file.empty()) STEP(write_site_prefs());      // -8
+    STEP(format_records());
+    r.s_align = secs(tg, now());
+  } else
+    STEP(stream_batches());
+  STEP(tally());
+#undef STEP
+  return o.rank_bam ? r.write_rank_bam() : r.bam_out ? r.write_bam() : r.write_sam();
 }
 
 // k4align -G g0,g1,...: the parent forks one rank per GPU BEFORE anything touches HIP and only waits and merges; the ranks

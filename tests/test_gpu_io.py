@@ -549,11 +549,12 @@ def test_k4align_rank_mode_writes_bam(golden_dir, tmp_path, case, extra):
     assert os.path.exists(out + ".bai")
 
 
-@pytest.mark.parametrize("case,form", [("se_s2", "gz"), ("pe_u1", "gz"), ("se_s2", "split"), ("pe_u1", "split")])
+@pytest.mark.parametrize("case,form", [("se_s2", "gz"), ("pe_u1", "gz"), ("se_s2", "split"), ("pe_u1", "split"), ("se_s2", "gzsplit")])
 def test_k4align_rank_mode_takes_compressed_and_several_input_files(golden_dir, tmp_path, case, form):
     """`k4align -G` on what a single `kalign` run takes as well: gzipped reads (no byte offsets into a compressed stream: every
     rank inflates it and keeps the record blocks dealt to it) and several -i / -u files (one sequence of records, cut by record
-    numbers over all files).  One rank here; the SAM equals the reference's."""
+    numbers over all files; "gzsplit": the same three files gzipped, so the dealt stream too meets a file that lacks its newline in
+    front of another).  One rank here; the SAM equals the reference's."""
     import gzip
     import json
     import lzma
@@ -574,9 +575,9 @@ def test_k4align_rank_mode_takes_compressed_and_several_input_files(golden_dir, 
             recs = text.decode().split(">")[1:]
             cuts = [0, len(recs) // 3, len(recs) // 3 + 7, len(recs)]
             for k in range(3):
-                dst = str(tmp_path / ("%d_%d.fa" % (e, k)))
+                dst = str(tmp_path / ("%d_%d.fa%s" % (e, k, ".gz" if form == "gzsplit" else "")))
                 part = "".join(">" + r for r in recs[cuts[k]:cuts[k + 1]])
-                open(dst, "w").write(part[:-1] if k == 1 else part)
+                (gzip.open(dst, "wt") if form == "gzsplit" else open(dst, "w")).write(part[:-1] if k == 1 else part)
                 files += [flag, dst]
     out = str(tmp_path / "o.sam")
     p = subprocess.run([os.path.join(root, "kit4b_amd", "k4align"), "-I", os.path.join(golden_dir, "g1.sfx"), "-o", out, "-G", "0"]

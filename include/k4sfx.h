@@ -375,6 +375,41 @@ int k4_align_stats_dev(k4_index* ix, int pe, int64_t n_reads, int32_t max_ml, in
 void k4_free_align_stats(k4_align_stats* s);
 int k4_write_align_stats(k4_index* ix, const k4_align_stats* s, uint64_t n_loaded, int32_t ml_mode, int32_t max_multi, int pe,
                          const char* path);
+/* ---- per-target PE insert length distributions (`kalign -3`, --petranslendist; kit4b_amd/csrc/k4_peinserts.hip) ------------------
+ * k4_pe_insert_dist_dev    <- the walk of CKAligner::ReportPEInsertLenDist (KAligner.cpp:5321-5454) in the order of SortPEHitMatch
+ *                             (:10928-10963) over the pair records in HBM as the last global stage left them (d_pe: 2 x n_pairs
+ *                             k4_pe_read, mates at 2q and 2q + 1): the reads that are accepted and FlgPEAligned, by (ChromID, pair,
+ *                             PE1 before PE2), taken TWO AT A TIME as the reference takes them -- where a later stage took one mate
+ *                             of a pair out, the pairings behind it on that walk shift by one, and a last odd read is dropped.
+ *                             With S = AdjAlignStartLoci + 1 and L = AdjAlignHitLen: TLen = S1 <= S2 ? (S2 - S1) + L2 : (S1 - S2) + L1
+ *                             in 32-bit unsigned arithmetic, counted on the target of the first of the two: dist[0] TLen < 100,
+ *                             dist[51] TLen > 600, else dist[1 + (TLen - 99) / 10].  Only the first 1 000 000 pairs of a target in
+ *                             walk order are counted (:5404).  median: CKAligner::MedianInsertLen (:5256-5319), which is not the
+ *                             textbook median (k4_pe_insert_median_host is the same rule on the host).  One row per target with a
+ *                             pair, ascending entry id.  Changes none of the records; waits for `stream`.  Release with
+ *                             k4_free_pe_insert_dist.
+ * k4_write_pe_insert_dist  <- the text (:5354-5357, :5383-5386): the header and per row "name",SeqLen,TotPEs,Median,Sum / TotPEs and
+ *                             the 52 columns; names and lengths are the index's.  kalign's file is <the -O path>.peinserts.csv
+ *                             (:205-215: appended to the whole path).  n_accepted: the accepted reads of the run; the file is
+ *                             left empty when it is 0 (:771), else the header is written even without a row.
+ * k4_pe_insert_bin_host / k4_pe_insert_median_host: the column of a TLen and MedianInsertLen of `n` values in walk order, on the
+ *                             host (no device, no index): the functions the kernels run (values must not hold a 0). */
+#define K4_PE_INSERT_BINS 52
+typedef struct {
+  uint32_t n_rows;
+  uint32_t reserved;
+  uint32_t* entry_id;   /* [n_rows] 1-based entry id of the target, ascending */
+  uint32_t* tot_pes;    /* [n_rows] NumPEs: pairs counted, at most 1 000 000 */
+  uint32_t* median;     /* [n_rows] MedianInsertLen over the counted pairs */
+  uint64_t* sum;        /* [n_rows] SumInsertLens */
+  uint32_t* dist;       /* [n_rows][K4_PE_INSERT_BINS] LenDist */
+  void* block;          /* the one allocation behind the arrays */
+} k4_pe_insert_dist;
+int k4_pe_insert_dist_dev(k4_index* ix, int64_t n_pairs, const void* d_pe, k4_pe_insert_dist* out, void* stream);
+void k4_free_pe_insert_dist(k4_pe_insert_dist* d);
+int k4_write_pe_insert_dist(k4_index* ix, const k4_pe_insert_dist* d, uint64_t n_accepted, const char* path);
+int k4_pe_insert_bin_host(uint32_t tlen);                                                  /* the column, 0..51 */
+int k4_pe_insert_median_host(const uint32_t* values, uint32_t n, uint32_t* median);  /* a K4_* code */
 /* ---- start-site octamer preferences (`kalign -8 <file>`, `-9 <ofs>`; kit4b_amd/csrc/k4_siteprefs.hip) ---------------------------
  * k4_site_prefs_dev      <- the walk of CKAligner::ProcessSiteProbabilites (KAligner.cpp:8750-8821) over the records in HBM as the last
  *                           global stage left them: n_reads reads (PE: both ends, d_pe; SE: d_rr and hit slot 0 of d_hits).  In
@@ -695,6 +730,8 @@ int k4_pipeline_wait_aligned(k4_pipeline* pl, k4_pipeline_view* view); /* after 
 int k4_pipeline_align_stats(k4_pipeline* pl, k4_align_stats* out);
 /* k4_site_prefs_dev over the pipeline's own arrays; likewise behind the last global stage and before k4_pipeline_format* */
 int k4_pipeline_site_prefs(k4_pipeline* pl, int32_t ofs, k4_site_prefs* out);
+/* k4_pe_insert_dist_dev over a paired-end pipeline's own arrays; likewise */
+int k4_pipeline_pe_insert_dist(k4_pipeline* pl, k4_pe_insert_dist* out);
 int k4_pipeline_format(k4_pipeline* pl, k4_sam_stats* stats, uint8_t* chrom_hit /* host, n_entries + 1, or NULL */, uint64_t* sam_bytes);
 /* ... as BAM records (k4_format_bam_dev); the pieces come down through k4_pipeline_next_sam / k4_pipeline_read_sam all the same */
 int k4_pipeline_format_bam(k4_pipeline* pl, int32_t sq_all, k4_sam_stats* stats, uint8_t* chrom_hit, uint64_t* bam_bytes);

@@ -131,6 +131,14 @@ class SitePrefs(C.Structure):  # k4_site_prefs
                 ("n_counted", C.c_uint64), ("block", C.c_void_p)]
 
 
+class PeInsertDist(C.Structure):  # k4_pe_insert_dist
+    _fields_ = [("n_rows", C.c_uint32), ("reserved", C.c_uint32), ("entry_id", C.POINTER(C.c_uint32)), ("tot_pes", C.POINTER(C.c_uint32)),
+                ("median", C.POINTER(C.c_uint32)), ("sum", C.POINTER(C.c_uint64)), ("dist", C.POINTER(C.c_uint32)), ("block", C.c_void_p)]
+
+
+PE_INSERT_BINS = 52
+
+
 class PbaFiles(C.Structure):  # k4_pba_files
     _fields_ = [("pba", C.c_void_p), ("pba_bytes", C.c_uint64), ("wig", C.c_void_p), ("wig_bytes", C.c_uint64), ("n_chroms", C.c_uint64)]
 
@@ -175,7 +183,8 @@ ABI_SYMBOLS = [
     "k4_set_raw_header", "k4_align_stats_collect", "k4_align_stats_dev", "k4_free_align_stats", "k4_write_align_stats",
     "k4_pipeline_align_stats", "k4_filter_loci_constraints_dev", "k4_filter_chroms_dev", "k4_load_loci_constraints", "k4_chrom_accept_mask",
     "k4_filter_marked_prior", "k4_site_prefs_dev", "k4_free_site_prefs", "k4_write_site_prefs", "k4_pipeline_site_prefs",
-    "k4_pba_run_dev", "k4_pba_classify_host", "k4_snp_run2_dev", "k4_marker_classify_host",
+    "k4_pe_insert_dist_dev", "k4_free_pe_insert_dist", "k4_write_pe_insert_dist", "k4_pipeline_pe_insert_dist", "k4_pe_insert_bin_host",
+    "k4_pe_insert_median_host", "k4_pba_run_dev", "k4_pba_classify_host", "k4_snp_run2_dev", "k4_marker_classify_host",
 ]
 
 
@@ -262,6 +271,13 @@ def lib():
     L.k4_free_site_prefs.restype = None
     L.k4_write_site_prefs.argtypes = [C.POINTER(SitePrefs), C.c_char_p]
     L.k4_pipeline_site_prefs.argtypes = [vp, C.c_int32, C.POINTER(SitePrefs)]
+    L.k4_pe_insert_dist_dev.argtypes = [vp, i64, vp, C.POINTER(PeInsertDist), vp]
+    L.k4_free_pe_insert_dist.argtypes = [C.POINTER(PeInsertDist)]
+    L.k4_free_pe_insert_dist.restype = None
+    L.k4_write_pe_insert_dist.argtypes = [vp, C.POINTER(PeInsertDist), u64, C.c_char_p]
+    L.k4_pipeline_pe_insert_dist.argtypes = [vp, C.POINTER(PeInsertDist)]
+    L.k4_pe_insert_bin_host.argtypes = [u32]
+    L.k4_pe_insert_median_host.argtypes = [vp, u32, C.POINTER(u32)]
     L.k4_filter_loci_constraints_dev.argtypes = [vp, C.POINTER(LociConstraint), C.c_int32, i32, i64, C.c_int32, vp, vp, vp, vp, vp, vp, vp,
                                                  C.POINTER(C.c_int64), vp]
     L.k4_filter_chroms_dev.argtypes = [vp, vp, i32, i64, C.c_int32, vp, vp, C.POINTER(C.c_int64), vp]
@@ -929,6 +945,25 @@ class SfxIndex:
         finally:
             lib().k4_free_site_prefs(C.byref(sp))
 
+    def pe_insert_dist(self, n_pairs, d_pe, stream=0, write=None):
+        """The table behind `kalign -3` (ReportPEInsertLenDist, KAligner.cpp:5321-5454) over n_pairs pairs of k4_pe_read records in a
+        device array (torch tensor or address; mates at 2q and 2q + 1).  Returns numpy arrays with one element per target that received
+        a pair, ascending entry id: entry_id, tot_pes, median (uint32), sum (uint64), dist [n_rows, 52].  write = (path, n_accepted):
+        also print the file (left empty when n_accepted is 0)."""
+        pd = PeInsertDist()
+        self._ck(lib().k4_pe_insert_dist_dev(self.h, int(n_pairs), d_pe if isinstance(d_pe, int) or d_pe is None else d_pe.data_ptr(),
+                                             C.byref(pd), stream))
+        try:
+            if write is not None:
+                path, n_accepted = write
+                self._ck(lib().k4_write_pe_insert_dist(self.h, C.byref(pd), int(n_accepted), os.fsencode(path)))
+            k = int(pd.n_rows)
+            arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n,)).astype(dt).copy() if n else np.zeros(0, dt)  # noqa: E731
+            return {"entry_id": arr(pd.entry_id, k, np.uint32), "tot_pes": arr(pd.tot_pes, k, np.uint32), "median": arr(pd.median, k, np.uint32),
+                    "sum": arr(pd.sum, k, np.uint64), "dist": arr(pd.dist, k * PE_INSERT_BINS, np.uint32).reshape(k, PE_INSERT_BINS)}
+        finally:
+            lib().k4_free_pe_insert_dist(C.byref(pd))
+
     def pipeline_sam(self, texts, kp, pe=None, min_len=50, max_len=500, chunk_bytes=0, ring=False, out=None, min_batch_units=0, all_reads=False, expect=True):
         """host text (bytes-like / pinned tensors: one for SE, two for PE) -> SAM body through the overlapped pipeline.
         ring=True feeds through acquire / submit (what k4align's reader threads do), else submit_host.  Returns (body or
@@ -1038,6 +1073,22 @@ class SfxIndex:
                               d_hits, stream=0):
         self._ck(lib().k4_align_reads_batch_dev(self.h, C.byref(params), n, max_read_len, d_reads, d_offs, d_lens,
                                                 d_rslt, d_inst, d_low, d_nxt, d_hits, stream))
+
+
+def pe_insert_bin_host(tlen):
+    """The column (0..51) of `kalign -3`'s table an insert length is counted in (k4_pe_insert_bin_host; needs the library, no GPU)."""
+    return int(lib().k4_pe_insert_bin_host(int(tlen)))
+
+
+def pe_insert_median_host(values):
+    """CKAligner::MedianInsertLen (KAligner.cpp:5256-5319) of a target's insert lengths in walk order, by the function the kernel runs
+    (k4_pe_insert_median_host; needs the library, no GPU).  values: uint32, none of them 0."""
+    values = np.ascontiguousarray(values, np.uint32)
+    med = C.c_uint32(0)
+    rc = lib().k4_pe_insert_median_host(values.ctypes.data, len(values), C.byref(med))
+    if rc != 0:
+        raise K4Error(rc, "k4_pe_insert_median_host")
+    return int(med.value)
 
 
 def pba_classify_host(cnt7, ref_bases):

@@ -491,6 +491,16 @@ extern "C" int k4_pipeline_site_prefs(k4_pipeline* pl, int32_t ofs, k4_site_pref
   return k4_site_prefs_dev(pl->ix, pl->n_ends == 2 ? 1 : 0, v.n_reads, v.max_ml, ofs, v.d_rr, v.d_hits, v.d_pe, out, pl->s_comp);
 }
 
+// `kalign -3`: likewise over the pair records the global stages left; an SE pipeline has none
+extern "C" int k4_pipeline_pe_insert_dist(k4_pipeline* pl, k4_pe_insert_dist* out) {
+  if (!pl || !out) return K4_ERR_PARAMS;
+  if (pl->n_ends != 2) return k4_fail(pl->ix, K4_ERR_PARAMS, "k4_pipeline_pe_insert_dist: not a paired-end pipeline");
+  k4_pipeline_view v;
+  int rc = k4_pipeline_wait_aligned(pl, &v);
+  if (rc != K4_OK) return rc;
+  return k4_pe_insert_dist_dev(pl->ix, v.n_units, v.d_pe, out, pl->s_comp);
+}
+
 static int pipeline_format(k4_pipeline* pl, int bam, int sq_all, k4_sam_stats* stats, uint8_t* chrom_hit, uint64_t* sam_bytes);
 extern "C" int k4_pipeline_format(k4_pipeline* pl, k4_sam_stats* stats, uint8_t* chrom_hit, uint64_t* sam_bytes) {
   return pipeline_format(pl, 0, 0, stats, chrom_hit, sam_bytes);

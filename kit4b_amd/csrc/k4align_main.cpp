@@ -15,13 +15,15 @@
 //                                                                                  -> k4_pcr5_primer_correct_dev
 //   statistics files (-O) CKAligner::WriteSubDist :6469-6525, WriteBasicCountStats :4159-4300, ReportTargHitCnts :5458-5712,
 //                        the insert size file of ProcessPairedEnds :3092-3146     -> k4_pipeline_align_stats, k4_write_align_stats
+//   PE insert lengths per target (-3, with -O) CKAligner::ReportPEInsertLenDist :5321-5454, MedianInsertLen :5256-5319
+//                                                                                  -> k4_pipeline_pe_insert_dist, k4_write_pe_insert_dist
 //   loci constraints (-5) CKAligner::LoadLociConstraints :1363-1545, IdentifyConstraintViolations :2716-2765
 //                                                                                  -> k4_load_loci_constraints, k4_filter_loci_constraints_dev
 //   site preferences (-8, -9) CKAligner::ProcessSiteProbabilites :8708-8876, WriteSitePrefs :8910-8945
 //                                                                                  -> k4_pipeline_site_prefs, k4_write_site_prefs
 //   chromosome filters   CKAligner::FiltByChroms :4025-4091 (kalign -Z / -z; here --chromexclude / --chromeinclude)
 //                                                                                  -> k4_chrom_accept_mask, k4_filter_chroms_dev
-// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k -6 -O -5 -8 -9 -g (plus -@ <gpu>, -S <i/N> read slice);
+// Options follow kalign's letters: -i -u -I -o -s -e -m -n -U -d -D -E -l -L -r -R -X -N -c -a -A -x -k -6 -O -3 -5 -8 -9 -g (plus -@ <gpu>, -S <i/N> read slice);
 // kalign's -Z / -z go by their long names --chromexclude / --chromeinclude (the letters mean something else here).
 #include <errno.h>
 #include <fcntl.h>
@@ -67,6 +69,7 @@ struct Opts {
   std::string loci_file;            // -5 / --lociconstraints <file>: loci base constraints CSV (KAlignerCL.cpp:255)
   std::vector<std::string> chrom_excl, chrom_incl;  // --chromexclude / --chromeinclude <regex>, each repeatable (kalign -Z / -z, KAlignerCL.cpp:274-275)
   std::string stats_file;           // -O <file>: alignment statistics (KAlignerCL.cpp:256) and its two side files
+  bool pe_insert_dist = false;      // -3 / --petranslendist: per-target PE insert length distributions into <-O file>.peinserts.csv (KAlignerCL.cpp:288)
   std::string site_file;            // -8 / --siteprefs <file>: start-site octamer preferences (KAlignerCL.cpp:252)
   int site_ofs = -4;                // -9 / --siteprefsofs <-100..100>: cDfltRelSiteStartOfs (KAlignerCL.cpp:253,1053)
   double batch_mb = 0;              // -b <MB>: stream the input, this much text per file per batch (0: the whole input at once)
@@ -547,7 +550,7 @@ std::string clean_id(const std::string& raw) {
 void usage() {
   fprintf(stderr,
           "k4align -i reads.f[aq][.gz] [-i more ...] [-u mates ...] -I index.sfx -o out.sam|out.bam [-z bgzf level=6] [-s subs/100bp=5] [-e 1|2] [-m 0..3] [-n maxNs=1]\n"
-          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads | -M3 --experimentid id --readsetid id: packed base alleles to -o, no SAM] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-6 pcrprimersubs 0..5] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv] [-7 centroids.csv] [-K markerlen 25..500 [--markerpolythres 0..0.5=0.333]]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
+          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads | -M3 --experimentid id --readsetid id: packed base alleles to -o, no SAM] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-6 pcrprimersubs 0..5] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv [-3 PE insert lengths per target to stats.csv.peinserts.csv]] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv] [-7 centroids.csv] [-K markerlen 25..500 [--markerpolythres 0..0.5=0.333]]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
 }
 
 }  // namespace
@@ -668,6 +671,7 @@ struct Run : RunHeld {
   double s_read = 0, s_parse = 0, s_align = 0, s_write = 0;
   k4_pipeline_view v;        // the pipelined modes: all reads of the run, aligned
   uint64_t pl_sam_bytes = 0;
+  uint64_t stats_accepted = 0;  // -O: the accepted reads it counted (m_NARAccepted), which -3 goes by as well
   DevBlock keep_sam;         // -Z, -S i/N: the SAM body of the single batch stays on the device
   uint64_t keep_bytes = 0;
   std::vector<std::string> parts;  // -b: the batches' sorted bodies
@@ -803,6 +807,11 @@ struct Run : RunHeld {
       made.push_back(o.stats_file);
       made.push_back(side_name(o.stats_file, ".AlignCntsDist.csv"));
       if (pe) made.push_back(side_name(o.stats_file, ".GlobalPEInsertDist.csv"));
+      if (o.pe_insert_dist) {  // (KAligner.cpp:4731-4752)
+        const std::string fn = o.stats_file + ".peinserts.csv";
+        if (!create_empty(fn)) { fprintf(stderr, "k4align: unable to create/truncate PE insert length distributions file '%s'\n", fn.c_str()); return 5; }
+        made.push_back(fn);
+      }
       CK(k4_align_stats_collect(ix, 1));
     }
     if (!o.site_file.empty()) {  // created / truncated with the other outputs (KAligner.cpp:4471-4491); it stays empty when no read is accepted
@@ -1005,9 +1014,22 @@ struct Run : RunHeld {
       for (uint64_t q = 0; q <= as.len_stride; q++) as.m_sub[q] *= 2;
     }
     const int rc = k4_write_align_stats(ix, &as, loaded, o.ml_mode, max_ml, pe ? 1 : 0, o.stats_file.c_str());
+    stats_accepted = as.n_accepted;
     k4_free_align_stats(&as);
     if (rc != K4_OK) { fprintf(stderr, "k4align: %s\n", k4_last_error(ix)); return 5; }
     if (chatty) fprintf(stderr, "k4align: alignment statistics written to %s in %.2fs\n", o.stats_file.c_str(), secs(ts, now()));
+    return 0;
+  }
+  int write_pe_insert_dist() {  // -3 (PE with -O): ReportPEInsertLenDist walks the reads the writer reports (KAligner.cpp:771)
+    auto ts = now();
+    const std::string fn = o.stats_file + ".peinserts.csv";  // (:205-215: appended to the whole name)
+    k4_pe_insert_dist pd;
+    CK(k4_pipeline_pe_insert_dist(pl, &pd));
+    const uint32_t n_rows = pd.n_rows;
+    const int rc = k4_write_pe_insert_dist(ix, &pd, stats_accepted, fn.c_str());
+    k4_free_pe_insert_dist(&pd);
+    if (rc != K4_OK) { fprintf(stderr, "k4align: %s\n", k4_last_error(ix)); return 5; }
+    if (chatty) fprintf(stderr, "k4align: PE insert lengths of %u target sequences written to %s in %.2fs\n", n_rows, fn.c_str(), secs(ts, now()));
     return 0;
   }
   int write_site_prefs() {  // -8: ProcessSiteProbabilites runs in front of the writer (KAligner.cpp:743), over the reads it will report
@@ -1352,6 +1374,7 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
     if (o.fmode == 3) return r.write_pba();                  // -M3: that is the report
     if (o.min_snp_reads > 0) STEP(write_snps());             // -p, -S, -K, -7
     if (!o.stats_file.empty()) STEP(write_align_stats());    // -O
+    if (o.pe_insert_dist) STEP(write_pe_insert_dist());      // -3
     if (!o.site_file.empty()) STEP(write_site_prefs());      // -8
     STEP(format_records());
     r.s_align = secs(tg, now());
@@ -1515,6 +1538,7 @@ int main(int argc, char** argv) {
       case '-': {  // kalign's long names, for the options whose letters are taken here: --name value | --name=value
         std::string name = a.substr(2), v;
         const size_t eq = name.find('=');
+        if (name == "petranslendist") { o.pe_insert_dist = true; o.given += '3'; break; }  // the one long name that is a flag
         if (eq != std::string::npos) { v = name.substr(eq + 1); name.resize(eq); }
         else if (i + 1 < argc) v = argv[++i];
         else { usage(); return 1; }
@@ -1532,6 +1556,7 @@ int main(int argc, char** argv) {
         else { usage(); return 1; }
         break;
       }
+      case '3': o.pe_insert_dist = true; break;
       case '5': o.loci_file = val(); break;
       case '6': o.primer_subs = atoi(val().c_str()); break;
       case 'i': o.in1.push_back(val()); break;
@@ -1620,7 +1645,7 @@ int main(int argc, char** argv) {
   // -M3: `ngskit4b genpba` (kalignerPBA, KAlignerCL.cpp:1540-2290).  Its argument table (:1556-1628) is kalign's without the
   // second-segment phases, the side files and SNP calling; -w / -W are required there (arg_str1, cleaned :1697-1729)
   if (o.fmode == 3) {
-    for (const char c : std::string("aAOjJ895pP1N7K"))
+    for (const char c : std::string("aAOjJ8953pP1N7K"))
       if (o.given.find(c) != std::string::npos) { fprintf(stderr, "k4align: genpba '-M3' has no option '-%c'\n", c); return 1; }
     if (!o.snp_file.empty()) { fprintf(stderr, "k4align: genpba '-M3' calls no SNPs: no SNP file '-S%s'\n", o.snp_file.c_str()); return 1; }
     if (o.given.find('w') == std::string::npos || o.given.find('W') == std::string::npos) {
@@ -1680,6 +1705,12 @@ int main(int argc, char** argv) {
   if (o.primer_subs > 0 && o.ml_mode == 5) {  // (there every reported locus is a read of its own to the reference)
     fprintf(stderr, "k4align: PCR primer correction '-6' with every multiloci alignment reported '-r5' is not built\n");
     return 3;
+  }
+  // -3 is honoured in paired end processing alone and needs -O, whose name its file takes (KAlignerCL.cpp:571-598)
+  if (!pe) o.pe_insert_dist = false;
+  if (o.pe_insert_dist && o.stats_file.empty()) {
+    fprintf(stderr, "k4align: PE insert length distributions requested but no output statistics file '-O<file>' specified\n");
+    return 1;
   }
   // the statistics count over all reads of the run in one place (summing per-rank counters is not built)
   if (!o.stats_file.empty()) {

@@ -683,28 +683,33 @@ class SfxIndex:
         lib().k4_free_device(d_sam)
         return body, {"nar": list(stats.nar), "plus": stats.plus, "minus": stats.minus, "n_lines": stats.n_lines}, chrom_hit
 
-    def snp_csv(self, reads, out=None, hits=None, pe_recs=None, min_snp_reads=5, qvalue=0.05, snp_nonref_pcnt=25.0):
-        """kalign's SNP calling (main CSV) over host-side results: SE (out + hits records) or PE (pe_recs, reads interleaved).
-        Returns (CSV text, number of SNPs)."""
+    def _upload(self, reads, *arrays):
+        """the reads (16 zero bytes behind them), their offsets and lengths, then each of `arrays`, as device byte tensors; and the
+        number of reads"""
         import torch
 
         dev = torch.device("cuda", self.info()["device"])
         cat, offs, lens = _flatten(reads)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
-        d_reads = torch.from_numpy(np.concatenate([cat, np.zeros(16, np.uint8)])).to(dev)
-        d_offs, d_lens = t(offs), t(lens)
+        return [torch.from_numpy(np.concatenate([cat, np.zeros(16, np.uint8)])).to(dev), t(offs), t(lens)] + [t(a) for a in arrays], len(lens)
+
+    def _records(self, reads, out, hits, pe_recs):
+        """the record arguments of a report stage's entry point, `pe` to `d_lens`, over host-side results: SE (out + hits records) or
+        PE (pe_recs, reads interleaved).  Returns (arguments, the tensors they point into: keep them until the call is over)."""
+        if pe_recs is not None:
+            keep, n = self._upload(reads, pe_recs)
+            return (1, n // 2, None, None, 1, keep[3].data_ptr(), keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr()), keep
+        keep, n = self._upload(reads, out, hits)
+        max_ml = 1 if hits.ndim == 1 else hits.shape[1]
+        return (0, n, keep[3].data_ptr(), keep[4].data_ptr(), max_ml, None, keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr()), keep
+
+    def snp_csv(self, reads, out=None, hits=None, pe_recs=None, min_snp_reads=5, qvalue=0.05, snp_nonref_pcnt=25.0):
+        """kalign's SNP calling (main CSV) over host-side results: SE (out + hits records) or PE (pe_recs, reads interleaved).
+        Returns (CSV text, number of SNPs)."""
+        rec, keep = self._records(reads, out, hits, pe_recs)
         L = lib()
         csv, nb, ns = C.c_void_p(), C.c_uint64(), C.c_uint64()
-        if pe_recs is not None:
-            d_pe = t(pe_recs)
-            self._ck(L.k4_snp_csv_dev(self.h, 1, len(lens) // 2, None, None, 1, d_pe.data_ptr(), d_reads.data_ptr(), d_offs.data_ptr(),
-                                      d_lens.data_ptr(), min_snp_reads, qvalue, snp_nonref_pcnt, C.byref(csv), C.byref(nb), C.byref(ns), 0))
-        else:
-            d_rr, d_hits = t(out), t(hits)
-            max_ml = 1 if hits.ndim == 1 else hits.shape[1]
-            self._ck(L.k4_snp_csv_dev(self.h, 0, len(lens), d_rr.data_ptr(), d_hits.data_ptr(), max_ml, None, d_reads.data_ptr(),
-                                      d_offs.data_ptr(), d_lens.data_ptr(), min_snp_reads, qvalue, snp_nonref_pcnt, C.byref(csv), C.byref(nb),
-                                      C.byref(ns), 0))
+        self._ck(L.k4_snp_csv_dev(self.h, *rec, min_snp_reads, qvalue, snp_nonref_pcnt, C.byref(csv), C.byref(nb), C.byref(ns), 0))
         text = C.string_at(csv.value, nb.value).decode()
         L.k4_free_host(csv)
         return text, ns.value
@@ -715,86 +720,32 @@ class SfxIndex:
         (.covsegs.wig), "disnp" (.disnp.csv), "trisnp" (.trisnp.csv), and "n_snps".  marker_len (kalign -K, 25..500; marker_poly_thres:
         --markerpolythres, default 1/3) adds "markers" (<snp file>.markers) and "n_markers"; centroids=True (kalign -7) adds
         "centroids" (k4_snp_run2_dev)."""
-        import torch
-
+        rec, keep = self._records(reads, out, hits, pe_recs)
+        L = lib()
+        head = (self.h, 1 if vcf else 0, *rec, min_snp_reads, qvalue, snp_nonref_pcnt)
+        f2 = SnpFiles2()
+        f, texts = f2.files, [(f2.files, k) for k in ("snp", "wig", "disnp", "trisnp")]
         if marker_len or centroids:
-            return self._snp_files2(reads, out, hits, pe_recs, min_snp_reads, qvalue, snp_nonref_pcnt, vcf, marker_len, marker_poly_thres, centroids)
-        dev = torch.device("cuda", self.info()["device"])
-        cat, offs, lens = _flatten(reads)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
-        d_reads = torch.from_numpy(np.concatenate([cat, np.zeros(16, np.uint8)])).to(dev)
-        d_offs, d_lens = t(offs), t(lens)
-        L = lib()
-        f = SnpFiles()
-        if pe_recs is not None:
-            d_pe = t(pe_recs)
-            self._ck(L.k4_snp_run_dev(self.h, 1 if vcf else 0, 1, len(lens) // 2, None, None, 1, d_pe.data_ptr(), d_reads.data_ptr(), d_offs.data_ptr(),
-                                      d_lens.data_ptr(), min_snp_reads, qvalue, snp_nonref_pcnt, C.byref(f), 0))
+            o = SnpOpts(int(marker_len), 1 if centroids else 0, DFLT_MARKER_POLY_THRES if marker_poly_thres is None else float(marker_poly_thres))
+            self._ck(L.k4_snp_run2_dev(*head, C.byref(o), C.byref(f2), 0))
+            texts += [(f2, k) for k, on in (("markers", marker_len), ("centroids", centroids)) if on]
         else:
-            d_rr, d_hits = t(out), t(hits)
-            max_ml = 1 if hits.ndim == 1 else hits.shape[1]
-            self._ck(L.k4_snp_run_dev(self.h, 1 if vcf else 0, 0, len(lens), d_rr.data_ptr(), d_hits.data_ptr(), max_ml, None, d_reads.data_ptr(),
-                                      d_offs.data_ptr(), d_lens.data_ptr(), min_snp_reads, qvalue, snp_nonref_pcnt, C.byref(f), 0))
+            self._ck(L.k4_snp_run_dev(*head, C.byref(f), 0))
         res = {"n_snps": f.n_snps}
-        for k in ("snp", "wig", "disnp", "trisnp"):
-            res[k] = C.string_at(getattr(f, k), getattr(f, k + "_bytes")).decode()
-            L.k4_free_host(getattr(f, k))
-        return res
-
-    def _snp_files2(self, reads, out, hits, pe_recs, min_snp_reads, qvalue, snp_nonref_pcnt, vcf, marker_len, marker_poly_thres, centroids):
-        import torch
-
-        dev = torch.device("cuda", self.info()["device"])
-        cat, offs, lens = _flatten(reads)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
-        d_reads = torch.from_numpy(np.concatenate([cat, np.zeros(16, np.uint8)])).to(dev)
-        d_offs, d_lens = t(offs), t(lens)
-        L = lib()
-        f = SnpFiles2()
-        o = SnpOpts(int(marker_len), 1 if centroids else 0, DFLT_MARKER_POLY_THRES if marker_poly_thres is None else float(marker_poly_thres))
-        if pe_recs is not None:
-            d_pe = t(pe_recs)
-            self._ck(L.k4_snp_run2_dev(self.h, 1 if vcf else 0, 1, len(lens) // 2, None, None, 1, d_pe.data_ptr(), d_reads.data_ptr(), d_offs.data_ptr(),
-                                       d_lens.data_ptr(), min_snp_reads, qvalue, snp_nonref_pcnt, C.byref(o), C.byref(f), 0))
-        else:
-            d_rr, d_hits = t(out), t(hits)
-            max_ml = 1 if hits.ndim == 1 else hits.shape[1]
-            self._ck(L.k4_snp_run2_dev(self.h, 1 if vcf else 0, 0, len(lens), d_rr.data_ptr(), d_hits.data_ptr(), max_ml, None, d_reads.data_ptr(),
-                                       d_offs.data_ptr(), d_lens.data_ptr(), min_snp_reads, qvalue, snp_nonref_pcnt, C.byref(o), C.byref(f), 0))
-        res = {"n_snps": f.files.n_snps}
-        for k in ("snp", "wig", "disnp", "trisnp"):
-            res[k] = C.string_at(getattr(f.files, k), getattr(f.files, k + "_bytes")).decode()
-            L.k4_free_host(getattr(f.files, k))
         if marker_len:
-            res["markers"], res["n_markers"] = C.string_at(f.markers, f.markers_bytes).decode(), f.n_markers
-            L.k4_free_host(f.markers)
-        if centroids:
-            res["centroids"] = C.string_at(f.centroids, f.centroids_bytes).decode()
-            L.k4_free_host(f.centroids)
+            res["n_markers"] = f2.n_markers
+        for st, k in texts:
+            res[k] = C.string_at(getattr(st, k), getattr(st, k + "_bytes")).decode()
+            L.k4_free_host(getattr(st, k))
         return res
 
     def pba(self, reads, out=None, hits=None, pe_recs=None, experiment_id="Unspecified", readset_id="Unspecified"):
         """`ngskit4b genpba` over host-side results (k4_pba_run_dev): SE (out + hits records) or PE (pe_recs, reads interleaved).
         Returns {"pba": the .pba file's bytes, "wig": the .covsegs.wig text, "n_chroms": the number of sequence records}."""
-        import torch
-
-        dev = torch.device("cuda", self.info()["device"])
-        cat, offs, lens = _flatten(reads)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
-        d_reads = torch.from_numpy(np.concatenate([cat, np.zeros(16, np.uint8)])).to(dev)
-        d_offs, d_lens = t(offs), t(lens)
+        rec, keep = self._records(reads, out, hits, pe_recs)
         L = lib()
         f = PbaFiles()
-        ids = (os.fsencode(experiment_id), os.fsencode(readset_id))
-        if pe_recs is not None:
-            d_pe = t(pe_recs)
-            self._ck(L.k4_pba_run_dev(self.h, 1, len(lens) // 2, None, None, 1, d_pe.data_ptr(), d_reads.data_ptr(), d_offs.data_ptr(),
-                                      d_lens.data_ptr(), *ids, C.byref(f), 0))
-        else:
-            d_rr, d_hits = t(out), t(hits)
-            max_ml = 1 if hits.ndim == 1 else hits.shape[1]
-            self._ck(L.k4_pba_run_dev(self.h, 0, len(lens), d_rr.data_ptr(), d_hits.data_ptr(), max_ml, None, d_reads.data_ptr(),
-                                      d_offs.data_ptr(), d_lens.data_ptr(), *ids, C.byref(f), 0))
+        self._ck(L.k4_pba_run_dev(self.h, *rec, os.fsencode(experiment_id), os.fsencode(readset_id), C.byref(f), 0))
         res = {"pba": C.string_at(f.pba, f.pba_bytes), "wig": C.string_at(f.wig, f.wig_bytes).decode(), "n_chroms": f.n_chroms}
         L.k4_free_host(f.pba)
         L.k4_free_host(f.wig)
@@ -803,15 +754,8 @@ class SfxIndex:
     def post_stages(self, reads, out, hits, seg2, min_flank_exacts=0, orphan_splice=False, orphan_indel=False):
         """AutoTrimFlanks / RemoveOrphanSpliceJuncts / RemoveOrphanMicroInDels (KAligner.cpp:653-686) over host arrays of SE
         results, in the reference's order; returns (out, hits, counts)."""
-        import torch
-
-        dev = torch.device("cuda", self.info()["device"])
-        cat, offs, lens = _flatten(reads)
         n, max_ml = hits.shape
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
-        d_rr, d_hits, d_seg2 = t(out), t(hits), t(seg2)
-        d_reads = torch.from_numpy(np.concatenate([cat, np.zeros(16, np.uint8)])).to(dev)
-        d_offs, d_lens = t(offs), t(lens)
+        (d_reads, d_offs, d_lens, d_rr, d_hits, d_seg2), _ = self._upload(reads, out, hits, seg2)
         cnt = {}
         c = C.c_int64(0)
         if min_flank_exacts > 0:

@@ -19,7 +19,6 @@
 #include <string.h>
 #include <algorithm>
 #include <chrono>
-#include <future>
 #include <memory>
 #include <string>
 #include <vector>
@@ -104,71 +103,47 @@ __global__ void __launch_bounds__(256) k4k_pba_coverage(SnpArgs a, T* __restrict
 
 }  // namespace
 
+// the record of a sequence (:7254-7259): name length, name, NUL, sequence length, then room for the bytes; returns where they start
+static size_t pba_record(std::vector<std::vector<uint8_t>>& recs, const char* name, uint32_t clen) {
+  const size_t nl = std::min<size_t>(strlen(name), 255), head = 1 + nl + 1 + 4;
+  recs.emplace_back(head + (size_t)clen);
+  std::vector<uint8_t>& rec = recs.back();
+  rec[0] = (uint8_t)nl;
+  memcpy(&rec[1], name, nl);
+  for (int k = 0; k < 4; k++) rec[2 + nl + k] = (uint8_t)(clen >> (8 * k));
+  return head;
+}
+
 // CUtility::TrimQuotedWhitespcExtd + ReduceWhitespace are the front end's business (k4align); the ids arrive here as they are written
 extern "C" int k4_pba_run_dev(k4_index* ix, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml, const void* d_pe,
                               const void* d_reads, const void* d_offs, const void* d_lens, const char* experiment_id, const char* readset_id,
                               k4_pba_files* out, void* stream) {
   if (!ix || !out) return K4_ERR_PARAMS;
-  memset(out, 0, sizeof(*out));
+  K4HandOut hand(out);
   if (n_units < 0 || !experiment_id || !readset_id) return k4_fail(ix, K4_ERR_PARAMS, "packed base alleles: parameters out of range");
-  SnpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.ix = ix->d;
-  K4_TRY(k4s_read_set(ix, pe, n_units, d_rr, d_hits, max_ml, d_pe, nullptr, d_reads, d_offs, d_lens, K4RS_HITS | K4RS_READS | K4RS_UNITS, &a.rs));
-  K4_HIP(ix, hipSetDevice(ix->device));
-  hipStream_t st = (hipStream_t)stream;
-  uint32_t max_len = 0;
-  for (const k4_entry& e : ix->entries) max_len = std::max(max_len, e.seq_len);
-  const size_t S = (size_t)max_len + 16;
-  std::vector<uint8_t> chrom_hit((size_t)ix->d.n_entries + 1, 0);
-  std::vector<uint64_t> ent_start_h((size_t)ix->d.n_entries, 0);
-  K4DevBuf cnt, tot, pbab, covb, covmax;
-  if (a.rs.n_reads > 0 && ix->d.n_entries) {
-    K4DevBuf flags;
-    K4_HIP(ix, flags.alloc(chrom_hit.size()));
-    K4_HIP(ix, hipMemsetAsync(flags.p, 0, chrom_hit.size(), st));
-    hipLaunchKernelGGL(k4k_snp_mark, dim3((unsigned)std::min<int64_t>((a.rs.n_reads + 255) / 256, 2048)), dim3(256), 0, st, a, flags.as<uint8_t>(), ix->d.n_entries);
-    K4_HIP(ix, hipMemcpyAsync(chrom_hit.data(), flags.p, chrom_hit.size(), hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipMemcpyAsync(ent_start_h.data(), ix->ent_start.p, ent_start_h.size() * 8, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
-  }
-  // :7224: the header once, a NUL behind it; the records follow
-  std::vector<std::vector<uint8_t>> recs;  // one per chromosome with alignments, in chromosome order
-  std::string hdr = std::string("Type:PbA\nVersion:1\nExperimentID:") + experiment_id + "\nReferenceID:" + ix->dataset + "\nReadsetID:" + readset_id;
   const char* times_path = getenv("K4_PBA_TIMES");
   FILE* times = times_path && *times_path ? fopen(times_path, "a") : nullptr;
   std::unique_ptr<FILE, int (*)(FILE*)> times_close(times, fclose);
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  if (times)
-    for (hipEvent_t& e : ev) K4_HIP(ix, hipEventCreate(&e));
-  struct EvGuard { hipEvent_t* ev; ~EvGuard() { for (int k = 0; k < 3; k++) if (ev[k]) (void)hipEventDestroy(ev[k]); } } ev_guard{ev};
-  std::vector<std::future<WigOut>> wig_jobs;  // (behind the trace file: the walks are waited for before it closes)
+  WigQueue wig;  // (behind the trace file: the walks are waited for before it closes)
+  wig.trace = times;
+  PileupWalk w;
+  K4_TRY(w.open(ix, K4Records{pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens}, stream, times != nullptr));
+  hipStream_t st = w.st;
+  const SnpArgs& a = w.a;
+  K4DevBuf pbab, covb, covmax;
+  // :7224: the header once, a NUL behind it; the records follow
+  std::vector<std::vector<uint8_t>> recs;  // one per chromosome with alignments, in chromosome order
+  const std::string hdr = std::string("Type:PbA\nVersion:1\nExperimentID:") + experiment_id + "\nReferenceID:" + ix->dataset + "\nReadsetID:" + readset_id;
   auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-  for (uint32_t chrom = 1; chrom <= ix->d.n_entries && a.rs.n_reads > 0; chrom++) {
-    if (!chrom_hit[chrom]) continue;
-    if (!cnt.p) {
-      K4_HIP(ix, cnt.alloc(7 * S * 4));
-      K4_HIP(ix, tot.alloc(4 * 8));
-      K4_HIP(ix, pbab.alloc(S));
-      K4_HIP(ix, covb.alloc(S * 4));
+  for (bool got = false;;) {
+    K4_TRY(w.next(&got));
+    if (!got) break;
+    if (!pbab.p) {
+      K4_HIP(ix, pbab.alloc(w.S));
+      K4_HIP(ix, covb.alloc(w.S * 4));
       K4_HIP(ix, covmax.alloc(4));
     }
-    const k4_entry& e = ix->entries[chrom - 1];
-    a.chrom_id = chrom; a.clen = e.seq_len; a.cnt = cnt.as<uint32_t>(); a.tot = tot.as<unsigned long long>();
-    a.cs = ent_start_h[chrom - 1];
-    const size_t Sc = K4_SNP_STRIDE(a);
-    if (times) K4_HIP(ix, hipEventRecord(ev[0], st));
-    K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 7 * Sc * 4, st));
-    K4_HIP(ix, hipMemsetAsync(tot.p, 0, 32, st));
     K4_HIP(ix, hipMemsetAsync(covmax.p, 0, 4, st));
-    if (times) K4_HIP(ix, hipEventRecord(ev[1], st));
-    hipLaunchKernelGGL(k4k_snp_pileup, dim3(2048), dim3(256), 0, st, a);
-    if (times) K4_HIP(ix, hipEventRecord(ev[2], st));
-    unsigned long long t3[4] = {0, 0, 0, 0};
-    K4_TRY(k4s_read_back(ix, &t3, tot.p, st));
-    float ms_memset = 0, ms_pileup = 0;
-    if (times) { K4_HIP(ix, hipEventElapsedTime(&ms_memset, ev[0], ev[1])); K4_HIP(ix, hipEventElapsedTime(&ms_pileup, ev[1], ev[2])); }
-    if (t3[2] == 0) continue;  // no alignment on this chromosome: no record (the reference never gets to OutputSNPs for it)
     const dim3 grid((unsigned)(((uint64_t)a.clen + 256 * K4_PBA_LPT - 1) / (256 * K4_PBA_LPT)));
     auto t_cls = std::chrono::steady_clock::now();
     hipLaunchKernelGGL(k4k_pba_classify, grid, dim3(256), 0, st, a, pbab.as<uint8_t>(), covb.as<uint8_t>(), covmax.as<uint32_t>());
@@ -176,69 +151,32 @@ extern "C" int k4_pba_run_dev(k4_index* ix, int pe, int64_t n_units, const void*
     uint32_t mx = 0;
     K4_TRY(k4s_read_back(ix, &mx, covmax.p, st));
     const double ms_classify = ms_since(t_cls);
-    // the record (:7254-7259): name length, name, NUL, sequence length, then the bytes straight from the device
-    const size_t nl = std::min<size_t>(strlen(e.name), 255), head = 1 + nl + 1 + 4;
-    recs.emplace_back(head + (size_t)a.clen);
-    std::vector<uint8_t>& rec = recs.back();
-    rec[0] = (uint8_t)nl;
-    memcpy(&rec[1], e.name, nl);
-    rec[1 + nl] = 0;
-    for (int k = 0; k < 4; k++) rec[2 + nl + k] = (uint8_t)(a.clen >> (8 * k));
+    const size_t head = pba_record(recs, w.e->name, a.clen);
     const int width = mx < 256 ? 1 : mx < 65536 ? 2 : 4;
     auto t_wide = std::chrono::steady_clock::now();
     if (width == 2) hipLaunchKernelGGL(k4k_pba_coverage<uint16_t>, grid, dim3(256), 0, st, a, covb.as<uint16_t>());
     else if (width == 4) hipLaunchKernelGGL(k4k_pba_coverage<uint32_t>, grid, dim3(256), 0, st, a, covb.as<uint32_t>());
+    K4_HIP(ix, hipGetLastError());
     if (times && width > 1) K4_HIP(ix, hipStreamSynchronize(st));
     const double ms_wide = width > 1 ? ms_since(t_wide) : 0.0;
     auto t_down = std::chrono::steady_clock::now();
-    K4_HIP(ix, hipMemcpyAsync(rec.data() + head, pbab.p, a.clen, hipMemcpyDeviceToHost, st));
-    std::unique_ptr<uint8_t[]> cov(new uint8_t[((size_t)a.clen + 1) * (size_t)width]);
-    K4_HIP(ix, hipMemcpyAsync(cov.get(), covb.p, (size_t)a.clen * (size_t)width, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
+    K4_HIP(ix, hipMemcpyAsync(recs.back().data() + head, pbab.p, a.clen, hipMemcpyDeviceToHost, st));
+    // no track line (:8192), the loci counted from 1, every chromosome's open span closed at its end (:7303)
+    K4_TRY(wig.add(ix, st, covb.p, width, a.clen, w.e->name, 1u, true));
     const double ms_down = ms_since(t_down);
-    if (wig_jobs.size() >= 12) wig_jobs[wig_jobs.size() - 12].wait();  // (at most twelve chromosomes' walks in flight)
-    wig_jobs.push_back(std::async(std::launch::async, [times](std::unique_ptr<uint8_t[]> c, int w, uint32_t n, std::string nm) {
-      auto t0 = std::chrono::steady_clock::now();
-      WigOut o = wig_chromosome(std::move(c), w, n, std::move(nm), 1u);
-      if (times) {  // (the walks of several chromosomes run side by side: each line is written whole)
-        char line[160];
-        const int k = snprintf(line, sizeof(line), "walk %u %.3f\n", n, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        fwrite(line, 1, (size_t)k, times);
-      }
-      return o;
-    }, std::move(cov), width, a.clen, std::string(e.name)));
     if (times)
-      fprintf(times, "chrom %s len %u reads %llu max_cov %u width %d memset_ms %.3f pileup_ms %.3f classify_ms %.3f wide_ms %.3f download_ms %.3f\n", e.name,
-              a.clen, t3[2], mx, width, ms_memset, ms_pileup, ms_classify, ms_wide, ms_down);
+      fprintf(times, "chrom %s len %u reads %llu max_cov %u width %d memset_ms %.3f pileup_ms %.3f classify_ms %.3f wide_ms %.3f download_ms %.3f\n", w.e->name,
+              a.clen, w.t[2], mx, width, w.ms_memset, w.ms_pileup, ms_classify, ms_wide, ms_down);
   }
-  // no track line (:8192), every chromosome's open span closed at its end (:7303)
-  std::vector<WigOut> parts;
-  parts.reserve(wig_jobs.size());
-  size_t wig_total = 0;
-  for (std::future<WigOut>& f : wig_jobs) {
-    parts.push_back(f.get());
-    wig_total += parts.back().body.size() + parts.back().tail.size();
-  }
-  size_t pba_total = 0;
+  size_t pba_total = recs.empty() ? 0 : hdr.size() + 1;  // (the header is written with the first chromosome: no chromosome, an empty file)
   for (const std::vector<uint8_t>& r : recs) pba_total += r.size();
-  if (!recs.empty()) pba_total += hdr.size() + 1;  // (the header is written with the first chromosome: no chromosome, an empty file)
-  uint8_t* po = (uint8_t*)malloc(pba_total + 1);
-  char* wo = (char*)malloc(wig_total + 1);
-  if (!po || !wo) { free(po); free(wo); return k4_fail(ix, K4_ERR_MEM, "out of memory"); }
+  K4_TRY(hand.block(ix, &out->pba, &out->pba_bytes, pba_total));
   size_t at = 0;
-  if (!recs.empty()) { memcpy(po, hdr.c_str(), hdr.size() + 1); at = hdr.size() + 1; }
-  for (const std::vector<uint8_t>& r : recs) { memcpy(po + at, r.data(), r.size()); at += r.size(); }
-  po[at] = 0;
-  at = 0;
-  for (const WigOut& w : parts) {
-    memcpy(wo + at, w.body.data(), w.body.size()); at += w.body.size();
-    memcpy(wo + at, w.tail.data(), w.tail.size()); at += w.tail.size();
-  }
-  wo[at] = 0;
-  out->pba = po; out->pba_bytes = pba_total;
-  out->wig = wo; out->wig_bytes = wig_total;
+  if (!recs.empty()) { memcpy(out->pba, hdr.c_str(), hdr.size() + 1); at = hdr.size() + 1; }
+  for (const std::vector<uint8_t>& r : recs) { memcpy(out->pba + at, r.data(), r.size()); at += r.size(); }
+  K4_TRY(wig.finish(ix, nullptr, hand, &out->wig, &out->wig_bytes));
   out->n_chroms = recs.size();
-  return K4_OK;
+  return hand.ok();
 }
 
 // the rule alone, on the host: no device, no index.  cnt7: seven arrays of `stride` words each (ref, nonref, A, C, G, T, N), as the

@@ -11,8 +11,9 @@
 // chromosome -- with the reference's own floating-point operations in its order (long double n-choose-k included).
 // The files kalign writes beside it: the coverage WIG (host threads, one per chromosome) and the DiSNP / TriSNP haplotype files
 // (:7767-8101; one thread per alignment finds the called loci it covers and counts its base combination for every run of two /
-// three of them).  The pile-up, the pass that marks the sequences with alignments and the WIG walk live in k4_pileup.h: genpba's packed
-// base alleles (k4_pba.hip) start from the same counts.  Not built: the BED form.  Equal p-values keep locus order in the ranking (the
+// three of them).  The pile-up, the walk over the sequences with alignments, the WIG queue and the hand-out of the texts live in
+// k4_pileup.h: genpba's packed base alleles (k4_pba.hip) start from the same counts.  A run is one SnpRun and named steps over it
+// (snp_sequence has their order); every entry point fills a SnpOpts and comes through snp_files.  Not built: the BED form.  Equal p-values keep locus order in the ranking (the
 // reference's multi-threaded quicksort leaves them in no defined order).
 // With the options of k4_snp_run2_dev two more files come out of the same counts:
 //   SNP centroids (kalign -7; :7380-7398, :8104-8133, :8626-8660): how often each of the 4^7 reference 7-mers lies around a locus
@@ -26,8 +27,6 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
-#include <future>
-#include <memory>
 #include <string>
 #include <vector>
 #include <hip/hip_runtime.h>
@@ -321,91 +320,417 @@ struct LociPV {
   double pvalue, bkgnd;
   uint32_t cent, marker_id, n_poly;
 };
-
-// what k4_snp_run2_dev adds to a run: the options, the centroid table and the marker text it fills
-struct SnpExtra {
-  int marker_len = 0;
-  double poly_thres = 0.0;
-  bool want_centroids = false;
-  std::string markers;
-  uint64_t n_markers = 0;  // m_MarkerID: counted over the whole run
-  std::string centroids;
-};
 struct Centroid { uint64_t n_insts, n_snps, ref_cnt, by_base[5]; };
 const uint32_t kMarkerChunk = 4096;  // candidates per launch of k4k_snp_markers: one wave each fills the device; the output stays below 2.1 MB
+const uint32_t kCandCap = 1u << 22;  // candidate loci per chromosome kept on the device (more: the call fails loudly)
+
+// what an entry point asks of a run: kalign's options and which files it wants beside the SNP file
+struct SnpOpts {
+  int vcf;
+  int32_t min_snp_reads;
+  double qvalue, nonref_pcnt;
+  bool want_wig, want_hap;
+  int marker_len = 0;  // k4_snp_run2_dev: 0 = no markers
+  double poly_thres = 0.0;
+  bool want_centroids = false;
+};
+
+// ---- the host-only steps: plain functions of their inputs ------------------------------------------------------------------------
+static std::string snp_header(int vcf, const std::string& dataset) {
+  if (vcf)
+    return "##fileformat=VCFv4.1\n##source=k4align1.0\n##reference=" + dataset +
+           "\n##INFO=<ID=AF,Number=A,Type=Float,Description=\"Allele Frequency\">\n##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Read Depth\">\n"
+           "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
+  return "\"SNP_ID\",\"ElType\",\"Species\",\"Chrom\",\"StartLoci\",\"EndLoci\",\"Len\",\"Strand\",\"Rank\",\"PValue\",\"Bases\",\"Mismatches\",\"RefBase\","
+         "\"MMBaseA\",\"MMBaseC\",\"MMBaseG\",\"MMBaseT\",\"MMBaseN\",\"BackgroundSubRate\",\"TotWinBases\",\"TotWinMismatches\",\"MarkerID\",\"NumPolymorphicSites\"\n";
+}
+// OutputSNPs' background rate and noise test (:7320, :7425-7450) over a sequence's candidates; tot: the pile-up's totals
+static void snp_noise_gate(const std::vector<Cand>& hc, const unsigned long long* tot, std::vector<LociPV>* pv) {
+  double global_rate = (double)tot[1] / (double)(1 + tot[0] + tot[1]);
+  global_rate = std::max(0.005, global_rate);  // cMinSeqErrRate
+  pv->clear();
+  for (const Cand& c : hc) {
+    const uint32_t ltmm = c.n_nonref <= c.loc_mm ? c.loc_mm - c.n_nonref : 0;
+    const uint32_t ltm = c.n_ref < c.loc_m ? c.loc_m - c.n_ref : 0;
+    double local_rate;
+    if ((ltmm + ltm) == 0) local_rate = global_rate;
+    else {
+      local_rate = (double)ltmm / (double)(ltmm + ltm);
+      if (local_rate < global_rate) local_rate = global_rate;
+    }
+    if (local_rate > 0.20) continue;  // cMaxBkgdNoiseThres
+    LociPV p;
+    const int tot_bases = (int)(c.n_ref + c.n_nonref);
+    p.pvalue = 0.0; p.cent = c.cent; p.marker_id = 0; p.n_poly = 0;
+    p.loci = c.loci; p.rank = 0; p.bkgnd = local_rate; p.local_reads = ltmm + ltm; p.local_subs = ltmm;
+    p.num_reads = (uint32_t)tot_bases; p.num_subs = c.n_nonref;
+    for (int b = 0; b < 5; b++) p.by_base[b] = c.by_base[b];
+    p.ref_base = c.ref_base > 4 ? 4 : c.ref_base;
+    pv->push_back(p);
+  }
+}
+// ranks by p-value (equal ones keep locus order: a stable sort), Benjamini-Hochberg at qvalue (:7567-7640); leaves the accepted
+// loci, ranked, in locus order
+static void snp_bh_cut(std::vector<LociPV>* pv, double qvalue) {
+  std::stable_sort(pv->begin(), pv->end(), [](const LociPV& x, const LociPV& y) { return x.pvalue < y.pvalue; });
+  size_t n_acc = 0;
+  for (size_t k = 0; k < pv->size(); k++) {
+    const double adj = ((k + 1) / (double)pv->size()) * qvalue;
+    if ((*pv)[k].pvalue >= adj) break;
+    (*pv)[k].rank = (uint32_t)(k + 1);
+    n_acc++;
+  }
+  pv->resize(n_acc);
+  std::sort(pv->begin(), pv->end(), [](const LociPV& x, const LociPV& y) { return x.loci < y.loci; });
+}
+// a VCF record (:7650-7696): alternative alleles with at least a tenth of the strongest one's count, their frequencies, phred of the
+// p-value.  alts / freq are the run's: the reference never clears its two strings, so a SNP whose mismatches are all N prints what
+// the SNP before it left there
+static void snp_vcf_line(std::string* text, const char* chrom, const LociPV& p, uint64_t id, char* alts, char* freq) {
+  uint32_t thres = 0;
+  for (uint32_t b = 0; b < 4; b++)
+    if (b != p.ref_base && p.by_base[b] > thres) thres = p.by_base[b];
+  thres = std::max((thres + 5) / 10, 1u);
+  int ao = 0, fo = 0;
+  for (uint32_t b = 0; b < 4; b++) {
+    if (b == p.ref_base || p.by_base[b] < thres) continue;
+    if (ao > 0) { alts[ao++] = ','; freq[fo++] = ','; }
+    alts[ao++] = "ACGT"[b]; alts[ao] = 0;
+    fo += sprintf(&freq[fo], "%1.4f", (double)p.by_base[b] / p.num_reads);
+  }
+  const int phred = p.pvalue < 0.0000000001 ? 100 : (int)(0.5 + (10.0 * log10(1.0 / p.pvalue)));
+  char line[512];
+  const int n = snprintf(line, sizeof(line), "%s\t%u\tSNP%d\t%c\t%s\t%d\tPASS\tAF=%s;DP=%d\n", chrom, p.loci + 1, (int)id, "ACGTN"[p.ref_base], alts, phred, freq,
+                         (int)p.num_reads);
+  text->append(line, (size_t)n);
+}
+// a line of the main CSV (:7698-7760); n_acc: the sequence's called loci, which the score is relative to
+static void snp_csv_line(std::string* text, const std::string& dataset, const char* chrom, LociPV p, uint64_t id, size_t n_acc) {
+  int rel = (int)(999 - ((999 * (int64_t)p.rank) / (int64_t)n_acc));
+  if (rel < 1) rel = 1;
+  p.by_base[p.ref_base] = p.num_reads - p.num_subs;  // :7698 (on this path only, and behind the centroid tally)
+  char line[512];
+  const int n = snprintf(line, sizeof(line), "%d,\"SNP\",\"%s\",\"%s\",%d,%d,1,\"+\",%d,%f,%d,%d,\"%c\",%d,%d,%d,%d,%d,%f,%d,%d,%d,%d\n", (int)id, dataset.c_str(),
+                         chrom, (int)p.loci, (int)p.loci, rel, p.pvalue, (int)p.num_reads, (int)p.num_subs, "ACGTN"[p.ref_base], (int)p.by_base[0],
+                         (int)p.by_base[1], (int)p.by_base[2], (int)p.by_base[3], (int)p.by_base[4], p.bkgnd, (int)p.local_reads, (int)p.local_subs,
+                         (int)p.marker_id, (int)p.n_poly);
+  text->append(line, (size_t)n);
+}
+// the centroid file (:8626-8660): every 7-mer, whether seen or not
+static std::string snp_centroid_text(const std::vector<unsigned long long>& insts, const std::vector<Centroid>& rows) {
+  std::string ct = "\"CentroidID\",\"Seq\",\"NumInsts\",\"NumSNPs\",\"RefBase\",\"RefBaseCnt\",\"BaseA\",\"BaseC\",\"BaseG\",\"BaseT\",\"BaseN\"\n";
+  char line[256];
+  for (uint32_t id = 0; id < K4_CENT_BINS; id++) {
+    char sq[8];
+    for (int k = 0; k < 7; k++) sq[k] = "ACGT"[(id >> (2 * (6 - k))) & 3u];
+    sq[7] = 0;
+    const Centroid& r = rows[id];
+    const int n = snprintf(line, sizeof(line), "%d,\"%s\",%d,%d,\"%c\",%d,%d,%d,%d,%d,%d\n", (int)id + 1, sq, (int)insts[id], (int)r.n_snps, sq[3], (int)r.ref_cnt,
+                           (int)r.by_base[0], (int)r.by_base[1], (int)r.by_base[2], (int)r.by_base[3], (int)r.by_base[4]);
+    ct.append(line, (size_t)n);
+  }
+  return ct;
+}
+
+// a run: the walk over the sequences, the device buffers of SNP calling alone, what the sequences leave behind, and the steps
+// (snp_sequence has their order)
+struct SnpRun {
+  k4_index* ix = nullptr;
+  hipStream_t st = nullptr;
+  SnpOpts o;
+  PileupWalk w;
+  SnpArgs& a = w.a;                    // of the sequence the walk handed out last
+  WigQueue wig;
+  K4DevBuf pref, pnon, cands, ncand, covb, covmax;
+  K4DevBuf cent_tab, mk_loci, mk_out;  // the run's centroid instance counts; a chunk of candidate loci and their markers
+  K4Scratch<K4DevBuf> tmp;             // of the prefix sums: sized for the longest sequence, once
+  std::vector<Cand> hc;                // the sequence's candidates, in locus order
+  std::vector<LociPV> pv;              // ... those still in the running
+  std::string text, di, tri, markers, centroids;
+  std::vector<Centroid> cent_rows;
+  uint64_t n_markers = 0, tot_snps = 0;  // m_MarkerID and the SNP ids: both run across sequences
+  char alts[100] = "", freq[100] = ""; // VCF: ALT and AF of the last SNP that had any (see snp_vcf_line)
+
+  int snp_open(k4_index* ix_, const K4Records& rec, const SnpOpts& o_, void* stream) {
+    ix = ix_;
+    o = o_;
+    if (rec.n_units < 0 || o.min_snp_reads < 1 || o.qvalue < 0.0 || o.nonref_pcnt < 0.0) return k4_fail(ix, K4_ERR_PARAMS, "SNP parameters out of range");
+    if (o.marker_len != 0 && (o.marker_len < 25 || o.marker_len > 500 || !(o.poly_thres >= 0.0 && o.poly_thres <= 0.5)))  // cMinMarkerLen .. cMaxMarkerLen
+      return k4_fail(ix, K4_ERR_PARAMS, "marker length must be 0 or 25..500 and the marker polymorphism threshold 0.0..0.5");
+    K4_TRY(w.open(ix, rec, stream));
+    st = w.st;
+    text = snp_header(o.vcf, ix->dataset);
+    di = hap_header(2);
+    tri = hap_header(3);
+    const size_t S = w.S;
+    K4_HIP(ix, pref.alloc((S + 1) * 8));
+    K4_HIP(ix, pnon.alloc((S + 1) * 8));
+    K4_HIP(ix, cands.alloc((size_t)kCandCap * sizeof(Cand)));
+    K4_HIP(ix, ncand.alloc(4));
+    if (o.want_centroids) {  // :8319-8332
+      cent_rows.assign(K4_CENT_BINS, Centroid{0, 0, 0, {0, 0, 0, 0, 0}});
+      K4_HIP(ix, cent_tab.alloc((size_t)K4_CENT_BINS * 8));
+      K4_HIP(ix, hipMemsetAsync(cent_tab.p, 0, (size_t)K4_CENT_BINS * 8, st));
+    }
+    if (o.marker_len) {
+      K4_HIP(ix, mk_loci.alloc((size_t)kMarkerChunk * 4));
+      K4_HIP(ix, mk_out.alloc((size_t)kMarkerChunk * ((size_t)o.marker_len + 8)));
+    }
+    return k4s_exclusive_scan(ix, (const uint32_t*)nullptr, pref.as<uint64_t>(), (uint64_t)0, S + 1, rocprim::plus<uint64_t>(), st, &tmp, true);
+  }
+  // SNP centroids, NumInsts of every locus of this sequence (independent of SNP calling, :7380-7398)
+  int snp_centroid_insts() {
+    const uint64_t tiles = ((uint64_t)a.clen + K4_CENT_THREADS * K4_CENT_LPT - 1) / (K4_CENT_THREADS * K4_CENT_LPT);
+    hipLaunchKernelGGL(k4k_snp_centroid_insts, dim3((unsigned)std::min<uint64_t>(tiles, 512)), dim3(K4_CENT_THREADS), 0, st, a, (int)o.min_snp_reads,
+                       cent_tab.as<unsigned long long>());
+    K4_HIP(ix, hipGetLastError());
+    return K4_OK;
+  }
+  // the sequence's coverage in the narrowest form, into the WIG queue: loci counted from 0, the tail left open until a candidate turns up
+  int snp_queue_wig(size_t* slot) {
+    const uint32_t* non = a.cnt + K4_SNP_STRIDE(a);
+    if (!covb.p) { K4_HIP(ix, covb.alloc(w.S * 4)); K4_HIP(ix, covmax.alloc(4)); }
+    K4_HIP(ix, hipMemsetAsync(covmax.p, 0, 4, st));
+    hipLaunchKernelGGL(k4k_snp_coverage_max, dim3(1024), dim3(256), 0, st, a.cnt, non, a.clen, covmax.as<uint32_t>());
+    K4_HIP(ix, hipGetLastError());
+    uint32_t mx = 0;
+    K4_TRY(k4s_read_back(ix, &mx, covmax.p, st));
+    const int width = mx < 256 ? 1 : mx < 65536 ? 2 : 4;
+    const dim3 cg((a.clen + 255) / 256);
+    if (width == 1) hipLaunchKernelGGL(k4k_snp_coverage<uint8_t>, cg, dim3(256), 0, st, a.cnt, non, a.clen, covb.as<uint8_t>());
+    else if (width == 2) hipLaunchKernelGGL(k4k_snp_coverage<uint16_t>, cg, dim3(256), 0, st, a.cnt, non, a.clen, covb.as<uint16_t>());
+    else hipLaunchKernelGGL(k4k_snp_coverage<uint32_t>, cg, dim3(256), 0, st, a.cnt, non, a.clen, covb.as<uint32_t>());
+    K4_HIP(ix, hipGetLastError());
+    return wig.add(ix, st, covb.p, width, a.clen, w.e->name, 0u, false, slot);
+  }
+  // the loci that pass the tests that need no error rate, in locus order: two prefix sums over [0, clen] (element l = sum of the loci
+  // below l; the arrays are zero behind clen), the candidate kernel, its list brought down
+  int snp_candidates() {
+    K4_HIP(ix, hipMemsetAsync(ncand.p, 0, 4, st));
+    K4_TRY(k4s_exclusive_scan(ix, a.cnt, pref.as<uint64_t>(), (uint64_t)0, (size_t)a.clen + 1, rocprim::plus<uint64_t>(), st, &tmp));
+    K4_TRY(k4s_exclusive_scan(ix, a.cnt + K4_SNP_STRIDE(a), pnon.as<uint64_t>(), (uint64_t)0, (size_t)a.clen + 1, rocprim::plus<uint64_t>(), st, &tmp));
+    hipLaunchKernelGGL(k4k_snp_candidates, dim3((a.clen + 255) / 256), dim3(256), 0, st, a, pref.as<uint64_t>(), pnon.as<uint64_t>(), (int)o.min_snp_reads,
+                       o.nonref_pcnt / 100.0 /* m_SNPNonRefPcnt, KAligner.cpp:256 */, cands.as<Cand>(), kCandCap, ncand.as<uint32_t>(), o.want_centroids ? 1 : 0);
+    K4_HIP(ix, hipGetLastError());
+    uint32_t nc = 0;
+    K4_TRY(k4s_read_back(ix, &nc, ncand.p, st));
+    if (nc > kCandCap) return k4_fail(ix, K4_ERR_MEM, "more than %u candidate SNP loci on %s", kCandCap, w.e->name);
+    hc.resize(nc);
+    if (nc) K4_HIP(ix, hipMemcpyAsync(hc.data(), cands.p, (size_t)nc * sizeof(Cand), hipMemcpyDeviceToHost, st));
+    K4_HIP(ix, hipStreamSynchronize(st));
+    std::sort(hc.begin(), hc.end(), [](const Cand& x, const Cand& y) { return x.loci < y.loci; });
+    return K4_OK;
+  }
+  // the marker gate (:7494-7560): in locus order, chunk by chunk; a candidate without a marker leaves pv here
+  int snp_marker_gate() {
+    const int marker_len = o.marker_len, m5 = marker_len / 2;
+    const size_t row = (size_t)marker_len;
+    std::vector<uint32_t> mk_l;
+    std::vector<uint8_t> mk_h;
+    size_t kept = 0;
+    char head[600];
+    for (size_t c0 = 0; c0 < pv.size(); c0 += kMarkerChunk) {
+      const uint32_t nq = (uint32_t)std::min<size_t>(kMarkerChunk, pv.size() - c0);
+      mk_l.resize(nq);
+      for (uint32_t k = 0; k < nq; k++) mk_l[k] = pv[c0 + k].loci;
+      uint32_t* d_hdr = mk_out.as<uint32_t>();
+      uint8_t* d_seq = mk_out.as<uint8_t>() + (size_t)nq * 8;
+      K4_HIP(ix, hipMemcpyAsync(mk_loci.p, mk_l.data(), (size_t)nq * 4, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k4k_snp_markers, dim3((nq + 3) / 4), dim3(256), 0, st, w.a, mk_loci.as<uint32_t>(), nq, marker_len, (int)o.min_snp_reads,
+                         o.poly_thres, d_hdr, d_seq);
+      K4_HIP(ix, hipGetLastError());
+      mk_h.resize((size_t)nq * (row + 8));
+      K4_HIP(ix, hipMemcpyAsync(mk_h.data(), mk_out.p, mk_h.size(), hipMemcpyDeviceToHost, st));
+      K4_HIP(ix, hipStreamSynchronize(st));
+      for (uint32_t k = 0; k < nq; k++) {
+        uint32_t h2[2];
+        memcpy(h2, &mk_h[(size_t)k * 8], 8);
+        if (!h2[0]) continue;
+        LociPV p = pv[c0 + k];
+        const uint8_t* sq = &mk_h[(size_t)nq * 8 + (size_t)k * row];
+        p.marker_id = (uint32_t)++n_markers;
+        p.n_poly = h2[1];
+        // >MarkerNNN Chrom StartLoci|MarkerLen|SNPLoci|Marker5Len|SNPbase|RefBase|NumPolymorphicSites (:7552)
+        const int hn = snprintf(head, sizeof(head), ">Marker%d %s %d|%d|%d|%d|%c|%c|%d\n", (int)p.marker_id, w.e->name, (int)p.loci - m5, marker_len, (int)p.loci,
+                                m5, (char)sq[m5], "ACGTN"[p.ref_base], (int)p.n_poly);
+        markers.append(head, (size_t)std::min<int>(hn, (int)sizeof(head) - 1));
+        markers.append((const char*)sq, row);
+        markers += '\n';
+        pv[kept++] = p;  // (kept <= c0 + k: nothing is overwritten before it is read)
+      }
+    }
+    pv.resize(kept);
+    return K4_OK;
+  }
+  // DiSNPs / TriSNPs of this sequence (:7767-8101) over its called loci pv: the slots on the host, the counters from the device
+  int snp_haplotypes() {
+    const size_t n_acc = pv.size();
+    const char* chrom = w.e->name;
+    const int mean_len = (int)(uint32_t)((w.t[3] + w.t[2] - 1) / w.t[2]);
+    const int max_sep = std::min(300, mean_len);  // m_MaxDiSNPSep = min(cDfltMaxDiSNPSep, MeanReadLen), :7346
+    std::vector<uint32_t> loci(n_acc);
+    std::vector<int32_t> slot(2 * n_acc, -1);  // [0, n_acc): pair ending at k, [n_acc, 2 n_acc): triple ending at k
+    uint32_t n_di = 0, n_tri = 0;
+    for (size_t k = 0; k < n_acc; k++) {
+      loci[k] = pv[k].loci;
+      const int cur = (int)pv[k].loci;
+      if (k >= 1 && cur > 0 && cur - (int)pv[k - 1].loci <= max_sep) slot[k] = (int32_t)n_di++;
+      if (k >= 2 && pv[k - 1].loci > 0 && cur > 0 && cur - (int)pv[k - 2].loci <= max_sep) slot[n_acc + k] = (int32_t)n_tri++;
+    }
+    if (!n_di) return K4_OK;  // (a triple holds two pairs: no pair, no triple)
+    K4DevBuf dl, ds, dd, dt;
+    K4_HIP(ix, dl.alloc(n_acc * 4));
+    K4_HIP(ix, ds.alloc(2 * n_acc * 4));
+    K4_HIP(ix, dd.alloc((size_t)n_di * 17 * 4));
+    K4_HIP(ix, dt.alloc((size_t)n_tri * 65 * 4));
+    K4_HIP(ix, hipMemcpyAsync(dl.p, loci.data(), n_acc * 4, hipMemcpyHostToDevice, st));
+    K4_HIP(ix, hipMemcpyAsync(ds.p, slot.data(), 2 * n_acc * 4, hipMemcpyHostToDevice, st));
+    K4_HIP(ix, hipMemsetAsync(dd.p, 0, (size_t)n_di * 17 * 4, st));
+    if (n_tri) K4_HIP(ix, hipMemsetAsync(dt.p, 0, (size_t)n_tri * 65 * 4, st));
+    HapArgs hp;
+    hp.loci = dl.as<uint32_t>(); hp.di_slot = ds.as<int32_t>(); hp.tri_slot = ds.as<int32_t>() + n_acc; hp.n_loci = (uint32_t)n_acc;
+    hp.di = dd.as<uint32_t>(); hp.tri = dt.as<uint32_t>();
+    const int64_t nb = std::min<int64_t>((w.a.rs.n_reads + 255) / 256, 8192);
+    hipLaunchKernelGGL(k4k_snp_haplotypes, dim3((unsigned)nb), dim3(256), 0, st, w.a, hp);
+    K4_HIP(ix, hipGetLastError());
+    std::vector<uint32_t> hd((size_t)n_di * 17), ht((size_t)n_tri * 65);
+    K4_HIP(ix, hipMemcpyAsync(hd.data(), dd.p, hd.size() * 4, hipMemcpyDeviceToHost, st));
+    if (n_tri) K4_HIP(ix, hipMemcpyAsync(ht.data(), dt.p, ht.size() * 4, hipMemcpyDeviceToHost, st));
+    K4_HIP(ix, hipStreamSynchronize(st));
+    int tot_di = 0, tot_tri = 0;  // (the ids restart with every chromosome, :7634-7635)
+    for (size_t k = 1; k < n_acc; k++) {
+      if (slot[k] >= 0) {
+        const uint32_t l2[2] = {pv[k - 1].loci, pv[k].loci}, r2[2] = {pv[k - 1].ref_base, pv[k].ref_base};
+        if (hap_line(di, "DiSNPs", tot_di + 1, ix->dataset, chrom, l2, r2, 2, &hd[(size_t)slot[k] * 17], o.min_snp_reads)) tot_di++;
+      }
+      if (k >= 2 && slot[n_acc + k] >= 0) {
+        const uint32_t l3[3] = {pv[k - 2].loci, pv[k - 1].loci, pv[k].loci}, r3[3] = {pv[k - 2].ref_base, pv[k - 1].ref_base, pv[k].ref_base};
+        if (hap_line(tri, "TriSNPs", tot_tri + 1, ix->dataset, chrom, l3, r3, 3, &ht[(size_t)slot[n_acc + k] * 65], o.min_snp_reads)) tot_tri++;
+      }
+    }
+    return K4_OK;
+  }
+  // the sequence's called SNPs into the SNP file and the centroid tallies
+  void snp_emit() {
+    for (const LociPV& p : pv) {
+      tot_snps++;
+      if (o.want_centroids && p.cent != K4_CENT_NONE) {  // the called SNP's counts as piled, for the 7-mer around it (:8104-8133)
+        Centroid& c = cent_rows[p.cent];
+        c.n_snps++;
+        c.ref_cnt += p.num_reads - p.num_subs;
+        for (int b = 0; b < 5; b++) c.by_base[b] += p.by_base[b];
+      }
+      if (o.vcf) snp_vcf_line(&text, w.e->name, p, tot_snps, alts, freq);
+      else snp_csv_line(&text, ix->dataset, w.e->name, p, tot_snps, pv.size());
+    }
+  }
+  // OutputSNPs for the sequence the walk has just piled up (:7320-7640)
+  int snp_sequence() {
+    if (o.want_centroids) K4_TRY(snp_centroid_insts());
+    size_t wig_slot = 0;
+    if (o.want_wig) K4_TRY(snp_queue_wig(&wig_slot));  // (its walk runs on a thread of its own from here on)
+    K4_TRY(snp_candidates());
+    snp_noise_gate(hc, w.t, &pv);
+    if (o.marker_len && !pv.empty()) K4_TRY(snp_marker_gate());  // (before the p-values: every file of the run changes with -K)
+    for (LociPV& p : pv) p.pvalue = 1.0 - binomial((int)p.num_reads, (int)p.num_subs, p.bkgnd);
+    // decided before the cut: a chromosome without a candidate never closes its last span, one whose candidates all fall to the cut does
+    if (o.want_wig && !pv.empty()) wig.jobs[wig_slot].close_tail = true;
+    if (pv.empty()) return K4_OK;
+    snp_bh_cut(&pv, o.qvalue);
+    if (o.want_hap && pv.size() >= 2) K4_TRY(snp_haplotypes());
+    snp_emit();
+    return K4_OK;
+  }
+  // the centroid instance counts down, the file's text
+  int snp_centroid_file() {
+    std::vector<unsigned long long> insts(K4_CENT_BINS);
+    K4_HIP(ix, hipMemcpyAsync(insts.data(), cent_tab.p, (size_t)K4_CENT_BINS * 8, hipMemcpyDeviceToHost, st));
+    K4_HIP(ix, hipStreamSynchronize(st));
+    centroids = snp_centroid_text(insts, cent_rows);
+    return K4_OK;
+  }
+};
+
+// a whole run into `out`: every member the options ask for, the others null.  Every entry point comes through here; on an error
+// the guard leaves `out` zeroed and nothing handed out.
+static int snp_files(k4_index* ix, const K4Records& rec, const SnpOpts& o, k4_snp_files2* out, void* stream) {
+  K4HandOut hand(out);
+  if (!ix) return K4_ERR_PARAMS;
+  SnpRun r;
+  K4_TRY(r.snp_open(ix, rec, o, stream));
+  for (bool got = false;;) {  // the sorted reads: one chromosome after the other
+    K4_TRY(r.w.next(&got));
+    if (!got) break;
+    K4_TRY(r.snp_sequence());
+  }
+  if (o.want_centroids) K4_TRY(r.snp_centroid_file());
+  k4_snp_files& f = out->files;
+  if (o.want_wig)  // :8235
+    K4_TRY(r.wig.finish(ix, "track type=wiggle_0 name=\"Coverage\" description=\"Alignment Segment Coverage\" useScore=1\n", hand, &f.wig, &f.wig_bytes));
+  K4_TRY(hand.give(ix, &f.snp, &f.snp_bytes, r.text));
+  if (o.want_hap) {
+    K4_TRY(hand.give(ix, &f.disnp, &f.disnp_bytes, r.di));
+    K4_TRY(hand.give(ix, &f.trisnp, &f.trisnp_bytes, r.tri));
+  }
+  if (o.marker_len) K4_TRY(hand.give(ix, &out->markers, &out->markers_bytes, r.markers));
+  if (o.want_centroids) K4_TRY(hand.give(ix, &out->centroids, &out->centroids_bytes, r.centroids));
+  f.n_snps = r.tot_snps;
+  out->n_markers = r.n_markers;
+  return hand.ok();
+}
 
 }  // namespace
 
-static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
-                        const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
-                        double qvalue, double snp_nonref_pcnt, char** csv, uint64_t* csv_bytes, uint64_t* n_snps, void* stream,
-                        char** wig = nullptr, uint64_t* wig_bytes = nullptr, std::string* di_text = nullptr, std::string* tri_text = nullptr,
-                        SnpExtra* extra = nullptr);
+// the SNP file alone or with the WIG, into the caller's pointers: what k4_snp_csv_dev, k4_snp_vcf_dev and k4_snp_files_dev hand out
+static int snp_text(k4_index* ix, const K4Records& rec, const SnpOpts& o, char** snp, uint64_t* snp_bytes, uint64_t* n_snps, char** wig, uint64_t* wig_bytes,
+                    void* stream) {
+  if (!snp || !snp_bytes || (o.want_wig && (!wig || !wig_bytes))) return K4_ERR_PARAMS;
+  k4_snp_files2 f;
+  const int rc = snp_files(ix, rec, o, &f, stream);  // (an error leaves f zeroed)
+  *snp = f.files.snp; *snp_bytes = f.files.snp_bytes;
+  if (n_snps) *n_snps = f.files.n_snps;
+  if (o.want_wig) { *wig = f.files.wig; *wig_bytes = f.files.wig_bytes; }
+  return rc;
+}
+extern "C" int k4_snp_csv_dev(k4_index* ix, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
+                              const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
+                              double qvalue, double snp_nonref_pcnt, char** csv, uint64_t* csv_bytes, uint64_t* n_snps, void* stream) {
+  return snp_text(ix, K4Records{pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens}, SnpOpts{0, min_snp_reads, qvalue, snp_nonref_pcnt, false, false},
+                  csv, csv_bytes, n_snps, nullptr, nullptr, stream);
+}
+// the VCF form (kalign: a SNP file name ending in .vcf, KAligner.cpp:186-187; header :8196-8199, records :7650-7696)
+extern "C" int k4_snp_vcf_dev(k4_index* ix, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
+                              const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
+                              double qvalue, double snp_nonref_pcnt, char** vcf, uint64_t* vcf_bytes, uint64_t* n_snps, void* stream) {
+  return snp_text(ix, K4Records{pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens}, SnpOpts{1, min_snp_reads, qvalue, snp_nonref_pcnt, false, false},
+                  vcf, vcf_bytes, n_snps, nullptr, nullptr, stream);
+}
 // both files of a kalign SNP run: the SNP file (CSV, or VCF when vcf != 0) and the coverage WIG (<snp file>.covsegs.wig)
 extern "C" int k4_snp_files_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
                                 const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
                                 double qvalue, double snp_nonref_pcnt, char** snp, uint64_t* snp_bytes, uint64_t* n_snps, char** wig,
                                 uint64_t* wig_bytes, void* stream) {
-  if (!wig || !wig_bytes) return K4_ERR_PARAMS;
-  return snp_text_dev(ix, vcf, pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens, min_snp_reads, qvalue, snp_nonref_pcnt, snp, snp_bytes,
-                      n_snps, stream, wig, wig_bytes);
+  return snp_text(ix, K4Records{pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens}, SnpOpts{vcf, min_snp_reads, qvalue, snp_nonref_pcnt, true, false},
+                  snp, snp_bytes, n_snps, wig, wig_bytes, stream);
 }
 // every file of a kalign SNP run: the SNP file, the coverage WIG and the two haplotype files (.disnp.csv, .trisnp.csv)
-static int snp_run(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml, const void* d_pe,
-                   const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads, double qvalue, double snp_nonref_pcnt,
-                   k4_snp_files* out, void* stream, SnpExtra* extra) {
-  if (!out) return K4_ERR_PARAMS;
-  memset(out, 0, sizeof(*out));
-  std::string di = hap_header(2), tri = hap_header(3);
-  int rc = snp_text_dev(ix, vcf, pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens, min_snp_reads, qvalue, snp_nonref_pcnt, &out->snp,
-                        &out->snp_bytes, &out->n_snps, stream, &out->wig, &out->wig_bytes, &di, &tri, extra);
-  if (rc == K4_OK) {
-    out->disnp = (char*)malloc(di.size() + 1);
-    out->trisnp = (char*)malloc(tri.size() + 1);
-    if (!out->disnp || !out->trisnp) rc = k4_fail(ix, K4_ERR_MEM, "out of memory");
-    else {
-      memcpy(out->disnp, di.c_str(), di.size() + 1); out->disnp_bytes = di.size();
-      memcpy(out->trisnp, tri.c_str(), tri.size() + 1); out->trisnp_bytes = tri.size();
-    }
-  }
-  if (rc != K4_OK) {
-    free(out->snp); free(out->wig); free(out->disnp); free(out->trisnp);
-    memset(out, 0, sizeof(*out));
-  }
-  return rc;
-}
 extern "C" int k4_snp_run_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
                               const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
                               double qvalue, double snp_nonref_pcnt, k4_snp_files* out, void* stream) {
-  return snp_run(ix, vcf, pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens, min_snp_reads, qvalue, snp_nonref_pcnt, out, stream, nullptr);
+  if (!out) return K4_ERR_PARAMS;
+  k4_snp_files2 f;
+  const int rc = snp_files(ix, K4Records{pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens},
+                           SnpOpts{vcf, min_snp_reads, qvalue, snp_nonref_pcnt, true, true}, &f, stream);
+  *out = f.files;  // (an error leaves f zeroed)
+  return rc;
 }
 // ... and, as the options ask, the marker sequences (<snp file>.markers) and the SNP centroid distribution
 extern "C" int k4_snp_run2_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
                                const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
                                double qvalue, double snp_nonref_pcnt, const k4_snp_opts* opts, k4_snp_files2* out, void* stream) {
   if (!out || !opts) return K4_ERR_PARAMS;
-  memset(out, 0, sizeof(*out));
-  SnpExtra ex;
-  ex.marker_len = opts->marker_len; ex.poly_thres = opts->marker_poly_thres; ex.want_centroids = opts->want_centroids != 0;
-  int rc = snp_run(ix, vcf, pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens, min_snp_reads, qvalue, snp_nonref_pcnt, &out->files, stream, &ex);
-  if (rc != K4_OK) return rc;
-  auto keep = [](const std::string& s, char** p, uint64_t* n) {
-    *p = (char*)malloc(s.size() + 1);
-    if (!*p) return false;
-    memcpy(*p, s.c_str(), s.size() + 1);
-    *n = s.size();
-    return true;
-  };
-  bool ok = true;
-  if (ex.marker_len) ok = keep(ex.markers, &out->markers, &out->markers_bytes);
-  if (ok && ex.want_centroids) ok = keep(ex.centroids, &out->centroids, &out->centroids_bytes);
-  out->n_markers = ex.n_markers;
-  if (!ok) {
-    free(out->files.snp); free(out->files.wig); free(out->files.disnp); free(out->files.trisnp); free(out->markers); free(out->centroids);
-    memset(out, 0, sizeof(*out));
-    return k4_fail(ix, K4_ERR_MEM, "out of memory");
-  }
-  return K4_OK;
+  return snp_files(ix, K4Records{pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens},
+                   SnpOpts{vcf, min_snp_reads, qvalue, snp_nonref_pcnt, true, true, opts->marker_len, opts->marker_poly_thres, opts->want_centroids != 0}, out, stream);
 }
 // the marker rule alone, on the host: no device, no index.  cnt7: seven arrays of `stride` words each (ref, nonref, A, C, G, T, N);
 // base[l] = 0..4, or 0xff (coverage below min_snp_reads) / 0xfe (no allele reaches 1 - threshold); poly[l] = 1 for a polymorphic locus
@@ -420,346 +745,6 @@ extern "C" int k4_marker_classify_host(const uint32_t* cnt7, uint64_t stride, ui
     base[l] = b == K4_MARKER_NO_COVERAGE ? 0xff : b == K4_MARKER_NO_ALLELE ? 0xfe : (uint8_t)b;
     poly[l] = (uint8_t)p;
   }
-  return K4_OK;
-}
-extern "C" int k4_snp_csv_dev(k4_index* ix, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
-                              const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
-                              double qvalue, double snp_nonref_pcnt, char** csv, uint64_t* csv_bytes, uint64_t* n_snps, void* stream) {
-  return snp_text_dev(ix, 0, pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens, min_snp_reads, qvalue, snp_nonref_pcnt, csv, csv_bytes,
-                      n_snps, stream);
-}
-// the VCF form (kalign: a SNP file name ending in .vcf, KAligner.cpp:186-187; header :8196-8199, records :7650-7696)
-extern "C" int k4_snp_vcf_dev(k4_index* ix, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
-                              const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
-                              double qvalue, double snp_nonref_pcnt, char** vcf, uint64_t* vcf_bytes, uint64_t* n_snps, void* stream) {
-  return snp_text_dev(ix, 1, pe, n_units, d_rr, d_hits, max_ml, d_pe, d_reads, d_offs, d_lens, min_snp_reads, qvalue, snp_nonref_pcnt, vcf, vcf_bytes,
-                      n_snps, stream);
-}
-static int snp_text_dev(k4_index* ix, int vcf, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
-                        const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens, int32_t min_snp_reads,
-                        double qvalue, double snp_nonref_pcnt, char** csv, uint64_t* csv_bytes, uint64_t* n_snps, void* stream,
-                        char** wig, uint64_t* wig_bytes, std::string* di_text, std::string* tri_text, SnpExtra* extra) {
-  if (!ix || !csv || !csv_bytes) return K4_ERR_PARAMS;
-  const int marker_len = extra ? extra->marker_len : 0;
-  const bool want_cent = extra && extra->want_centroids;
-  *csv = nullptr;
-  *csv_bytes = 0;
-  if (wig) { *wig = nullptr; *wig_bytes = 0; }
-  struct WigJob { std::future<WigOut> f; bool close_tail; };
-  std::vector<WigJob> wig_jobs;  // one per chromosome with alignments, in chromosome order
-  K4DevBuf covb, covmax;
-  if (n_snps) *n_snps = 0;
-  if (n_units < 0 || min_snp_reads < 1 || qvalue < 0.0 || snp_nonref_pcnt < 0.0) return k4_fail(ix, K4_ERR_PARAMS, "SNP parameters out of range");
-  if (marker_len != 0 && (marker_len < 25 || marker_len > 500 || !(extra->poly_thres >= 0.0 && extra->poly_thres <= 0.5)))  // cMinMarkerLen .. cMaxMarkerLen
-    return k4_fail(ix, K4_ERR_PARAMS, "marker length must be 0 or 25..500 and the marker polymorphism threshold 0.0..0.5");
-  SnpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.ix = ix->d;
-  K4_TRY(k4s_read_set(ix, pe, n_units, d_rr, d_hits, max_ml, d_pe, nullptr, d_reads, d_offs, d_lens, K4RS_HITS | K4RS_READS | K4RS_UNITS, &a.rs));
-  K4_HIP(ix, hipSetDevice(ix->device));
-  hipStream_t st = (hipStream_t)stream;
-  std::string text =
-      "\"SNP_ID\",\"ElType\",\"Species\",\"Chrom\",\"StartLoci\",\"EndLoci\",\"Len\",\"Strand\",\"Rank\",\"PValue\",\"Bases\",\"Mismatches\",\"RefBase\","
-      "\"MMBaseA\",\"MMBaseC\",\"MMBaseG\",\"MMBaseT\",\"MMBaseN\",\"BackgroundSubRate\",\"TotWinBases\",\"TotWinMismatches\",\"MarkerID\",\"NumPolymorphicSites\"\n";
-  if (vcf)
-    text = "##fileformat=VCFv4.1\n##source=k4align1.0\n##reference=" + ix->dataset +
-           "\n##INFO=<ID=AF,Number=A,Type=Float,Description=\"Allele Frequency\">\n##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Read Depth\">\n"
-           "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
-  uint32_t max_len = 0;
-  for (const k4_entry& e : ix->entries) max_len = std::max(max_len, e.seq_len);
-  const size_t S = (size_t)max_len + 16;
-  K4DevBuf cnt, tot, pref, pnon, cands, ncand;
-  K4Scratch<K4DevBuf> tmp;  // of the prefix sums: sized for the longest sequence, once
-  const uint32_t cap = 1u << 22;  // candidate loci per chromosome kept on the device (more: the call fails loudly)
-  K4_HIP(ix, cnt.alloc(7 * S * 4));
-  K4_HIP(ix, tot.alloc(4 * 8));
-  K4_HIP(ix, pref.alloc((S + 1) * 8));
-  K4_HIP(ix, pnon.alloc((S + 1) * 8));
-  K4_HIP(ix, cands.alloc((size_t)cap * sizeof(Cand)));
-  K4_HIP(ix, ncand.alloc(4));
-  K4DevBuf cent_tab, mk_loci, mk_out;  // the run's centroid instance counts; a chunk of candidate loci and their markers
-  std::vector<Centroid> cent_rows;
-  if (want_cent) {  // :8319-8332
-    cent_rows.assign(K4_CENT_BINS, Centroid{0, 0, 0, {0, 0, 0, 0, 0}});
-    K4_HIP(ix, cent_tab.alloc((size_t)K4_CENT_BINS * 8));
-    K4_HIP(ix, hipMemsetAsync(cent_tab.p, 0, (size_t)K4_CENT_BINS * 8, st));
-  }
-  if (marker_len) {
-    K4_HIP(ix, mk_loci.alloc((size_t)kMarkerChunk * 4));
-    K4_HIP(ix, mk_out.alloc((size_t)kMarkerChunk * ((size_t)marker_len + 8)));
-  }
-  std::vector<uint32_t> mk_l;
-  std::vector<uint8_t> mk_h;
-  K4_TRY(k4s_exclusive_scan(ix, cnt.as<uint32_t>(), pref.as<uint64_t>(), (uint64_t)0, S + 1, rocprim::plus<uint64_t>(), st, &tmp, true));
-  uint64_t tot_snps = 0;
-  const double nonref_frac = snp_nonref_pcnt / 100.0;  // m_SNPNonRefPcnt, KAligner.cpp:256
-  std::vector<Cand> hc;
-  std::vector<LociPV> pv;
-  char alts[100] = "", freq[100] = "";  // VCF: ALT and AF of the last SNP that had any (see below)
-  std::vector<uint8_t> chrom_hit((size_t)ix->d.n_entries + 1, 0);
-  std::vector<uint64_t> ent_start_h((size_t)ix->d.n_entries, 0);
-  if (a.rs.n_reads > 0 && ix->d.n_entries) {
-    K4DevBuf flags;
-    K4_HIP(ix, flags.alloc(chrom_hit.size()));
-    K4_HIP(ix, hipMemsetAsync(flags.p, 0, chrom_hit.size(), st));
-    hipLaunchKernelGGL(k4k_snp_mark, dim3((unsigned)std::min<int64_t>((a.rs.n_reads + 255) / 256, 2048)), dim3(256), 0, st, a, flags.as<uint8_t>(), ix->d.n_entries);
-    K4_HIP(ix, hipMemcpyAsync(chrom_hit.data(), flags.p, chrom_hit.size(), hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipMemcpyAsync(ent_start_h.data(), ix->ent_start.p, ent_start_h.size() * 8, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
-  }
-  for (uint32_t chrom = 1; chrom <= ix->d.n_entries && a.rs.n_reads > 0; chrom++) {  // the sorted reads: one chromosome after the other
-    if (!chrom_hit[chrom]) continue;  // (nothing the pile-up would take: no device work, no synchronisation for it)
-    const k4_entry& e = ix->entries[chrom - 1];
-    a.chrom_id = chrom; a.clen = e.seq_len; a.cnt = cnt.as<uint32_t>(); a.tot = tot.as<unsigned long long>();
-    a.cs = ent_start_h[chrom - 1];
-    const size_t Sc = K4_SNP_STRIDE(a);
-    K4_HIP(ix, hipMemsetAsync(cnt.p, 0, 7 * Sc * 4, st));
-    K4_HIP(ix, hipMemsetAsync(tot.p, 0, 32, st));
-    K4_HIP(ix, hipMemsetAsync(ncand.p, 0, 4, st));
-    hipLaunchKernelGGL(k4k_snp_pileup, dim3(2048), dim3(256), 0, st, a);
-    unsigned long long t3[4] = {0, 0, 0, 0};
-    K4_TRY(k4s_read_back(ix, &t3, tot.p, st));
-    if (t3[2] == 0) continue;  // no alignment on this chromosome
-    if (want_cent) {  // NumInsts of every locus of this chromosome (independent of SNP calling, :7380-7398)
-      const uint64_t tiles = ((uint64_t)a.clen + K4_CENT_THREADS * K4_CENT_LPT - 1) / (K4_CENT_THREADS * K4_CENT_LPT);
-      hipLaunchKernelGGL(k4k_snp_centroid_insts, dim3((unsigned)std::min<uint64_t>(tiles, 512)), dim3(K4_CENT_THREADS), 0, st, a, (int)min_snp_reads,
-                         cent_tab.as<unsigned long long>());
-      K4_HIP(ix, hipGetLastError());
-    }
-    size_t wig_slot = 0;
-    if (wig) {  // coverage down to the host, its walk on a thread of its own (at most twelve chromosomes in flight)
-      if (!covb.p) { K4_HIP(ix, covb.alloc(S * 4)); K4_HIP(ix, covmax.alloc(4)); }
-      K4_HIP(ix, hipMemsetAsync(covmax.p, 0, 4, st));
-      hipLaunchKernelGGL(k4k_snp_coverage_max, dim3(1024), dim3(256), 0, st, a.cnt, a.cnt + K4_SNP_STRIDE(a), a.clen, covmax.as<uint32_t>());
-      uint32_t mx = 0;
-      K4_TRY(k4s_read_back(ix, &mx, covmax.p, st));
-      const int width = mx < 256 ? 1 : mx < 65536 ? 2 : 4;
-      const dim3 cg((a.clen + 255) / 256);
-      if (width == 1) hipLaunchKernelGGL(k4k_snp_coverage<uint8_t>, cg, dim3(256), 0, st, a.cnt, a.cnt + K4_SNP_STRIDE(a), a.clen, covb.as<uint8_t>());
-      else if (width == 2) hipLaunchKernelGGL(k4k_snp_coverage<uint16_t>, cg, dim3(256), 0, st, a.cnt, a.cnt + K4_SNP_STRIDE(a), a.clen, covb.as<uint16_t>());
-      else hipLaunchKernelGGL(k4k_snp_coverage<uint32_t>, cg, dim3(256), 0, st, a.cnt, a.cnt + K4_SNP_STRIDE(a), a.clen, covb.as<uint32_t>());
-      std::unique_ptr<uint8_t[]> cov(new uint8_t[((size_t)a.clen + 1) * (size_t)width]);
-      K4_HIP(ix, hipMemcpyAsync(cov.get(), covb.p, (size_t)a.clen * (size_t)width, hipMemcpyDeviceToHost, st));
-      K4_HIP(ix, hipStreamSynchronize(st));
-      if (wig_jobs.size() >= 12) wig_jobs[wig_jobs.size() - 12].f.wait();
-      wig_slot = wig_jobs.size();
-      wig_jobs.push_back({std::async(std::launch::async, wig_chromosome, std::move(cov), width, a.clen, std::string(e.name), 0u), false});
-    }
-    // prefix sums over [0, clen]: element l = sum of the loci below l (the arrays are zero behind clen)
-    K4_TRY(k4s_exclusive_scan(ix, a.cnt, pref.as<uint64_t>(), (uint64_t)0, (size_t)a.clen + 1, rocprim::plus<uint64_t>(), st, &tmp));
-    K4_TRY(k4s_exclusive_scan(ix, a.cnt + Sc, pnon.as<uint64_t>(), (uint64_t)0, (size_t)a.clen + 1, rocprim::plus<uint64_t>(), st, &tmp));
-    hipLaunchKernelGGL(k4k_snp_candidates, dim3((a.clen + 255) / 256), dim3(256), 0, st, a, pref.as<uint64_t>(), pnon.as<uint64_t>(), (int)min_snp_reads,
-                       nonref_frac, cands.as<Cand>(), cap, ncand.as<uint32_t>(), want_cent ? 1 : 0);
-    uint32_t nc = 0;
-    K4_TRY(k4s_read_back(ix, &nc, ncand.p, st));
-    if (nc > cap) return k4_fail(ix, K4_ERR_MEM, "more than %u candidate SNP loci on %s", cap, e.name);
-    hc.resize(nc);
-    if (nc) K4_HIP(ix, hipMemcpy(hc.data(), cands.p, (size_t)nc * sizeof(Cand), hipMemcpyDeviceToHost));
-    std::sort(hc.begin(), hc.end(), [](const Cand& x, const Cand& y) { return x.loci < y.loci; });
-    // ---- OutputSNPs from here on (:7320, :7425-7450, :7567-7640) -------------------------------------------------------------
-    double global_rate = (double)t3[1] / (double)(1 + t3[0] + t3[1]);
-    global_rate = std::max(0.005, global_rate);  // cMinSeqErrRate
-    pv.clear();
-    for (const Cand& c : hc) {
-      const uint32_t ltmm = c.n_nonref <= c.loc_mm ? c.loc_mm - c.n_nonref : 0;
-      const uint32_t ltm = c.n_ref < c.loc_m ? c.loc_m - c.n_ref : 0;
-      double local_rate;
-      if ((ltmm + ltm) == 0) local_rate = global_rate;
-      else {
-        local_rate = (double)ltmm / (double)(ltmm + ltm);
-        if (local_rate < global_rate) local_rate = global_rate;
-      }
-      if (local_rate > 0.20) continue;  // cMaxBkgdNoiseThres
-      LociPV p;
-      const int tot_bases = (int)(c.n_ref + c.n_nonref);
-      p.pvalue = 0.0; p.cent = c.cent; p.marker_id = 0; p.n_poly = 0;
-      p.loci = c.loci; p.rank = 0; p.bkgnd = local_rate; p.local_reads = ltmm + ltm; p.local_subs = ltmm;
-      p.num_reads = (uint32_t)tot_bases; p.num_subs = c.n_nonref;
-      for (int b = 0; b < 5; b++) p.by_base[b] = c.by_base[b];
-      p.ref_base = c.ref_base > 4 ? 4 : c.ref_base;
-      pv.push_back(p);
-    }
-    if (marker_len && !pv.empty()) {  // the marker gate (:7494-7560): in locus order, chunk by chunk; a candidate without a marker leaves here
-      const size_t row = (size_t)marker_len;
-      size_t kept = 0;
-      char head[600];
-      for (size_t c0 = 0; c0 < pv.size(); c0 += kMarkerChunk) {
-        const uint32_t nq = (uint32_t)std::min<size_t>(kMarkerChunk, pv.size() - c0);
-        mk_l.resize(nq);
-        for (uint32_t k = 0; k < nq; k++) mk_l[k] = pv[c0 + k].loci;
-        uint32_t* d_hdr = mk_out.as<uint32_t>();
-        uint8_t* d_seq = mk_out.as<uint8_t>() + (size_t)nq * 8;
-        K4_HIP(ix, hipMemcpyAsync(mk_loci.p, mk_l.data(), (size_t)nq * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k4k_snp_markers, dim3((nq + 3) / 4), dim3(256), 0, st, a, mk_loci.as<uint32_t>(), nq, marker_len, (int)min_snp_reads,
-                           extra->poly_thres, d_hdr, d_seq);
-        K4_HIP(ix, hipGetLastError());
-        mk_h.resize((size_t)nq * (row + 8));
-        K4_HIP(ix, hipMemcpyAsync(mk_h.data(), mk_out.p, mk_h.size(), hipMemcpyDeviceToHost, st));
-        K4_HIP(ix, hipStreamSynchronize(st));
-        for (uint32_t k = 0; k < nq; k++) {
-          uint32_t h2[2];
-          memcpy(h2, &mk_h[(size_t)k * 8], 8);
-          if (!h2[0]) continue;
-          LociPV p = pv[c0 + k];
-          const uint8_t* sq = &mk_h[(size_t)nq * 8 + (size_t)k * row];
-          const int m5 = marker_len / 2;
-          p.marker_id = (uint32_t)++extra->n_markers;
-          p.n_poly = h2[1];
-          // >MarkerNNN Chrom StartLoci|MarkerLen|SNPLoci|Marker5Len|SNPbase|RefBase|NumPolymorphicSites (:7552)
-          const int hn = snprintf(head, sizeof(head), ">Marker%d %s %d|%d|%d|%d|%c|%c|%d\n", (int)p.marker_id, e.name, (int)p.loci - m5, marker_len, (int)p.loci,
-                                  m5, (char)sq[m5], "ACGTN"[p.ref_base], (int)p.n_poly);
-          extra->markers.append(head, (size_t)std::min<int>(hn, (int)sizeof(head) - 1));
-          extra->markers.append((const char*)sq, row);
-          extra->markers += '\n';
-          pv[kept++] = p;  // (kept <= c0 + k: nothing is overwritten before it is read)
-        }
-      }
-      pv.resize(kept);
-    }
-    for (LociPV& p : pv) p.pvalue = 1.0 - binomial((int)p.num_reads, (int)p.num_subs, p.bkgnd);
-    if (wig && !pv.empty()) wig_jobs[wig_slot].close_tail = true;  // (a chromosome without a candidate never closes its last span)
-    if (pv.empty()) continue;
-    std::stable_sort(pv.begin(), pv.end(), [](const LociPV& x, const LociPV& y) { return x.pvalue < y.pvalue; });
-    size_t n_acc = 0;
-    for (size_t k = 0; k < pv.size(); k++) {  // Benjamini-Hochberg
-      const double adj = ((k + 1) / (double)pv.size()) * qvalue;
-      if (pv[k].pvalue >= adj) break;
-      pv[k].rank = (uint32_t)(k + 1);
-      n_acc++;
-    }
-    pv.resize(n_acc);
-    std::sort(pv.begin(), pv.end(), [](const LociPV& x, const LociPV& y) { return x.loci < y.loci; });
-    if ((di_text || tri_text) && n_acc >= 2) {  // ---- DiSNPs / TriSNPs of this chromosome (:7767-8101) ------------------------------
-      const int mean_len = (int)(uint32_t)((t3[3] + t3[2] - 1) / t3[2]);
-      const int max_sep = std::min(300, mean_len);  // m_MaxDiSNPSep = min(cDfltMaxDiSNPSep, MeanReadLen), :7346
-      std::vector<uint32_t> loci(n_acc);
-      std::vector<int32_t> slot(2 * n_acc, -1);  // [0, n_acc): pair ending at k, [n_acc, 2 n_acc): triple ending at k
-      uint32_t n_di = 0, n_tri = 0;
-      for (size_t k = 0; k < n_acc; k++) {
-        loci[k] = pv[k].loci;
-        const int cur = (int)pv[k].loci;
-        if (k >= 1 && cur > 0 && cur - (int)pv[k - 1].loci <= max_sep) slot[k] = (int32_t)n_di++;
-        if (k >= 2 && pv[k - 1].loci > 0 && cur > 0 && cur - (int)pv[k - 2].loci <= max_sep) slot[n_acc + k] = (int32_t)n_tri++;
-      }
-      if (n_di) {  // (a triple holds two pairs: no pair, no triple)
-        K4DevBuf dl, ds, dd, dt;
-        K4_HIP(ix, dl.alloc(n_acc * 4));
-        K4_HIP(ix, ds.alloc(2 * n_acc * 4));
-        K4_HIP(ix, dd.alloc((size_t)n_di * 17 * 4));
-        K4_HIP(ix, dt.alloc((size_t)n_tri * 65 * 4));
-        K4_HIP(ix, hipMemcpyAsync(dl.p, loci.data(), n_acc * 4, hipMemcpyHostToDevice, st));
-        K4_HIP(ix, hipMemcpyAsync(ds.p, slot.data(), 2 * n_acc * 4, hipMemcpyHostToDevice, st));
-        K4_HIP(ix, hipMemsetAsync(dd.p, 0, (size_t)n_di * 17 * 4, st));
-        if (n_tri) K4_HIP(ix, hipMemsetAsync(dt.p, 0, (size_t)n_tri * 65 * 4, st));
-        HapArgs hp;
-        hp.loci = dl.as<uint32_t>(); hp.di_slot = ds.as<int32_t>(); hp.tri_slot = ds.as<int32_t>() + n_acc; hp.n_loci = (uint32_t)n_acc;
-        hp.di = dd.as<uint32_t>(); hp.tri = dt.as<uint32_t>();
-        const int64_t nb = std::min<int64_t>((a.rs.n_reads + 255) / 256, 8192);
-        hipLaunchKernelGGL(k4k_snp_haplotypes, dim3((unsigned)nb), dim3(256), 0, st, a, hp);
-        std::vector<uint32_t> hd((size_t)n_di * 17), ht((size_t)n_tri * 65);
-        K4_HIP(ix, hipMemcpyAsync(hd.data(), dd.p, hd.size() * 4, hipMemcpyDeviceToHost, st));
-        if (n_tri) K4_HIP(ix, hipMemcpyAsync(ht.data(), dt.p, ht.size() * 4, hipMemcpyDeviceToHost, st));
-        K4_HIP(ix, hipStreamSynchronize(st));
-        int tot_di = 0, tot_tri = 0;  // (the ids restart with every chromosome, :7634-7635)
-        for (size_t k = 1; k < n_acc; k++) {
-          if (di_text && slot[k] >= 0) {
-            const uint32_t l2[2] = {pv[k - 1].loci, pv[k].loci}, r2[2] = {pv[k - 1].ref_base, pv[k].ref_base};
-            if (hap_line(*di_text, "DiSNPs", tot_di + 1, ix->dataset, e.name, l2, r2, 2, &hd[(size_t)slot[k] * 17], min_snp_reads)) tot_di++;
-          }
-          if (tri_text && k >= 2 && slot[n_acc + k] >= 0) {
-            const uint32_t l3[3] = {pv[k - 2].loci, pv[k - 1].loci, pv[k].loci}, r3[3] = {pv[k - 2].ref_base, pv[k - 1].ref_base, pv[k].ref_base};
-            if (hap_line(*tri_text, "TriSNPs", tot_tri + 1, ix->dataset, e.name, l3, r3, 3, &ht[(size_t)slot[n_acc + k] * 65], min_snp_reads)) tot_tri++;
-          }
-        }
-      }
-    }
-    for (LociPV& p : pv) {
-      tot_snps++;
-      if (want_cent && p.cent != K4_CENT_NONE) {  // the called SNP's counts as piled, for the 7-mer around it (:8104-8133)
-        Centroid& r = cent_rows[p.cent];
-        r.n_snps++;
-        r.ref_cnt += p.num_reads - p.num_subs;
-        for (int b = 0; b < 5; b++) r.by_base[b] += p.by_base[b];
-      }
-      int rel = (int)(999 - ((999 * (int64_t)p.rank) / (int64_t)n_acc));
-      if (rel < 1) rel = 1;
-      char line[512];
-      if (vcf) {  // alternative alleles with at least a tenth of the strongest one's count, their frequencies, phred of the p-value
-        uint32_t thres = 0;
-        for (uint32_t b = 0; b < 4; b++)
-          if (b != p.ref_base && p.by_base[b] > thres) thres = p.by_base[b];
-        thres = std::max((thres + 5) / 10, 1u);
-        // (the reference never clears its two strings: a SNP whose mismatches are all N prints what the SNP before it left there)
-        int ao = 0, fo = 0;
-        for (uint32_t b = 0; b < 4; b++) {
-          if (b == p.ref_base || p.by_base[b] < thres) continue;
-          if (ao > 0) { alts[ao++] = ','; freq[fo++] = ','; }
-          alts[ao++] = "ACGT"[b]; alts[ao] = 0;
-          fo += sprintf(&freq[fo], "%1.4f", (double)p.by_base[b] / p.num_reads);
-        }
-        const int phred = p.pvalue < 0.0000000001 ? 100 : (int)(0.5 + (10.0 * log10(1.0 / p.pvalue)));
-        const int n = snprintf(line, sizeof(line), "%s\t%u\tSNP%d\t%c\t%s\t%d\tPASS\tAF=%s;DP=%d\n", e.name, p.loci + 1, (int)tot_snps, "ACGTN"[p.ref_base],
-                               alts, phred, freq, (int)p.num_reads);
-        text.append(line, (size_t)n);
-        continue;
-      }
-      p.by_base[p.ref_base] = p.num_reads - p.num_subs;  // :7698
-      const int n = snprintf(line, sizeof(line), "%d,\"SNP\",\"%s\",\"%s\",%d,%d,1,\"+\",%d,%f,%d,%d,\"%c\",%d,%d,%d,%d,%d,%f,%d,%d,%d,%d\n", (int)tot_snps,
-                             ix->dataset.c_str(), e.name, (int)p.loci, (int)p.loci, rel, p.pvalue, (int)p.num_reads, (int)p.num_subs, "ACGTN"[p.ref_base],
-                             (int)p.by_base[0], (int)p.by_base[1], (int)p.by_base[2], (int)p.by_base[3], (int)p.by_base[4], p.bkgnd, (int)p.local_reads,
-                             (int)p.local_subs, (int)p.marker_id, (int)p.n_poly);
-      text.append(line, (size_t)n);
-    }
-  }
-  if (wig) {  // header + the chromosomes' texts, copied side by side into the one block the caller gets (gigabytes at low coverage)
-    const std::string hdr = "track type=wiggle_0 name=\"Coverage\" description=\"Alignment Segment Coverage\" useScore=1\n";  // :8235
-    std::vector<WigOut> parts;
-    parts.reserve(wig_jobs.size());
-    std::vector<size_t> at;
-    size_t total = hdr.size();
-    for (WigJob& j : wig_jobs) {
-      parts.push_back(j.f.get());
-      if (!j.close_tail) parts.back().tail.clear();
-      at.push_back(total);
-      total += parts.back().body.size() + parts.back().tail.size();
-    }
-    char* wo = (char*)malloc(total + 1);
-    if (!wo) return k4_fail(ix, K4_ERR_MEM, "out of memory");
-    memcpy(wo, hdr.data(), hdr.size());
-    std::vector<std::future<void>> cp;
-    for (size_t k = 0; k < parts.size(); k++)
-      cp.push_back(std::async(std::launch::async, [&, k] {
-        memcpy(wo + at[k], parts[k].body.data(), parts[k].body.size());
-        memcpy(wo + at[k] + parts[k].body.size(), parts[k].tail.data(), parts[k].tail.size());
-      }));
-    for (std::future<void>& f : cp) f.get();
-    wo[total] = 0;
-    *wig = wo;
-    *wig_bytes = total;
-  }
-  if (want_cent) {  // the centroid file (:8626-8660): every 7-mer, whether seen or not
-    std::vector<unsigned long long> insts(K4_CENT_BINS);
-    K4_HIP(ix, hipMemcpyAsync(insts.data(), cent_tab.p, (size_t)K4_CENT_BINS * 8, hipMemcpyDeviceToHost, st));
-    K4_HIP(ix, hipStreamSynchronize(st));
-    std::string& ct = extra->centroids;
-    ct = "\"CentroidID\",\"Seq\",\"NumInsts\",\"NumSNPs\",\"RefBase\",\"RefBaseCnt\",\"BaseA\",\"BaseC\",\"BaseG\",\"BaseT\",\"BaseN\"\n";
-    char line[256];
-    for (uint32_t id = 0; id < K4_CENT_BINS; id++) {
-      char sq[8];
-      for (int k = 0; k < 7; k++) sq[k] = "ACGT"[(id >> (2 * (6 - k))) & 3u];
-      sq[7] = 0;
-      const Centroid& r = cent_rows[id];
-      const int n = snprintf(line, sizeof(line), "%d,\"%s\",%d,%d,\"%c\",%d,%d,%d,%d,%d,%d\n", (int)id + 1, sq, (int)insts[id], (int)r.n_snps, sq[3], (int)r.ref_cnt,
-                             (int)r.by_base[0], (int)r.by_base[1], (int)r.by_base[2], (int)r.by_base[3], (int)r.by_base[4]);
-      ct.append(line, (size_t)n);
-    }
-  }
-  char* out = (char*)malloc(text.size() + 1);
-  if (!out) return k4_fail(ix, K4_ERR_MEM, "out of memory");
-  memcpy(out, text.c_str(), text.size() + 1);
-  *csv = out;
-  *csv_bytes = text.size();
-  if (n_snps) *n_snps = tot_snps;
   return K4_OK;
 }
 extern "C" void k4_free_host(void* p) { free(p); }

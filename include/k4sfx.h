@@ -544,6 +544,53 @@ int k4_prepare_reads_trim_dev(k4_index* ix, int pe, int64_t n_units, int32_t min
                               int32_t sample_nth, int64_t first_unit, const void* d_offs1, const void* d_lens1, const void* d_offs2, const void* d_lens2, uint64_t reads2_base,
                               void* d_offs_out, void* d_lens_out, uint64_t* n_under, uint64_t* n_over, uint32_t* max_read_len,
                               void* stream);
+/* ---- contaminant flank trimming (`kalign -H <file>`, --contaminants; kit4b_amd/csrc/k4_contam.hip) --------------------------
+ * k4_load_contaminants   <- CContaminants::LoadContaminantsFile (libkit4b/Contaminants.cpp:211-443) with AddFlankContam (:650-816) and
+ *                           FinaliseContaminants (:449): a multi-FASTA, plain or gzip, of 4..200 bases A, C, G, T or N per record.  The
+ *                           first word of the descriptor is the name; `@` and digits behind it name the classes (1 5' of SE/PE1, 2 5' of
+ *                           PE2, 3 3' of SE/PE1, 4 3' of PE2, 5..8 the same for the reverse complement); without a code, or without a
+ *                           descriptor, classes 1, 2, 5 and 6.  One k4_contaminant per (record, class), at most 1600; *tbl is malloc'd
+ *                           (k4_free_host), ordered by class and falling length.  What the reference refuses (a length outside 4..200, an
+ *                           illegal base, a name or a sequence twice in one class, too many entries, nothing loaded) gives K4_ERR_PARSE /
+ *                           K4_ERR_PARAMS with the reference's sentence in k4_last_error (ix may be NULL) and, when errbuf is not NULL, in
+ *                           errbuf (256 bytes).  A `&` (vector, containment) record gives K4_ERR_UNSUPPORTED.  Host only.
+ * k4_contam_match_host   <- CContaminants::MatchContaminants (:1243-1325) as the plain rule its trie answers (k4_contam_rule.h): the
+ *                           largest overlap L >= max(min_overlap, 1) of a contaminant of class cls (0..3) onto the read end, 0 for none,
+ *                           for a read outside 20..2000 bases or a class without entries.  read_bases: etSeqBase bytes (bits 0..2 count).
+ *                           < 0: a K4_* code.  Host only: no device, no index.
+ * k4_contam_trims_dev    <- the calls of LoadRawReads (ngskit4b/KAligner.cpp:11992-12039) for every read of a parsed chunk, as
+ *                           k4_parse_fastx_dev left it (PE: both ends, d_offs2 / d_lens2, their offsets relative to d_reads +
+ *                           reads2_base): d_contam5[r] / d_contam3[r] (bytes; PE: r = 2i for PE1 and 2i + 1 for PE2 of pair i) = the overlap
+ *                           beyond the end trim, max(L - trim5, 0) / max(L - trim3, 0) with a minimum overlap of trim + 1.  Units that
+ *                           `-#` (sample_nth, first_unit as in k4_prepare_reads_trim_dev) does not load get 0.  totals4 (host, may be NULL):
+ *                           reads with a 5' / 3' trim among PE1, then among PE2, before any length test.  tbl: HOST array.  Waits for
+ *                           `stream`.
+ * k4_prepare_reads_contam_dev: k4_prepare_reads_trim_dev with the per-read trims beside trim5 / trim3 (either array NULL: zeros): the length
+ *                           tests go over trim5 + trim3 + contam5 + contam3 (:12041-12075), a kept read starts trim5 + contam5 bases in and
+ *                           loses trim3 + contam3 at its end (:12254-12261, :12280-12286; the quality of a base lives in its byte and goes
+ *                           with it).  n_contam4 (host, may be NULL): the reference's four totals (:12262-12265, :12287-12290), the KEPT
+ *                           reads with a 5' / 3' contaminant trim among PE1, then among PE2. */
+typedef struct {
+  uint8_t cls;          /* teContamType: 0 5' of SE/PE1, 1 5' of PE2, 2 3' of SE/PE1, 3 3' of PE2 */
+  uint8_t len;          /* 4..200 */
+  uint8_t revcpl;       /* the record's reverse complement (codes 5..8) */
+  uint8_t reserved[5];
+  /* one bit per base in 256 positions: the two bits of A=0 C=1 G=2 T=3, and "is N".  5' classes: base k of len at position
+   * 256 - len + k (the suffix ends at 255); 3' classes: base k at position k */
+  uint64_t p0[4], p1[4], nmask[4];
+} k4_contaminant;
+int k4_load_contaminants(k4_index* ix, const char* path, k4_contaminant** tbl, int32_t* n, char* errbuf);
+int k4_contam_match_host(const k4_contaminant* tbl, int32_t n, int32_t cls, int32_t min_overlap, const uint8_t* read_bases,
+                         int32_t read_len);
+int k4_contam_trims_dev(k4_index* ix, const k4_contaminant* tbl, int32_t n, int pe, int64_t n_units, int32_t trim5, int32_t trim3,
+                        int32_t sample_nth, int64_t first_unit, const void* d_reads, const void* d_offs1, const void* d_lens1,
+                        const void* d_offs2, const void* d_lens2, uint64_t reads2_base, void* d_contam5, void* d_contam3,
+                        uint64_t* totals4, void* stream);
+int k4_prepare_reads_contam_dev(k4_index* ix, int pe, int64_t n_units, int32_t min_len, int32_t max_len, int32_t trim5, int32_t trim3,
+                                int32_t sample_nth, int64_t first_unit, const void* d_offs1, const void* d_lens1, const void* d_offs2,
+                                const void* d_lens2, uint64_t reads2_base, const void* d_contam5, const void* d_contam3,
+                                void* d_offs_out, void* d_lens_out, uint64_t* n_under, uint64_t* n_over, uint32_t* max_read_len,
+                                uint64_t* n_contam4, void* stream);
 int k4_format_sam_dev(k4_index* ix, int pe, int64_t n_units, const void* d_rr, const void* d_hits, int32_t max_ml,
                       const void* d_pe, const void* d_reads, const void* d_offs, const void* d_lens,
                       const k4_sam_names* names, void** d_sam, uint64_t* sam_bytes, k4_sam_stats* stats,
@@ -721,6 +768,11 @@ typedef struct {                /* where the aligned batch lives in HBM (for the
 int k4_pipeline_open(k4_index* ix, const k4_pipeline_params* p, k4_pipeline** out);
 int k4_pipeline_set_trims(k4_pipeline* pl, int32_t trim5, int32_t trim3); /* kalign -y / -Y; before the first chunk is submitted */
 int k4_pipeline_set_sampling(k4_pipeline* pl, int32_t sample_nth);          /* kalign -#<n> (one input file per end); likewise */
+/* kalign -H: k4_contam_trims_dev runs on the compute stream between the parse and the prepare of every batch (the table, a HOST array
+ * of k4_load_contaminants, is copied); likewise before the first chunk.  Never called: no kernel more, no buffer more than before */
+int k4_pipeline_set_contaminants(k4_pipeline* pl, const k4_contaminant* tbl, int32_t n);
+/* ... and after k4_pipeline_wait_aligned the reference's four totals (n_contam4 of k4_prepare_reads_contam_dev) over the run */
+int k4_pipeline_contam_totals(k4_pipeline* pl, uint64_t* n_contam4);
 int k4_pipeline_acquire(k4_pipeline* pl, int end, void** buf, uint64_t* cap); /* blocks while every buffer is on its way up */
 int k4_pipeline_submit(k4_pipeline* pl, int end, uint64_t bytes, int final_chunk);
 /* text in the caller's own memory (pinned for the full PCIe rate); it must stay valid until k4_pipeline_wait_aligned returns */

@@ -115,6 +115,16 @@ LOCI_CONSTRAINT_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end",
 NAR_CHROMFILT, NAR_LOCICONSTRAINED = 11, 19
 
 
+class Contaminant(C.Structure):  # k4_contaminant
+    _fields_ = [("cls", C.c_uint8), ("len", C.c_uint8), ("revcpl", C.c_uint8), ("reserved", C.c_uint8 * 5), ("p0", C.c_uint64 * 4),
+                ("p1", C.c_uint64 * 4), ("nmask", C.c_uint64 * 4)]
+
+
+CONTAMINANT_DTYPE = np.dtype([("cls", "u1"), ("len", "u1"), ("revcpl", "u1"), ("reserved", "u1", (5,)), ("p0", "<u8", (4,)), ("p1", "<u8", (4,)),
+                              ("nmask", "<u8", (4,))])
+CONTAM_5PE1, CONTAM_5PE2, CONTAM_3PE1, CONTAM_3PE2 = 0, 1, 2, 3  # teContamType
+
+
 class AlignStats(C.Structure):  # k4_align_stats
     _fields_ = [("max_align_len", C.c_uint32), ("len_stride", C.c_uint32), ("n_entries", C.c_uint32), ("reserved", C.c_uint32),
                 ("n_accepted", C.c_uint64), ("q_insts", C.POINTER(C.c_uint64)), ("q_subs", C.POINTER(C.c_uint64)),
@@ -185,6 +195,8 @@ ABI_SYMBOLS = [
     "k4_filter_marked_prior", "k4_site_prefs_dev", "k4_free_site_prefs", "k4_write_site_prefs", "k4_pipeline_site_prefs",
     "k4_pe_insert_dist_dev", "k4_free_pe_insert_dist", "k4_write_pe_insert_dist", "k4_pipeline_pe_insert_dist", "k4_pe_insert_bin_host",
     "k4_pe_insert_median_host", "k4_pba_run_dev", "k4_pba_classify_host", "k4_snp_run2_dev", "k4_marker_classify_host",
+    "k4_load_contaminants", "k4_contam_match_host", "k4_contam_trims_dev", "k4_prepare_reads_contam_dev", "k4_pipeline_set_contaminants",
+    "k4_pipeline_contam_totals",
 ]
 
 
@@ -319,6 +331,13 @@ def lib():
     L.k4_unaligned_fasta_dev.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, C.POINTER(SamNames), C.c_int32, pvp, pu64, pu64, vp]
     L.k4_prepare_reads_trim_dev.argtypes = [vp, i32, i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i64, vp, vp, vp, vp, u64,
                                             vp, vp, pu64, pu64, C.POINTER(u32), vp]
+    L.k4_load_contaminants.argtypes = [vp, C.c_char_p, C.POINTER(C.POINTER(Contaminant)), C.POINTER(C.c_int32), C.c_char_p]
+    L.k4_contam_match_host.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32]
+    L.k4_contam_trims_dev.argtypes = [vp, vp, C.c_int32, i32, i64, C.c_int32, C.c_int32, C.c_int32, i64, vp, vp, vp, vp, vp, u64, vp, vp, pu64, vp]
+    L.k4_prepare_reads_contam_dev.argtypes = [vp, i32, i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i64, vp, vp, vp, vp, u64, vp, vp,
+                                              vp, vp, pu64, pu64, C.POINTER(u32), pu64, vp]
+    L.k4_pipeline_set_contaminants.argtypes = [vp, vp, C.c_int32]
+    L.k4_pipeline_contam_totals.argtypes = [vp, pu64]
     snp_head = [vp, i32, i64, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, dbl, dbl]  # ix, pe .. snp_nonref_pcnt
     L.k4_snp_csv_dev.argtypes = snp_head + [pvp, pu64, pu64, vp]
     L.k4_snp_vcf_dev.argtypes = snp_head + [pvp, pu64, pu64, vp]
@@ -801,6 +820,40 @@ class SfxIndex:
         finally:
             lib().k4_free_host(C.cast(tbl, C.c_void_p))
 
+    def load_contaminants(self, path):
+        """LoadContaminantsFile (`kalign -H <file>`): see the module's load_contaminants; a refusal is also left in this index's last error."""
+        return load_contaminants(path, _ix=self)
+
+    def contaminant_trims(self, contaminants, reads, reads2=None, trim5=0, trim3=0, sample_nth=1, first_unit=0):
+        """k4_contam_trims_dev over host reads (PE: reads2 holds the mates): (contam5, contam3, totals) -- per read (PE: interleaved,
+        2i = PE1 and 2i + 1 = PE2 of pair i) the bases a contaminant of its class overlaps the 5' / 3' end by beyond trim5 / trim3, and
+        the reads with such a trim at the 5' / 3' end among PE1, then among PE2 (before any length test)."""
+        import torch
+
+        pe = reads2 is not None
+        tbl = np.ascontiguousarray(contaminants, dtype=CONTAMINANT_DTYPE)
+        c1, o1, l1 = _flatten(reads)
+        n = len(l1)
+        if pe:
+            c2, o2, l2 = _flatten(reads2)
+            assert len(l2) == n
+        else:
+            c2, o2, l2 = np.zeros(0, np.uint8), np.zeros(0, np.uint64), np.zeros(0, np.uint32)
+        dev = torch.device("cuda", self.info()["device"])
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
+        d_reads = t(np.concatenate([c1, c2, np.zeros(16, np.uint8)]))
+        d_o1, d_l1, d_o2, d_l2 = t(o1), t(l1), t(o2), t(l2)
+        nr = 2 * n if pe else n
+        d_c5 = torch.full((nr + 1,), 255, dtype=torch.uint8, device=dev)
+        d_c3 = torch.full((nr + 1,), 255, dtype=torch.uint8, device=dev)
+        tot = (C.c_uint64 * 4)()
+        self._ck(lib().k4_contam_trims_dev(self.h, tbl.ctypes.data, len(tbl), 1 if pe else 0, n, int(trim5), int(trim3), int(sample_nth), int(first_unit),
+                                           d_reads.data_ptr(), d_o1.data_ptr(), d_l1.data_ptr(), d_o2.data_ptr() if pe else None,
+                                           d_l2.data_ptr() if pe else None, len(c1), d_c5.data_ptr(), d_c3.data_ptr(), tot,
+                                           torch.cuda.current_stream().cuda_stream))
+        assert int(d_c5[nr]) == 255 and int(d_c3[nr]) == 255  # nothing behind the last read was written
+        return d_c5[:nr].cpu().numpy(), d_c3[:nr].cpu().numpy(), tuple(int(x) for x in tot)
+
     def chrom_accept_mask(self, include=(), exclude=()):
         """Which sequences `kalign -z <include regex> -Z <exclude regex>` keeps (CUtility::MatchExcludeRegExpr / MatchIncludeRegExpr):
         uint8[n_entries + 1] indexed by entry id, 1 = keep; an expression that does not compile raises K4Error (-100)."""
@@ -1022,6 +1075,32 @@ class SfxIndex:
 def pe_insert_bin_host(tlen):
     """The column (0..51) of `kalign -3`'s table an insert length is counted in (k4_pe_insert_bin_host; needs the library, no GPU)."""
     return int(lib().k4_pe_insert_bin_host(int(tlen)))
+
+
+def load_contaminants(path, _ix=None):
+    """LoadContaminantsFile (`kalign -H <file>`, libkit4b/Contaminants.cpp:211-443): the flank contaminants of a multi-FASTA (plain or
+    gzip) as a CONTAMINANT_DTYPE array, one element per (record, class), by class and falling length.  A file the reference turns down
+    raises K4Error with its sentence; a `&` (vector) record raises K4Error (-3).  Needs the library, no GPU and no index."""
+    tbl, n = C.POINTER(Contaminant)(), C.c_int32(0)
+    err = C.create_string_buffer(256)
+    rc = lib().k4_load_contaminants(_ix.h if _ix is not None else None, os.fsencode(path), C.byref(tbl), C.byref(n), err)
+    if rc != 0:
+        raise K4Error(rc, err.value.decode("latin-1"))
+    try:
+        return np.frombuffer(C.string_at(tbl, n.value * C.sizeof(Contaminant)), CONTAMINANT_DTYPE).copy()
+    finally:
+        lib().k4_free_host(C.cast(tbl, C.c_void_p))
+
+
+def contam_match_host(contaminants, cls, min_overlap, read_bases):
+    """MatchContaminants as the plain rule (k4_contam_match_host): the largest overlap >= max(min_overlap, 1) of a contaminant of class
+    cls (0..3) onto the read's 5' (classes 0, 1) or 3' end, 0 for none.  read_bases: etSeqBase bytes.  Needs the library, no GPU."""
+    tbl = np.ascontiguousarray(contaminants, dtype=CONTAMINANT_DTYPE)
+    rd = np.ascontiguousarray(read_bases, dtype=np.uint8)
+    rc = int(lib().k4_contam_match_host(tbl.ctypes.data if len(tbl) else None, len(tbl), int(cls), int(min_overlap), rd.ctypes.data if len(rd) else None, len(rd)))
+    if rc < 0:
+        raise K4Error(rc, "k4_contam_match_host")
+    return rc
 
 
 def pe_insert_median_host(values):

@@ -141,6 +141,16 @@ int k4i_kalign_batch_dev(k4_index* ix, const k4_kalign_params* p, int64_t n, int
 // k4_stats.hip: the run tallies of `kalign -O` (no-ops while k4_align_stats_collect is off)
 int k4i_stats_tally_multi(k4_index* ix, const void* d_rr, int64_t n, void* stream);
 unsigned long long* k4i_stats_pe_len_dist(k4_index* ix);
+// k4_contam.hip: the table of `kalign -H` in HBM, per class (teContamType) its entries by falling length: bits = 12 rows
+// (plane 0..2 x word 0..3 of k4_contaminant) of n[cls] words each, lens = n[cls] lengths; and k4_contam_trims_dev over it
+struct K4ContamDev {
+  K4DevBuf bits[4], lens[4];
+  uint32_t n[4] = {0, 0, 0, 0};
+};
+int k4i_contam_upload(k4_index* ix, const k4_contaminant* tbl, int32_t n, K4ContamDev* out);
+int k4i_contam_trims(k4_index* ix, const K4ContamDev& t, int pe, int64_t n_units, int32_t trim5, int32_t trim3, int32_t sample_nth,
+                     int64_t first_unit, const void* d_reads, const void* d_offs1, const void* d_lens1, const void* d_offs2,
+                     const void* d_lens2, uint64_t reads2_base, void* d_contam5, void* d_contam3, uint64_t* totals4, hipStream_t st);
 // k4_sabuild.hip
 int k4i_build_sa(uint64_t n, uint32_t el, const uint8_t* d_seq, uint8_t* d_sa, int device, std::string* err);
 

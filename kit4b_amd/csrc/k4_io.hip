@@ -389,40 +389,51 @@ __global__ void __launch_bounds__(256) k4k_prepare_reads(int pe, int64_t n, uint
                                                          const uint64_t* __restrict__ o2, const uint32_t* __restrict__ l2,
                                                          uint64_t base2, uint64_t* __restrict__ oo, uint32_t* __restrict__ lo,
                                                          unsigned long long* __restrict__ tot, uint32_t trim5, uint32_t trim3, uint32_t sample_nth,
-                                                         int64_t first_unit) {
+                                                         int64_t first_unit, const uint8_t* __restrict__ c5, const uint8_t* __restrict__ c3) {
   // grid-stride, tallies kept per thread and folded once per wave at the end: a same-address atomic per wave of a
   // one-thread-per-read launch (312 k of them for 20 M reads) costs more than the whole copy
   uint32_t n_u = 0, n_o = 0, mx = 0;
+  uint32_t n_c[4] = {0, 0, 0, 0};  // `-H`: kept reads with a 5' / 3' contaminant trim among PE1, among PE2 (KAligner.cpp:12262-12265, :12287-12290)
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-    // the end trims of `-y` / `-Y` come off first (KAligner.cpp:12254-12260); sloughed in the reference's order of tests (:12040-12090):
+    // the end trims of `-y` / `-Y` come off first (KAligner.cpp:12254-12260), with them what `-H` found of a contaminant beyond them on that
+    // read (c5 / c3, PE: interleaved; null without -H); sloughed in the reference's order of tests (:12040-12090):
     // PE1 under, PE1 over, PE2 under, PE2 over -- which tally a pair lands in depends on it
-    const uint32_t trims = trim5 + trim3;
+    const int64_t ia = pe ? 2 * i : i, ib = pe ? 2 * i + 1 : i;
+    const uint32_t a5 = trim5 + (c5 ? c5[ia] : 0u), a3 = trim3 + (c3 ? c3[ia] : 0u);
+    const uint32_t b5 = trim5 + (c5 ? c5[ib] : 0u), b3 = trim3 + (c3 ? c3[ib] : 0u);
     const uint32_t ra = l1[i], rb = pe ? l2[i] : ra;
-    const uint32_t a = ra > trims ? ra - trims : 0, b = rb > trims ? rb - trims : 0;
+    const uint32_t a = ra > a5 + a3 ? ra - (a5 + a3) : 0, b = rb > b5 + b3 ? rb - (b5 + b3) : 0;
     // `-#<n>`: every n-th read (pair) of the file is loaded, the first one included; the others are never looked at (:11983-11989)
     const bool sampled = sample_nth <= 1 || (uint64_t)(first_unit + i) % sample_nth == 0;
     const bool under = sampled && (a < min_len || (a <= max_len && b < min_len));
     const bool over = sampled && !under && (a > max_len || b > max_len);
     const bool keep = sampled && !under && !over;
     if (pe) {
-      oo[2 * i] = o1[i] + trim5; lo[2 * i] = keep ? a : 0;
-      oo[2 * i + 1] = o2[i] + base2 + trim5; lo[2 * i + 1] = keep ? b : 0;
+      oo[2 * i] = o1[i] + a5; lo[2 * i] = keep ? a : 0;
+      oo[2 * i + 1] = o2[i] + base2 + b5; lo[2 * i + 1] = keep ? b : 0;
     } else {
-      oo[i] = o1[i] + trim5; lo[i] = keep ? a : 0;
+      oo[i] = o1[i] + a5; lo[i] = keep ? a : 0;
     }
     n_u += under; n_o += over;
     if (keep) mx = max(mx, max(a, b));
+    if (keep && c5) { n_c[0] += a5 > trim5; n_c[1] += a3 > trim3; if (pe) { n_c[2] += b5 > trim5; n_c[3] += b3 > trim3; } }
   }
   for (int d = 32; d > 0; d >>= 1) {
     n_u += __shfl_xor(n_u, d, 64);
     n_o += __shfl_xor(n_o, d, 64);
     mx = max(mx, (uint32_t)__shfl_xor(mx, d, 64));
   }
+  if (c5)
+    for (int k = 0; k < 4; k++)
+      for (int d = 32; d > 0; d >>= 1) n_c[k] += __shfl_xor(n_c[k], d, 64);
   if ((threadIdx.x & 63) == 0) {
     if (n_u) atomicAdd(&tot[0], (unsigned long long)n_u);
     if (n_o) atomicAdd(&tot[1], (unsigned long long)n_o);
     if (mx) atomicMax(&tot[2], (unsigned long long)mx);
+    if (c5)
+      for (int k = 0; k < 4; k++)
+        if (n_c[k]) atomicAdd(&tot[3 + k], (unsigned long long)n_c[k]);
   }
 }
 }  // namespace
@@ -440,28 +451,41 @@ extern "C" int k4_prepare_reads_trim_dev(k4_index* ix, int pe, int64_t n, int32_
                                          int32_t sample_nth, int64_t first_unit, const void* d_offs1, const void* d_lens1, const void* d_offs2, const void* d_lens2,
                                          uint64_t reads2_base, void* d_offs_out, void* d_lens_out, uint64_t* n_under, uint64_t* n_over,
                                          uint32_t* max_read_len, void* stream) {
-  if (!ix || n < 0 || trim5 < 0 || trim3 < 0 || sample_nth < 0 || first_unit < 0) return K4_ERR_PARAMS;
+  return k4_prepare_reads_contam_dev(ix, pe, n, min_len, max_len, trim5, trim3, sample_nth, first_unit, d_offs1, d_lens1, d_offs2, d_lens2, reads2_base,
+                                     nullptr, nullptr, d_offs_out, d_lens_out, n_under, n_over, max_read_len, nullptr, stream);
+}
+// ... and with the per-read contaminant trims of `-H` (k4_contam_trims_dev; both arrays or neither): offsets, lengths, the pair-drop
+// rule and the under / over counts of every prepare call come from this one place
+extern "C" int k4_prepare_reads_contam_dev(k4_index* ix, int pe, int64_t n, int32_t min_len, int32_t max_len, int32_t trim5, int32_t trim3,
+                                           int32_t sample_nth, int64_t first_unit, const void* d_offs1, const void* d_lens1, const void* d_offs2,
+                                           const void* d_lens2, uint64_t reads2_base, const void* d_contam5, const void* d_contam3,
+                                           void* d_offs_out, void* d_lens_out, uint64_t* n_under, uint64_t* n_over, uint32_t* max_read_len,
+                                           uint64_t* n_contam4, void* stream) {
+  if (!ix || n < 0 || trim5 < 0 || trim3 < 0 || sample_nth < 0 || first_unit < 0 || (d_contam5 == nullptr) != (d_contam3 == nullptr)) return K4_ERR_PARAMS;
   if (n_under) *n_under = 0;
   if (n_over) *n_over = 0;
   if (max_read_len) *max_read_len = 0;
+  if (n_contam4) n_contam4[0] = n_contam4[1] = n_contam4[2] = n_contam4[3] = 0;
   if (n == 0) return K4_OK;
   if (!d_offs1 || !d_lens1 || !d_offs_out || !d_lens_out || (pe && (!d_offs2 || !d_lens2))) return k4_fail(ix, K4_ERR_PARAMS, "null buffer");
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
   PoolStream pool_scope(st);
   Buf tot;
-  K4_HIP(ix, tot.alloc(24));
-  K4_HIP(ix, hipMemsetAsync(tot.p, 0, 24, st));
+  K4_HIP(ix, tot.alloc(56));
+  K4_HIP(ix, hipMemsetAsync(tot.p, 0, 56, st));
   hipLaunchKernelGGL(k4k_prepare_reads, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), 0, st, pe ? 1 : 0, n,
                      (uint32_t)std::max(min_len, 0), (uint32_t)std::max(max_len, 0), (const uint64_t*)d_offs1, (const uint32_t*)d_lens1,
                      (const uint64_t*)d_offs2, (const uint32_t*)d_lens2, reads2_base, (uint64_t*)d_offs_out, (uint32_t*)d_lens_out,
-                     tot.as<unsigned long long>(), (uint32_t)trim5, (uint32_t)trim3, (uint32_t)sample_nth, first_unit);
-  unsigned long long t[3];
-  K4_HIP(ix, hipMemcpyAsync(t, tot.p, 24, hipMemcpyDeviceToHost, st));
+                     tot.as<unsigned long long>(), (uint32_t)trim5, (uint32_t)trim3, (uint32_t)sample_nth, first_unit,
+                     (const uint8_t*)d_contam5, (const uint8_t*)d_contam3);
+  unsigned long long t[7];
+  K4_HIP(ix, hipMemcpyAsync(t, tot.p, 56, hipMemcpyDeviceToHost, st));
   K4_HIP(ix, hipStreamSynchronize(st));
   if (n_under) *n_under = t[0];
   if (n_over) *n_over = t[1];
   if (max_read_len) *max_read_len = (uint32_t)t[2];
+  if (n_contam4) for (int k = 0; k < 4; k++) n_contam4[k] = t[3 + k];
   return K4_OK;
 }
 

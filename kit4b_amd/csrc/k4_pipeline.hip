@@ -100,6 +100,10 @@ struct k4_pipeline {
   int n_ends = 1;
   int32_t trim5 = 0, trim3 = 0;  // kalign -y / -Y (k4_pipeline_set_trims)
   int32_t sample_nth = 1;        // kalign -#<n> (k4_pipeline_set_sampling)
+  bool contam_on = false;        // kalign -H (k4_pipeline_set_contaminants): the table, the trims of the batch being prepared, the run's totals
+  K4ContamDev contam;
+  Arena contam5, contam3;
+  uint64_t n_contam[4] = {0, 0, 0, 0};
   // worker
   std::thread worker;
   std::mutex m;
@@ -194,9 +198,21 @@ int align_more(k4_pipeline* pl, bool flush) {
   uint64_t under = 0, over = 0;
   uint32_t max_len = 0;
   const int64_t d = pl->units_done;
-  rc = k4_prepare_reads_trim_dev(ix, pe ? 1 : 0, n, pl->prm.min_len, pl->prm.max_len, pl->trim5, pl->trim3, pl->sample_nth, d, pl->end[0].offs.p + 8 * d, pl->end[0].lens.p + 4 * d,
-                            pe ? pl->end[1].offs.p + 8 * d : nullptr, pe ? pl->end[1].lens.p + 4 * d : nullptr, 0,
-                            pl->c_offs.p + 8 * r0, pl->c_lens.p + 4 * r0, &under, &over, &max_len, pl->s_comp);
+  const uint8_t* const offs1 = pl->end[0].offs.p + 8 * d, * const lens1 = pl->end[0].lens.p + 4 * d;
+  const uint8_t* const offs2 = pe ? pl->end[1].offs.p + 8 * d : nullptr, * const lens2 = pe ? pl->end[1].lens.p + 4 * d : nullptr;
+  if (!pl->contam_on) {
+    rc = k4_prepare_reads_trim_dev(ix, pe ? 1 : 0, n, pl->prm.min_len, pl->prm.max_len, pl->trim5, pl->trim3, pl->sample_nth, d, offs1, lens1, offs2, lens2, 0,
+                                   pl->c_offs.p + 8 * r0, pl->c_lens.p + 4 * r0, &under, &over, &max_len, pl->s_comp);
+  } else {  // -H: the contaminant overlaps of this batch's read ends, then the prepare with them
+    if ((rc = pl->contam5.reserve(ix, (size_t)nr, 8)) != K4_OK || (rc = pl->contam3.reserve(ix, (size_t)nr, 8)) != K4_OK) return rc;
+    rc = k4i_contam_trims(ix, pl->contam, pe ? 1 : 0, n, pl->trim5, pl->trim3, pl->sample_nth, d, pl->reads.p, offs1, lens1, offs2, lens2, 0,
+                          pl->contam5.p, pl->contam3.p, nullptr, pl->s_comp);
+    if (rc != K4_OK) return rc;
+    uint64_t nc[4];
+    rc = k4_prepare_reads_contam_dev(ix, pe ? 1 : 0, n, pl->prm.min_len, pl->prm.max_len, pl->trim5, pl->trim3, pl->sample_nth, d, offs1, lens1, offs2, lens2, 0,
+                                     pl->contam5.p, pl->contam3.p, pl->c_offs.p + 8 * r0, pl->c_lens.p + 4 * r0, &under, &over, &max_len, nc, pl->s_comp);
+    for (int k = 0; k < 4 && rc == K4_OK; k++) pl->n_contam[k] += nc[k];
+  }
   if (rc != K4_OK) return rc;
   pl->c_offs.used = (size_t)(r0 + nr) * 8; pl->c_lens.used = (size_t)(r0 + nr) * 4;
   pl->n_under += under; pl->n_over += over;
@@ -350,7 +366,7 @@ extern "C" int k4_pipeline_open(k4_index* ix, const k4_pipeline_params* p, k4_pi
     for (Arena* a : {&E.text, &E.offs, &E.lens, &E.noff, &E.nlen}) a->st = pl->s_comp;
     E.text.writer = pl->s_in;
   }
-  for (Arena* a : {&pl->reads, &pl->c_offs, &pl->c_lens, &pl->rr, &pl->hits, &pl->seg2, &pl->pe}) a->st = pl->s_comp;
+  for (Arena* a : {&pl->reads, &pl->c_offs, &pl->c_lens, &pl->rr, &pl->hits, &pl->seg2, &pl->pe, &pl->contam5, &pl->contam3}) a->st = pl->s_comp;
   for (int e = 0; e < pl->n_ends && rc == K4_OK; e++) {
     pl->end[e].ring.resize((size_t)pl->prm.n_buffers);
     if (p->expect_text_bytes[e]) rc = pl->end[e].text.reserve(ix, (size_t)p->expect_text_bytes[e] + 64, 64);
@@ -365,6 +381,21 @@ extern "C" int k4_pipeline_set_trims(k4_pipeline* pl, int32_t trim5, int32_t tri
   if (!pl || trim5 < 0 || trim3 < 0 || trim5 > 50 || trim3 > 50) return K4_ERR_PARAMS;
   std::lock_guard<std::mutex> lk(pl->m);
   pl->trim5 = trim5; pl->trim3 = trim3;  // (read by the worker when it prepares a batch: set them before the first submit)
+  return K4_OK;
+}
+
+extern "C" int k4_pipeline_set_contaminants(k4_pipeline* pl, const k4_contaminant* tbl, int32_t n) {
+  if (!pl || !tbl || n < 1) return K4_ERR_PARAMS;
+  std::lock_guard<std::mutex> lk(pl->m);
+  const int rc = k4i_contam_upload(pl->ix, tbl, n, &pl->contam);
+  pl->contam_on = rc == K4_OK;  // (read by the worker when it prepares a batch: before the first submit)
+  return rc;
+}
+
+extern "C" int k4_pipeline_contam_totals(k4_pipeline* pl, uint64_t* n_contam4) {
+  if (!pl || !n_contam4) return K4_ERR_PARAMS;
+  std::lock_guard<std::mutex> lk(pl->m);
+  for (int k = 0; k < 4; k++) n_contam4[k] = pl->n_contam[k];
   return K4_OK;
 }
 
@@ -622,7 +653,7 @@ extern "C" void k4_pipeline_close(k4_pipeline* pl) {
     for (Arena* a : {&E.text, &E.offs, &E.lens, &E.noff, &E.nlen}) a->release();
   }
   for (PinBuf& b : pl->out_ring) { if (b.h) hipHostFree(b.h); if (b.ev) hipEventDestroy(b.ev); }
-  for (Arena* a : {&pl->reads, &pl->c_offs, &pl->c_lens, &pl->rr, &pl->hits, &pl->seg2, &pl->pe}) a->release();
+  for (Arena* a : {&pl->reads, &pl->c_offs, &pl->c_lens, &pl->rr, &pl->hits, &pl->seg2, &pl->pe, &pl->contam5, &pl->contam3}) a->release();
   pl->slices.clear();
   pl->sam_buf.st = pl->s_comp;  // (everything is idle: hipDeviceSynchronize above)
   pl->sam_buf.release();

@@ -84,6 +84,9 @@ struct Opts {
   std::string none_file, multi_file; // -j / -J <file>: the reads without an alignment / the multi-aligned reads as FASTA (KAlignerCL.cpp:254-255)
   int sample_nth = 1;               // -# <n>: every n-th read / pair of the input is processed (KAlignerCL.cpp:244,484-489)
   int trim5 = 0, trim3 = 0;         // -y / -Y <n>: bases taken off the 5' / 3' end of every read when loading (KAlignerCL.cpp:763-774)
+  std::string contam_file;          // -H / --contaminants <file>: flank contaminants trimmed off the read ends when loading (KAlignerCL.cpp:251)
+  k4_contaminant* contam_tbl = nullptr;  // ... loaded before anything touches a device (KAligner.cpp:284-301); lives as long as the process
+  int32_t n_contam_tbl = 0;
   int align_strand = 0;             // -Q <0|1|2>: align to either strand, the sense or the antisense strand only (KAlignerCL.cpp:241,491)
   int fmode = 0;                    // -M <0|1|3>: 0 SAM / BAM with the accepted alignments, 1 SAM with every loaded read (KAlignerCL.cpp:217),
                                     // 3 no SAM: -o is genpba's packed base alleles file (kalignerPBA, KAlignerCL.cpp:1540-2290)
@@ -550,7 +553,7 @@ std::string clean_id(const std::string& raw) {
 void usage() {
   fprintf(stderr,
           "k4align -i reads.f[aq][.gz] [-i more ...] [-u mates ...] -I index.sfx -o out.sam|out.bam [-z bgzf level=6] [-s subs/100bp=5] [-e 1|2] [-m 0..3] [-n maxNs=1]\n"
-          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-Q 0|1|2 strand] [-M 0|1 all reads | -M3 --experimentid id --readsetid id: packed base alleles to -o, no SAM] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-6 pcrprimersubs 0..5] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv [-3 PE insert lengths per target to stats.csv.peinserts.csv]] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv] [-7 centroids.csv] [-K markerlen 25..500 [--markerpolythres 0..0.5=0.333]]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
+          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-H contaminants.fa flank contaminants trimmed off the read ends] [-Q 0|1|2 strand] [-M 0|1 all reads | -M3 --experimentid id --readsetid id: packed base alleles to -o, no SAM] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-6 pcrprimersubs 0..5] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv [-3 PE insert lengths per target to stats.csv.peinserts.csv]] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv] [-7 centroids.csv] [-K markerlen 25..500 [--markerpolythres 0..0.5=0.333]]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
 }
 
 }  // namespace
@@ -668,6 +671,7 @@ struct Run : RunHeld {
   bool two_seg = false, pipelined = false, bam_out = false;
   k4_sam_stats tot;
   uint64_t n_under = 0, n_over = 0, n_units = 0, my_lines = 0;
+  uint64_t n_contam[4] = {0, 0, 0, 0};  // -H: loaded reads with a 5' / 3' contaminant trim among PE1, among PE2
   double s_read = 0, s_parse = 0, s_align = 0, s_write = 0;
   k4_pipeline_view v;        // the pipelined modes: all reads of the run, aligned
   uint64_t pl_sam_bytes = 0;
@@ -821,6 +825,7 @@ struct Run : RunHeld {
     CK(k4_pipeline_open(ix, &pp2, &pl));
     CK(k4_pipeline_set_trims(pl, o.trim5, o.trim3));
     CK(k4_pipeline_set_sampling(pl, o.sample_nth));
+    if (o.contam_tbl) CK(k4_pipeline_set_contaminants(pl, o.contam_tbl, o.n_contam_tbl));
     return 0;
   }
   // -G over uncompressed files: reads are independent units, rank r aligns the r-th contiguous slice of the records (pairs stay
@@ -1085,8 +1090,21 @@ struct Run : RunHeld {
     uint32_t max_len = 0;
     CK(alloc_dev(ix, (uint64_t)(n_reads + 1) * 8, d_offs));
     CK(alloc_dev(ix, (uint64_t)(n_reads + 1) * 4, d_lens));
-    CK(k4_prepare_reads_trim_dev(ix, pe ? 1 : 0, n, o.min_len, o.max_len, o.trim5, o.trim3, 1, 0, from_r0(p1.offs, 8), from_r0(p1.lens, 4),
-                                 from_r0(p2.offs, 8), from_r0(p2.lens, 4), 0, d_offs.get(), d_lens.get(), &under, &over, &max_len, nullptr));
+    if (!o.contam_tbl)
+      CK(k4_prepare_reads_trim_dev(ix, pe ? 1 : 0, n, o.min_len, o.max_len, o.trim5, o.trim3, 1, 0, from_r0(p1.offs, 8), from_r0(p1.lens, 4),
+                                   from_r0(p2.offs, 8), from_r0(p2.lens, 4), 0, d_offs.get(), d_lens.get(), &under, &over, &max_len, nullptr));
+    else {  // -H: the same ingest calls as the pipeline's (every batch, every slice: the stage is per read)
+      DevBlock d_c5, d_c3;
+      uint64_t nc[4];
+      CK(alloc_dev(ix, (uint64_t)n_reads + 1, d_c5));
+      CK(alloc_dev(ix, (uint64_t)n_reads + 1, d_c3));
+      CK(k4_contam_trims_dev(ix, o.contam_tbl, o.n_contam_tbl, pe ? 1 : 0, n, o.trim5, o.trim3, 1, 0, d_reads.get(), from_r0(p1.offs, 8), from_r0(p1.lens, 4),
+                             from_r0(p2.offs, 8), from_r0(p2.lens, 4), 0, d_c5.get(), d_c3.get(), nullptr, nullptr));
+      CK(k4_prepare_reads_contam_dev(ix, pe ? 1 : 0, n, o.min_len, o.max_len, o.trim5, o.trim3, 1, 0, from_r0(p1.offs, 8), from_r0(p1.lens, 4),
+                                     from_r0(p2.offs, 8), from_r0(p2.lens, 4), 0, d_c5.get(), d_c3.get(), d_offs.get(), d_lens.get(), &under, &over,
+                                     &max_len, nc, nullptr));
+      for (int k = 0; k < 4; k++) n_contam[k] += nc[k];
+    }
     auto tb = now();
     // ---- align (ProcCoredApprox / ProcessPairedEnds), the global stages, the SAM body on the device (k4_format_sam_dev) ----------
     k4_sam_names nm;
@@ -1160,6 +1178,18 @@ struct Run : RunHeld {
       f1.drop(u1);
       f2.drop(u2);
       if (whole) break;
+    }
+    return 0;
+  }
+
+  // -H: the four totals LoadRawReads logs behind the reads (KAligner.cpp:12392-12413), over every rank of a -G run
+  int report_contaminants() {
+    if (!o.contam_tbl) return 0;
+    if (pl) CK(k4_pipeline_contam_totals(pl, n_contam));
+    if (comm && k4_comm_allreduce_sum_u64(comm, n_contam, 4) != K4_OK) { fprintf(stderr, "k4align: rank %d: all-reduce failed: %s\n", o.rank, k4_comm_last_error(comm)); return 2; }
+    if (chatty) {
+      fprintf(stderr, "k4align: %llu 5' and %llu 3' contaminant trimmed %s reads\n", (unsigned long long)n_contam[0], (unsigned long long)n_contam[1], pe ? "PE1" : "SE");
+      if (pe) fprintf(stderr, "k4align: %llu 5' and %llu 3' contaminant trimmed PE2 reads\n", (unsigned long long)n_contam[2], (unsigned long long)n_contam[3]);
     }
     return 0;
   }
@@ -1367,6 +1397,7 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
   if (r.pipelined) {
     STEP(open_pipeline());
     STEP(feed_pipeline());
+    STEP(report_contaminants());
     auto tg = now();
     const k4_pipeline_view& v = r.v;
     STEP(global_stages(v.n_units, v.max_read_len, v.d_rr, v.d_hits, v.d_seg2, v.d_pe, v.d_reads, v.d_offs, v.d_lens));
@@ -1378,8 +1409,10 @@ static int run_rank(Opts& o, const bool pe, const int max_ml) {
     if (!o.site_file.empty()) STEP(write_site_prefs());      // -8
     STEP(format_records());
     r.s_align = secs(tg, now());
-  } else
+  } else {
     STEP(stream_batches());
+    STEP(report_contaminants());
+  }
   STEP(tally());
 #undef STEP
   return o.rank_bam ? r.write_rank_bam() : r.bam_out ? r.write_bam() : r.write_sam();
@@ -1551,6 +1584,7 @@ int main(int argc, char** argv) {
         else if (name == "snpcentroid") { o.cent_file = v; o.given += '7'; }
         else if (name == "markerlen") { o.marker_len = atoi(v.c_str()); o.given += 'K'; }
         else if (name == "markerpolythres") { o.marker_poly_thres = atof(v.c_str()); o.marker_thres_given = true; o.given += 'K'; }
+        else if (name == "contaminants") { o.contam_file = v; o.given += 'H'; }
         else if (name == "experimentid") { o.experiment_id = clean_id(v); o.given += 'w'; }
         else if (name == "readsetid") { o.readset_id = clean_id(v); o.given += 'W'; }
         else { usage(); return 1; }
@@ -1611,6 +1645,7 @@ int main(int argc, char** argv) {
       case 'j': o.none_file = val(); break;
       case 'J': o.multi_file = val(); break;
       case '#': o.sample_nth = std::min(10000, std::max(1, atoi(val().c_str()))); break;
+      case 'H': o.contam_file = val(); break;
       case 'y': o.trim5 = atoi(val().c_str()); break;
       case 'Y': o.trim3 = atoi(val().c_str()); break;
       case 'Z': o.legacy = true; break;
@@ -1823,6 +1858,18 @@ int main(int argc, char** argv) {
     if (o.pair_max < std::max(1, o.pair_min) || o.pair_max > 100000) { fprintf(stderr, "k4align: paired end apparent max length '-D%d' must be in range %d..100000\n", o.pair_max, std::max(1, o.pair_min)); return 1; }
   } else if (o.pair_max < 0) o.pair_max = 1000;
 
+  // -H: the contaminants are loaded before the index and the reads (KAligner.cpp:284-301); a file that is turned down ends the run here
+  if (!o.contam_file.empty()) {
+    char why[256];
+    const int rc = k4_load_contaminants(nullptr, o.contam_file.c_str(), &o.contam_tbl, &o.n_contam_tbl, why);
+    if (rc != K4_OK) {
+      fprintf(stderr, "k4align: %s (%d)\n", why, rc);
+      if (rc == K4_ERR_UNSUPPORTED) return 3;
+      fprintf(stderr, "k4align: Unable to load contaminate sequences file '%s'\n", o.contam_file.c_str());
+      return rc == K4_ERR_OPEN_FILE ? 2 : 1;
+    }
+    fprintf(stderr, "k4align: %d flank contaminant sequences loaded from '%s'\n", (int)o.n_contam_tbl, o.contam_file.c_str());
+  }
   if (!o.gpus.empty()) return run_multi_gpu(o, pe, max_ml);
   return run_rank(o, pe, max_ml);
 }

@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = sorted(os.path.basename(p)[6:-4] for p in glob.glob(os.path.join(GOLDEN, "align_*.npz"))
-               if not os.path.basename(p).startswith("align_ext_"))  # (the optional-phase vectors: test_*_ext.py)
+               if not os.path.basename(p).startswith(("align_ext_", "align_mt300_")))  # (the optional-phase vectors: test_*_ext.py;
+#                                                                            the 300-target index's: test_*manytargets*.py)
 
 
 @pytest.fixture(scope="module")

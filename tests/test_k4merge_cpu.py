@@ -185,3 +185,28 @@ def test_k4merge_keeps_unplaced_records_behind_and_by_nar_code(tmp_path, golden_
     assert [code(l) for l in tail] == sorted(code(l) for l in unplaced)
     # stable: within a code, the order of the single file (its shards were contiguous slices in order)
     assert tail == sorted(unplaced, key=code)
+
+
+@pytest.mark.skipif(not os.path.exists(EXE), reason="k4merge not built")
+def test_k4merge_takes_the_shards_sq_threshold(tmp_path):
+    """`k4merge -4 n`: shards declare every sequence; with more than n of them the merged header keeps those that received a
+    record in any shard, in index order (kalign's `-4` rule); without the option the threshold is kalign's default of 10 000.
+    `-t` and `-4` combine in either order."""
+    names = ["t%03d" % i for i in range(1, 13)]
+    hdr = ["@HD\tVN:1.4\tSO:coordinate"] + ["@SQ\tAS:t\tSN:%s\tLN:5000" % c for c in names] + ["@PG\tID:k4align\tVN:1.0"]
+    rec = lambda name, c, pos: "%s\t0\t%s\t%d\t254\t50M\t*\t0\t0\t%s\t*" % (name, c, pos, "A" * 50)  # noqa: E731
+    shards = []
+    for k, recs in enumerate(([rec("a", "t002", 7), rec("b", "t011", 3)], [rec("c", "t002", 5), rec("d", "t007", 9)], [])):
+        p = tmp_path / ("s%d.sam" % k)
+        p.write_text("\n".join(hdr + recs) + "\n")
+        shards.append(str(p))
+    out = tmp_path / "m.sam"
+    for args, kept in ((["-4", "11"], ["t002", "t007", "t011"]), (["-4", "12"], names), ([], names), (["-t", "2", "-4", "5"], ["t002", "t007", "t011"]),
+                       (["-4", "5", "-t", "2"], ["t002", "t007", "t011"])):
+        r = subprocess.run([EXE] + args + [str(out)] + shards, capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, r.stderr
+        got = out.read_text().splitlines()
+        assert [l.split("\tSN:")[1].split("\t")[0] for l in got if l.startswith("@SQ")] == kept, args
+        assert [l.split("\t")[0] for l in got if not l.startswith("@")] == ["c", "a", "d", "b"]
+    r = subprocess.run([EXE, "-4", "0", str(out)] + shards, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 1 and "-4" in r.stderr

@@ -11,7 +11,8 @@ from oracle_bindings import HIT_DTYPE, Oracle, Ref, ref_available
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = sorted(os.path.basename(p)[6:-4] for p in glob.glob(os.path.join(GOLDEN, "align_*.npz"))
-               if not os.path.basename(p).startswith("align_ext_"))  # (the optional-phase vectors: test_*_ext.py)
+               if not os.path.basename(p).startswith(("align_ext_", "align_mt300_")))  # (the optional-phase vectors: test_*_ext.py;
+#                                                                            the 300-target index's: test_*manytargets*.py)
 
 
 def check_against(res, exp, max_hits):

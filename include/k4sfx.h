@@ -333,6 +333,42 @@ int k4_filter_chroms_dev(k4_index* ix, const void* d_accept, int pe, int64_t n_r
  * a tally made while the reads are aligned (m_NumSloughedNs, KAligner.cpp:3732), so a PE mate that went from EN to LC is still in it. */
 int k4_filter_marked_prior(const k4_index* ix, uint64_t* prior20);
 int k4_load_loci_constraints(k4_index* ix, const char* path, k4_loci_constraint** tbl, int32_t* n, char* errbuf);
+/* ---- priority regions (`kalign -B <bed>`, `-V`; kit4b_amd/csrc/k4_priority.hip) ---------------------------------------------------
+ * k4_set_priority_regions  <- what CKAligner::Align keeps of its CBEDfile (KAligner.cpp:311-330): n_intervals features as (1-based
+ *                             entry id, start, end), 0-based INCLUSIVE loci (a BED line's end column less one), any order; they may
+ *                             overlap.  HOST arrays; the index keeps its own device copy until the next call or k4_close.
+ *                             n_intervals = 0 clears the table.  Waits for the device.  While a table is set, every
+ *                             k4_kalign_*_batch* / k4_kalign_pe_batch* call and a pipeline run CKAligner::ProcCoredApprox's priority
+ *                             pass (:9682-9770) in front of the normal call: each read is first aligned for max_ml + 10 hits without
+ *                             the microInDel / splice phases; when 1..max_ml of the hits that call reported lie in a feature
+ *                             (CBEDfile::InAnyFeature over Seg[0]'s raw MatchLoci .. MatchLoci + MatchLen - 1), the read goes on with
+ *                             that many hits -- compacted as :9732-9755 compact them, which is not stable: see k4_priority.hip --
+ *                             and with that call's LowMMCnt / NxtLowMMCnt; every other read gets the normal call.  Such a call waits for its stream (the reads that need the normal call are counted on the host),
+ *                             and pe_mode 3 / 4 (-X / -N) is turned down with K4_ERR_UNSUPPORTED.  Without a table the calls launch
+ *                             what they launched before.
+ * k4_filter_priority_regions_dev <- CKAligner::FiltByPriorityRegions (:4093-4155), which kalign runs behind FiltByChroms unless -V was
+ *                             given: an accepted read whose Seg[0] span is in no feature of its own sequence becomes
+ *                             K4_NAR_REGIONFILT with num_hits = 0 (inst stays) and the ChromID of its hit -- and of its second
+ *                             segment, d_seg2, may be NULL -- zeroed.  With no table set no sequence has a feature: every accepted
+ *                             read is marked (a BED file that names none of the index's sequences).  pe: d_rr_or_pe holds n_reads
+ *                             k4_pe_read records, read by read, else k4_read_result with hit slot 0 of d_hits.  Waits for `stream`.
+ * k4_priority_times        <- for tools/priority_bench.py: while k4_enable_kernel_timing is on, the host-clock milliseconds the calls
+ *                             spent in the wide pass, the select kernel with the listing, the normal pass with the scatter; and the
+ *                             reads that went through the wide pass / that needed the normal pass.  Reading zeroes them. */
+enum { K4_NAR_REGIONFILT = 12 /* eNARRegionFilt, KAligner.h:149 */ };
+int k4_set_priority_regions(k4_index* ix, int64_t n_intervals, const uint32_t* entry_ids, const uint32_t* starts, const uint32_t* ends);
+int k4_filter_priority_regions_dev(k4_index* ix, int pe, int64_t n_reads, int32_t max_ml, void* d_rr_or_pe, void* d_hits, void* d_seg2,
+                                   int64_t* n_removed, void* stream);
+int k4_priority_times(k4_index* ix, double ms3[3], uint64_t reads2[2]);
+/* k4_priority_select_dev   <- the walk of :9724-9763 alone, step (b) of the priority pass, over records the caller supplies: d_wide_rr /
+ *                             d_wide_hits hold n_reads results of a call with max_ml + 10 hit slots per read; reads with 1..max_ml
+ *                             priority hits get their k4_read_result (classified for pe_mode 0..2) and hits in d_out_rr / d_out_hits
+ *                             (max_ml slots per read; the slots behind the instances zeroed unless sparse_hits) and d_need[i] = 0;
+ *                             every other read gets d_need[i] = 1 (uint8), its d_out_rr record is left as it was and its hit slots
+ *                             are undefined.  Enqueues only.  A feature of no bases is given to k4_set_priority_regions as
+ *                             end = start - 1 (start >= 1) and meets a span that covers start - 1 and start, as in the reference. */
+int k4_priority_select_dev(k4_index* ix, int64_t n_reads, int32_t max_ml, int32_t pe_mode, int32_t sparse_hits, const void* d_wide_rr,
+                           const void* d_wide_hits, void* d_out_rr, void* d_out_hits, void* d_need, void* stream);
 int k4_chrom_accept_mask(k4_index* ix, int32_t n_incl, const char* const* incl, int32_t n_excl, const char* const* excl, uint8_t* mask);
 /* ---- alignment statistics (`kalign -O <file>`; kit4b_amd/csrc/k4_stats.hip) -------------------------------------------------
  * k4_align_stats_collect <- m_MultiHitDist (KAligner.cpp:9943) and m_pLenDist (:3251, :3408, :3511): on = 1 zeroes two tallies on the

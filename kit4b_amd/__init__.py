@@ -196,7 +196,7 @@ ABI_SYMBOLS = [
     "k4_pe_insert_dist_dev", "k4_free_pe_insert_dist", "k4_write_pe_insert_dist", "k4_pipeline_pe_insert_dist", "k4_pe_insert_bin_host",
     "k4_pe_insert_median_host", "k4_pba_run_dev", "k4_pba_classify_host", "k4_snp_run2_dev", "k4_marker_classify_host",
     "k4_load_contaminants", "k4_contam_match_host", "k4_contam_trims_dev", "k4_prepare_reads_contam_dev", "k4_pipeline_set_contaminants",
-    "k4_pipeline_contam_totals",
+    "k4_pipeline_contam_totals", "k4_set_priority_regions", "k4_filter_priority_regions_dev", "k4_priority_times", "k4_priority_select_dev",
 ]
 
 
@@ -294,6 +294,10 @@ def lib():
                                                  C.POINTER(C.c_int64), vp]
     L.k4_filter_chroms_dev.argtypes = [vp, vp, i32, i64, C.c_int32, vp, vp, C.POINTER(C.c_int64), vp]
     L.k4_filter_marked_prior.argtypes = [vp, C.POINTER(u64)]
+    L.k4_set_priority_regions.argtypes = [vp, i64, vp, vp, vp]
+    L.k4_filter_priority_regions_dev.argtypes = [vp, i32, i64, C.c_int32, vp, vp, vp, C.POINTER(C.c_int64), vp]
+    L.k4_priority_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64)]
+    L.k4_priority_select_dev.argtypes = [vp, i64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.k4_load_loci_constraints.argtypes = [vp, C.c_char_p, C.POINTER(C.POINTER(LociConstraint)), C.POINTER(C.c_int32), C.c_char_p]
     L.k4_chrom_accept_mask.argtypes = [vp, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), vp]
     L.k4_format_sam_ext_dev.argtypes = [vp, i32, i64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(SamNames), C.POINTER(vp),
@@ -886,6 +890,40 @@ class SfxIndex:
                                                       int(n_units), int(max_ml), ptr(d_rr), ptr(d_hits), ptr(d_seg2), ptr(d_pe), ptr(d_reads),
                                                       ptr(d_offs), ptr(d_lens), C.byref(c), stream))
         return c.value
+
+    def set_priority_regions(self, entry_ids=(), starts=(), ends=()):
+        """`kalign -B`: the features as (1-based entry id, start, end), 0-based inclusive loci; none clears the table.  While a table is
+        set, kalign_batch / kalign_pe_batch and the *_dev calls run ProcCoredApprox's priority pass (KAligner.cpp:9682-9770) first."""
+        c = np.ascontiguousarray(entry_ids, np.uint32)
+        s = np.ascontiguousarray(starts, np.uint32)
+        e = np.ascontiguousarray(ends, np.uint32)
+        assert len(c) == len(s) == len(e)
+        self._ck(lib().k4_set_priority_regions(self.h, len(c), c.ctypes.data, s.ctypes.data, e.ctypes.data))
+
+    def filter_priority_regions(self, n, max_ml, d_rr=None, d_hits=None, d_seg2=None, d_pe=None, stream=0):
+        """FiltByPriorityRegions (KAligner.cpp:4093-4155) in place over device arrays: accepted reads whose Seg[0] span is in no feature
+        of the table become NAR 12 (PR) with num_hits 0 and chrom_id 0; SE d_rr + d_hits (+ d_seg2) or PE d_pe (n records).  Returns
+        the number of reads marked."""
+        c = C.c_int64(0)
+        ptr = lambda a: None if a is None else a if isinstance(a, int) else a.data_ptr()  # noqa: E731
+        pe = d_pe is not None
+        self._ck(lib().k4_filter_priority_regions_dev(self.h, 1 if pe else 0, int(n), int(max_ml), ptr(d_pe if pe else d_rr), ptr(d_hits),
+                                                      ptr(d_seg2), C.byref(c), stream))
+        return c.value
+
+    def priority_select(self, n, max_ml, d_wide_rr, d_wide_hits, d_out_rr, d_out_hits, d_need, pe_mode=0, sparse_hits=False, stream=0):
+        """Step (b) of the priority pass alone (KAligner.cpp:9724-9763) over device tensors: the results of a call with max_ml + 10 hit
+        slots in, the settled reads' records and hits and the uint8 marks of the reads that need the normal call out.  Enqueues only."""
+        self._ck(lib().k4_priority_select_dev(self.h, int(n), int(max_ml), int(pe_mode), 1 if sparse_hits else 0, d_wide_rr.data_ptr(),
+                                              d_wide_hits.data_ptr(), d_out_rr.data_ptr(), d_out_hits.data_ptr(), d_need.data_ptr(), stream))
+
+    def priority_times(self):
+        """(ms of the wide pass, the select step, the normal pass; reads through the wide pass, reads that needed the normal pass)
+        since the last call, while kernel timing is on"""
+        ms = (C.c_double * 3)()
+        rd = (C.c_uint64 * 2)()
+        self._ck(lib().k4_priority_times(self.h, ms, rd))
+        return tuple(ms[:]), tuple(int(x) for x in rd[:])
 
     def filter_marked_prior(self):
         """uint64[20]: the reads filter_chroms / filter_loci_constraints marked on this index so far, by the NAR they carried before"""

@@ -885,8 +885,8 @@ int k4i_kalign_batch_dev(k4_index* ix, const k4_kalign_params* p, int64_t n, int
                          const void* d_offs, const void* d_lens, void* d_out, void* d_hits, void* stream, int sparse_hits) {
   return kalign_dev(ix, p, n, max_len, d_reads, d_offs, d_lens, d_out, d_hits, nullptr, stream, sparse_hits);
 }
-static int kalign_dev(k4_index* ix, const k4_kalign_params* p, int64_t n, int32_t max_len, const void* d_reads, const void* d_offs,
-                      const void* d_lens, void* d_out, void* d_hits, void* d_seg2, void* stream, int sparse_hits) {
+int k4i_kalign_core(k4_index* ix, const k4_kalign_params* p, int64_t n, int32_t max_len, const void* d_reads, const void* d_offs,
+                    const void* d_lens, void* d_out, void* d_hits, void* d_seg2, void* stream, int sparse_hits) {
   if (!ix) return K4_ERR_PARAMS;
   K4AlignArgs a;
   memset(&a, 0, sizeof(a));
@@ -898,7 +898,14 @@ static int kalign_dev(k4_index* ix, const k4_kalign_params* p, int64_t n, int32_
   a.rr = (k4_read_result*)d_out; a.hits = (k4_hit*)d_hits; a.max_hits = a.kp.max_ml;
   a.seg2 = (k4_seg2*)d_seg2;
   a.sparse_hits = sparse_hits;
-  rc = run_dev(ix, a, max_len, stream);
+  return run_dev(ix, a, max_len, stream);
+}
+static int kalign_dev(k4_index* ix, const k4_kalign_params* p, int64_t n, int32_t max_len, const void* d_reads, const void* d_offs,
+                      const void* d_lens, void* d_out, void* d_hits, void* d_seg2, void* stream, int sparse_hits) {
+  if (!ix) return K4_ERR_PARAMS;
+  // `kalign -B`: with a priority table the reads go through the wide pass first (k4_priority.hip); without one this is the call it was
+  int rc = ix->pri_n ? k4i_priority_kalign(ix, p, n, max_len, d_reads, d_offs, d_lens, d_out, d_hits, d_seg2, stream, sparse_hits)
+                     : k4i_kalign_core(ix, p, n, max_len, d_reads, d_offs, d_lens, d_out, d_hits, d_seg2, stream, sparse_hits);
   // m_MultiHitDist (KAligner.cpp:9943), only while the `-O` tallies are on.  (pe_mode 2 is also how `-r2` gets every instance
   // before one is drawn, so it is tallied; under a real eMLall the reference leaves the switch at :9913-9931 without
   // tallying -- `k4align -O -r5` is turned down)

@@ -101,6 +101,15 @@ struct k4_index {
   // `kalign -O` run tallies (k4_align_stats_collect, k4_stats.hip): K4_STATS_MULTI multihit bins, then K4_STATS_PE_LEN + 1 insert lengths;
   // empty = not collected (the align and pairing kernels then do nothing more than before)
   K4DevBuf d_run_stats;
+  // `kalign -B`: the priority regions (k4_set_priority_regions, k4_priority.hip).  pri_off[c] .. pri_off[c + 1] are the intervals of
+  // entry id c in pri_start / pri_end (sorted, disjoint, inclusive); pri_n = 0: no table, the align calls do what they did before
+  // A feature of no bases (BED start == end) is kept as the reference keeps it, End = Start - 1: it meets every span that covers both
+  // Start - 1 and Start.  Those sit apart, as sorted points: pri_pt_off[c] .. pri_pt_off[c + 1] in pri_pt.
+  K4DevBuf pri_off, pri_start, pri_end, pri_pt_off, pri_pt;
+  uint32_t pri_n = 0;    // intervals + points
+  K4DevBuf pri_scratch[10];  // the priority pass's scratch (wide records and hits, marks, list, the normal call's inputs and records): grow-only
+  double pri_ms[3] = {0, 0, 0};  // while kernel timing is on: the wide pass, the select kernel, the normal pass + scatter (host clock)
+  uint64_t pri_reads[2] = {0, 0};  // reads that went through the priority pass / that needed the normal pass behind it
   uint64_t filter_prior[20] = {0};  // reads the filter stages (k4_filter.hip) marked so far, by the NAR they carried before
   double deep_bucket_frac = 0;  // share of the suffixes that sit in k-mer buckets deeper than K4_DEEP_BUCKET (k4_index.hip)
   std::vector<k4_entry> entries;
@@ -138,6 +147,12 @@ int k4i_build_device_structures(k4_index* ix, const void* d_seq_bytes, int kmer_
 #define K4_SMALL_READS 4096
 int k4i_kalign_batch_dev(k4_index* ix, const k4_kalign_params* p, int64_t n, int32_t max_len, const void* d_reads,
                          const void* d_offs, const void* d_lens, void* d_out, void* d_hits, void* stream, int sparse_hits);
+// the body of the k4_kalign_*_batch_dev calls without a priority table: the step kernels and the general kernel over n reads
+int k4i_kalign_core(k4_index* ix, const k4_kalign_params* p, int64_t n, int32_t max_len, const void* d_reads, const void* d_offs,
+                    const void* d_lens, void* d_out, void* d_hits, void* d_seg2, void* stream, int sparse_hits);
+// k4_priority.hip: the same with a priority table set (CKAligner::ProcCoredApprox's priority pass in front of the normal one)
+int k4i_priority_kalign(k4_index* ix, const k4_kalign_params* p, int64_t n, int32_t max_len, const void* d_reads, const void* d_offs,
+                        const void* d_lens, void* d_out, void* d_hits, void* d_seg2, void* stream, int sparse_hits);
 // k4_stats.hip: the run tallies of `kalign -O` (no-ops while k4_align_stats_collect is off)
 int k4i_stats_tally_multi(k4_index* ix, const void* d_rr, int64_t n, void* stream);
 unsigned long long* k4i_stats_pe_len_dist(k4_index* ix);

@@ -51,6 +51,7 @@
 #include "../../include/k4sfx.h"
 #include "../../include/k4_bam.hpp"
 #include "k4_merge.h"
+#include "k4_priority_bed.h"
 
 namespace {
 
@@ -68,6 +69,8 @@ struct Opts {
   int primer_subs = 0;              // -6 / --pcrprimersubs <0..5>: align with -s + n, then correct 5' primer artefacts back to -s (KAlignerCL.cpp:268,803-815); 0 = off
   std::string loci_file;            // -5 / --lociconstraints <file>: loci base constraints CSV (KAlignerCL.cpp:255)
   std::vector<std::string> chrom_excl, chrom_incl;  // --chromexclude / --chromeinclude <regex>, each repeatable (kalign -Z / -z, KAlignerCL.cpp:274-275)
+  std::string priority_file;        // --priorityregionfile <bed>: kalign's -B (KAlignerCL.cpp:1095-1106; -B is the chunk size here)
+  bool no_filt_priority = false;    // -V / --nofiltpriority: FiltByPriorityRegions is left out; without a file it does nothing
   std::string stats_file;           // -O <file>: alignment statistics (KAlignerCL.cpp:256) and its two side files
   bool pe_insert_dist = false;      // -3 / --petranslendist: per-target PE insert length distributions into <-O file>.peinserts.csv (KAlignerCL.cpp:288)
   std::string site_file;            // -8 / --siteprefs <file>: start-site octamer preferences (KAlignerCL.cpp:252)
@@ -553,7 +556,7 @@ std::string clean_id(const std::string& raw) {
 void usage() {
   fprintf(stderr,
           "k4align -i reads.f[aq][.gz] [-i more ...] [-u mates ...] -I index.sfx -o out.sam|out.bam [-z bgzf level=6] [-s subs/100bp=5] [-e 1|2] [-m 0..3] [-n maxNs=1]\n"
-          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-H contaminants.fa flank contaminants trimmed off the read ends] [-Q 0|1|2 strand] [-M 0|1 all reads | -M3 --experimentid id --readsetid id: packed base alleles to -o, no SAM] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-6 pcrprimersubs 0..5] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [-O stats.csv [-3 PE insert lengths per target to stats.csv.peinserts.csv]] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv] [-7 centroids.csv] [-K markerlen 25..500 [--markerpolythres 0..0.5=0.333]]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
+          "        [-U 0..4 PE mode] [-d minins=100] [-D maxins=1000] [-E] [-l minlen=50] [-L maxlen=500] [-r 0..5] [-R maxmulti=5] [-X] [-N] [-j unaligned.fa] [-J multialigned.fa] [-# every nth read] [-4 all @SQ up to n=10000] [-y trim5] [-Y trim3] [-H contaminants.fa flank contaminants trimmed off the read ends] [-Q 0|1|2 strand] [-M 0|1 all reads | -M3 --experimentid id --readsetid id: packed base alleles to -o, no SAM] [-c minchimeric%%] [-a microindel] [-A splicejunct] [-x flankexacts] [-k pcrwin 0..250] [-6 pcrprimersubs 0..5] [-5 lociconstraints.csv] [--chromexclude regex ...] [--chromeinclude regex ...] [--priorityregionfile regions.bed [-V | --nofiltpriority]] [-O stats.csv [-3 PE insert lengths per target to stats.csv.peinserts.csv]] [-8 siteprefs.csv [-9 ofs=-4]] [-p minsnpreads [-P qvalue=0.05] [-1 nonref%%=25] [-S snps.csv] [-7 centroids.csv] [-K markerlen 25..500 [--markerpolythres 0..0.5=0.333]]] [-S i/N] [-b MB per batch] [-B MB per upload=256] [-t io threads=8] [-Z] [-g 0..3 FASTQ qualities: Sanger | Illumina 1.3+ | Solexa | ignore=3] [-@ gpu=0] [-G gpu,gpu,... one rank per GPU]\n");
 }
 
 }  // namespace
@@ -757,6 +760,30 @@ struct Run : RunHeld {
         return 1;
       }
     }
+    if (!o.priority_file.empty()) {  // the BED file's features on the index's sequences (KAligner.cpp:311-330); names the index lacks are dropped
+      std::vector<K4BedFeature> feats;
+      if (k4_read_bed_features(o.priority_file.c_str(), &feats) != 0) {
+        fprintf(stderr, "k4align: Unable to open high priority regions BED file '%s'\n", o.priority_file.c_str());
+        return 2;
+      }
+      std::unordered_map<std::string, int> names;  // lower-cased BED name -> its number; the features by that number
+      std::vector<std::vector<size_t>> feats_of;
+      for (size_t k = 0; k < feats.size(); k++) {
+        const auto it = names.emplace(k4_bed_lower(feats[k].chrom.c_str()), (int)feats_of.size());
+        if (it.second) feats_of.emplace_back();
+        feats_of[(size_t)it.first->second].push_back(k);
+      }
+      std::vector<uint32_t> ids, starts, ends;
+      for (uint32_t c = 1; c <= info.n_entries; c++) {
+        k4_entry e;
+        if (k4_get_entry(ix, c, &e) != K4_OK) continue;
+        const int q = k4_bed_locate_chrom(names, e.name);
+        if (q < 0) continue;
+        for (const size_t k : feats_of[(size_t)q]) { ids.push_back(c); starts.push_back(feats[k].start); ends.push_back(feats[k].end); }
+      }
+      CK(k4_set_priority_regions(ix, (int64_t)ids.size(), ids.data(), starts.data(), ends.data()));
+      if (chatty) fprintf(stderr, "k4align: High priority regions BED file '%s' loaded: %zu features on sequences of the index\n", o.priority_file.c_str(), ids.size());
+    }
     return 0;
   }
   // the combinations that need the run's mode, the parameters of the alignment, and which input and output path this run takes
@@ -940,6 +967,10 @@ struct Run : RunHeld {
       CK(k4_copy_to_device(ix, d_accept.get(), chrom_accept.data(), chrom_accept.size()));
       CK(k4_filter_chroms_dev(ix, d_accept.get(), pe ? 1 : 0, pe ? 2 * n : n, max_ml, pe ? d_pe : d_rr, d_hits, &cnt, nullptr));
       fprintf(stderr, "k4align: %lld matches removed by chromosome filtering\n", (long long)cnt);
+    }
+    if (!o.priority_file.empty() && !o.no_filt_priority) {  // FiltByPriorityRegions: directly behind FiltByChroms (KAligner.cpp:705)
+      CK(k4_filter_priority_regions_dev(ix, pe ? 1 : 0, pe ? 2 * n : n, max_ml, pe ? d_pe : d_rr, d_hits, pe ? nullptr : d_seg2, &cnt, nullptr));
+      fprintf(stderr, "k4align: %lld matches removed by priority region filtering\n", (long long)cnt);
     }
     return K4_OK;
   }
@@ -1571,12 +1602,14 @@ int main(int argc, char** argv) {
       case '-': {  // kalign's long names, for the options whose letters are taken here: --name value | --name=value
         std::string name = a.substr(2), v;
         const size_t eq = name.find('=');
-        if (name == "petranslendist") { o.pe_insert_dist = true; o.given += '3'; break; }  // the one long name that is a flag
+        if (name == "petranslendist") { o.pe_insert_dist = true; o.given += '3'; break; }  // the long names that are flags
+        if (name == "nofiltpriority") { o.no_filt_priority = true; break; }
         if (eq != std::string::npos) { v = name.substr(eq + 1); name.resize(eq); }
         else if (i + 1 < argc) v = argv[++i];
         else { usage(); return 1; }
         if (name == "chromexclude") o.chrom_excl.push_back(v);
         else if (name == "chromeinclude") o.chrom_incl.push_back(v);
+        else if (name == "priorityregionfile") o.priority_file = v;
         else if (name == "lociconstraints") { o.loci_file = v; o.given += '5'; }
         else if (name == "pcrprimersubs") { o.primer_subs = atoi(v.c_str()); o.given += '6'; }
         else if (name == "siteprefs") { o.site_file = v; o.given += '8'; }
@@ -1622,6 +1655,7 @@ int main(int argc, char** argv) {
       case '1': o.snp_nonref_pcnt = atof(val().c_str()); break;
       case '7': o.cent_file = val(); break;
       case 'K': o.marker_len = atoi(val().c_str()); break;
+      case 'V': o.no_filt_priority = true; break;
       case 'X': o.clamp = true; break;
       case 'N': o.best = true; break;
       case 'S': {  // "i/N": this process's slice of the reads; anything else: kalign's -S, the SNP file
@@ -1677,6 +1711,15 @@ int main(int argc, char** argv) {
   }
   if (o.in1.empty() || o.sfx.empty() || o.out.empty()) { usage(); return 1; }
   const bool pe = !o.in2.empty();
+  // --priorityregionfile (kalign -B): the priority pass needs AlignReads' own hit limit, which -X clamps and -N does not have; genpba
+  // has no such option
+  if (!o.priority_file.empty()) {
+    if (o.ml_mode == 5 && (o.clamp || o.best)) { fprintf(stderr, "k4align: priority regions '--priorityregionfile' with -r5 -X / -N are not built\n"); return 3; }
+    if (o.fmode == 3) { fprintf(stderr, "k4align: priority regions '--priorityregionfile' with packed base alleles '-M3' are not built\n"); return 3; }
+    FILE* t = fopen(o.priority_file.c_str(), "rb");
+    if (!t) { fprintf(stderr, "k4align: Unable to open high priority regions BED file '%s'\n", o.priority_file.c_str()); return 2; }
+    fclose(t);
+  }
   // -M3: `ngskit4b genpba` (kalignerPBA, KAlignerCL.cpp:1540-2290).  Its argument table (:1556-1628) is kalign's without the
   // second-segment phases, the side files and SNP calling; -w / -W are required there (arg_str1, cleaned :1697-1729)
   if (o.fmode == 3) {

@@ -25,6 +25,12 @@
 // ==== fast kernel ==================================================================================================
 // threads per block: the per-lane LDS columns of a 16-word read (257..512 bp) would leave room for one 256-thread block per CU
 #define K4_BS(nch) ((nch) >= 16 ? 128 : 256)
+// Length classes whose block keeps the per-length plan (K4ReadPlan, one 16-byte record per length 0..32*NCH) in LDS.  The 5- and
+// 8-word classes would lose a resident block per CU to the table (4 x 41.8 KB, 3 x 55.6 KB against 160 KB): their lanes evaluate
+// k4d_read_plan themselves.
+#define K4_PLAN_IN_LDS(nch) ((nch) == 4 || (nch) == 16)
+#define K4_PLAN_BYTES(nch) (K4_PLAN_IN_LDS(nch) ? (32 * (nch) + 1) * 16 : 0)
+#define K4_CIDX_BLOCKS 256  // coarse blocks of the concatenation in front of the entry search (one byte each)
 template <int NCH>
 struct K4Lane {
   const uint64_t* rd;  // LDS: word (s*NW + c) of this lane's read at rd[(s*NW + c) * K4_BS(NCH)]
@@ -32,6 +38,8 @@ struct K4Lane {
   const uint32_t* sup; // LDS (block-shared): coarse exception bitmap, K4_SUP_WORDS words
   const uint64_t* ent; // LDS (block-shared): chromosome starts [0..K4_LDS_ENTRIES) then ends, when they fit
   uint64_t* memo;      // LDS: what the offset-0 lookup of strand s found in the first phase, at memo[s * K4_BS(NCH)]
+  const uint8_t* cidx; // LDS (block-shared, beside ent): cidx[b] = last entry that starts at or before b << eshift (0 when none does)
+  uint32_t eshift;     // ... with (ix.n >> eshift) + 1 < K4_CIDX_BLOCKS
   static constexpr int NW = NCH + 1;
   K4_DEV uint64_t word(int s, int c) const { return rd[(s * NW + c) * K4_BS(NCH)]; }
   K4_DEV uint64_t chunk_at(int s, int o) const {  // 32 bases of strand s starting at base o
@@ -289,7 +297,10 @@ K4_DEV int k4d_lcm_fast(const K4AlignArgs& a, const K4Lane<NCH>& ln, int len, in
           int e;
           uint64_t e_start, e_end;
           if (ix.n_entries <= K4_LDS_ENTRIES) {  // MapChunkHit2Entry (SfxArray.cpp:2609-2654) over the LDS copy
-            int lo_e = 0, hi_e = (int)ix.n_entries - 1;
+            // the entry that holds left is the last one that starts at or before it, if any does: not before the last one that
+            // starts at or before the coarse block's first base, not behind the last one that starts at or before the next block's
+            const uint32_t cb = (uint32_t)(left >> ln.eshift);
+            int lo_e = ln.cidx[cb], hi_e = ln.cidx[cb + 1];
             e = -1; e_start = 0; e_end = 0;
             while (hi_e >= lo_e) {
               const int mid_e = (hi_e + lo_e) >> 1;
@@ -335,6 +346,39 @@ K4_DEV uint64_t k4d_rev2(uint64_t x) {
 
 // etSeqBase bytes -> this lane's LDS column: forward words [0][c], reverse-complement words [1][c], pad words zero.
 // Returns K4_RF_* flags; n_ns = number of N (the fast path cannot express N: such reads go to the general kernel).
+// The four 2-bit codes of a word already masked to 0x03030303 (first base in the low byte), as b0<<6 | b1<<4 | b2<<2 | b3
+// in the TOP byte of the result; what lies below it is of no use.  Two shift-ors: the first sets b0 beside b1 and b2 beside
+// b3 (bits 8-11 and 24-27), the second brings the first pair above the second; neither moves a set bit onto another.
+// ((d * 0x40100401u) gives the same top byte in one instruction, but a 32-bit multiply issues at a quarter of the rate of
+// v_lshl_or_b32: sixteen cycles against eight.)
+K4_DEV uint32_t k4d_squeeze4(uint32_t d) {
+  const uint32_t u = (d << 10) | d;
+  return (u << 20) | u;
+}
+
+// the exact form of packed word c of a read that holds a symbol above T: such symbols pack as 0; N (4) is counted, 5..7 flag
+// the read invalid.  src32 / sh / span as in k4d_pack_read.
+K4_DEV uint64_t k4d_pack_chunk_exact(const uint32_t* __restrict__ src32, uint32_t sh, int span, int len, int c, uint32_t& fl, uint32_t& n_ns) {
+  uint64_t acc = 0;
+  uint32_t lo = c * 32 < span ? src32[c * 8] : 0u;
+#pragma unroll
+  for (int q = 0; q < 8; q++) {
+    const int base = c * 32 + q * 4;
+    const uint32_t hi = base + 4 < span ? src32[c * 8 + q + 1] : 0u;
+    uint32_t d = __builtin_amdgcn_alignbyte(hi, lo, sh);
+    lo = hi;
+    d &= 0x07070707u;
+    if (base + 4 > len) d &= len > base ? (0xFFFFFFFFu >> (8 * (4 - (len - base)))) : 0u;  // bytes past the end
+    const uint32_t hi4 = d & 0x04040404u;  // bit 2 set => symbol >= 4
+    const uint32_t inval = hi4 & ((d << 1) | (d << 2)) & 0x04040404u;  // 5,6,7: bit2 and (bit1 or bit0)
+    if (inval) fl |= K4_RF_INVALID;
+    n_ns += __popc(hi4 & ~inval);
+    d &= ~(hi4 | (hi4 >> 1) | (hi4 >> 2));
+    acc = (acc << 8) | (k4d_squeeze4(d & 0x03030303u) >> 24);
+  }
+  return acc;
+}
+
 template <int NCH>
 K4_DEV uint32_t k4d_pack_read(const uint8_t* __restrict__ src, int len, uint64_t* col, uint32_t& n_ns) {
   constexpr int NW = NCH + 1;
@@ -346,6 +390,10 @@ K4_DEV uint32_t k4d_pack_read(const uint8_t* __restrict__ src, int len, uint64_t
   const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 3);
   const uint32_t* __restrict__ src32 = reinterpret_cast<const uint32_t*>(src - sh);
   const int span = len + (int)sh;  // bytes from src32 to the end of the read
+  // the read's end falls into one word: whole = words in front of it, tail_mask = its bytes inside the read
+  const int whole = len >> 2;
+  const uint32_t tail_mask = (len & 3) ? 0xFFFFFFFFu >> (8 * (4 - (len & 3))) : 0u;
+  uint32_t above = 0;  // bit 2 of every symbol of the read, ORed: set when any symbol is N or higher (rare: settled behind the loop)
 #pragma unroll
   for (int c = 0; c < NCH; c++) {
     uint64_t acc = 0;
@@ -362,26 +410,33 @@ K4_DEV uint32_t k4d_pack_read(const uint8_t* __restrict__ src, int len, uint64_t
           if (c * 32 + q * 4 < span) dq[q] = src32[c * 8 + q];
       }
       if (c * 32 + 32 < span) dq[8] = src32[c * 8 + 8];
+      uint32_t half[2] = {0, 0};
+      if (c * 32 + 32 <= len) {  // every word inside the read: no end mask
 #pragma unroll
-      for (int q = 0; q < 8; q++) {
-        const int base = c * 32 + q * 4;
-        uint32_t d = __builtin_amdgcn_alignbyte(dq[q + 1], dq[q], sh);
-        d &= 0x07070707u;
-        if (base + 4 > len) d &= len > base ? (0xFFFFFFFFu >> (8 * (4 - (len - base)))) : 0u;  // bytes past the end
-        // N / invalid detection on the four bytes at once: bit 2 set => symbol >= 4
-        const uint32_t hi4 = d & 0x04040404u;
-        if (hi4) {
-          const uint32_t inval = hi4 & ((d << 1) | (d << 2)) & 0x04040404u;  // 5,6,7: bit2 and (bit1 or bit0)
-          if (inval) fl |= K4_RF_INVALID;
-          n_ns += __popc(hi4 & ~inval);
-          d &= ~(hi4 | (hi4 >> 1) | (hi4 >> 2));  // such symbols pack as 0
+        for (int q = 0; q < 8; q++) {
+          const uint32_t d = __builtin_amdgcn_alignbyte(dq[q + 1], dq[q], sh);
+          above |= d & 0x04040404u;
+          half[q >> 2] = __builtin_amdgcn_alignbit(half[q >> 2], k4d_squeeze4(d & 0x03030303u), 24);
         }
-        acc = (acc << 8) | ((d & 3) << 6) | (((d >> 8) & 3) << 4) | (((d >> 16) & 3) << 2) | ((d >> 24) & 3);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+          const int w = c * 8 + q;
+          uint32_t d = __builtin_amdgcn_alignbyte(dq[q + 1], dq[q], sh);
+          d &= w < whole ? 0xFFFFFFFFu : w == whole ? tail_mask : 0u;  // bytes past the end
+          above |= d & 0x04040404u;
+          half[q >> 2] = __builtin_amdgcn_alignbit(half[q >> 2], k4d_squeeze4(d & 0x03030303u), 24);
+        }
       }
+      acc = ((uint64_t)half[0] << 32) | half[1];
     }
     col[c * K4_BS(NCH)] = acc;
   }
   col[NCH * K4_BS(NCH)] = 0;
+  if (above) {  // a second pass with the exact classification (the loop above packed 5, 6, 7 as 1, 2, 3)
+#pragma unroll 1
+    for (int c = 0; 32 * c < len; c++) col[c * K4_BS(NCH)] = k4d_pack_chunk_exact(src32, sh, span, len, c, fl, n_ns);
+  }
   if (n_ns) fl |= K4_RF_HAS_N;
   // reverse complement from the stored forward words: rc bases [32c, 32c+32) = complement of forward bases
   // [len-32(c+1), len-32c) in reverse order
@@ -422,15 +477,34 @@ __global__ void __launch_bounds__(K4_BS(NCH), (NCH >= 16 ? K4_STEP_WAVES_LONG : 
   ln.memo = lds + 2 * NW * K4_BS(NCH) + (K4_DEDUP_CAP * K4_BS(NCH)) / 2 + tid;
   uint64_t* ent_l = lds + 2 * NW * K4_BS(NCH) + (K4_DEDUP_CAP * K4_BS(NCH)) / 2 + 2 * K4_BS(NCH);
   uint32_t* sup_l = reinterpret_cast<uint32_t*>(ent_l + 2 * K4_LDS_ENTRIES);
+  uint4* plan_l = reinterpret_cast<uint4*>(sup_l + K4_SUP_WORDS + 4);  // (16-byte aligned: every part in front is a multiple of 16 bytes)
+  uint8_t* cidx_l = reinterpret_cast<uint8_t*>(sup_l + K4_SUP_WORDS + 4) + K4_PLAN_BYTES(NCH);
   ln.ent = ent_l;
   ln.sup = sup_l;
+  ln.cidx = cidx_l;
+  ln.eshift = 0;
+  while ((a.ix.n >> ln.eshift) + 1 >= K4_CIDX_BLOCKS) ln.eshift++;
   for (int q = tid; q < K4_SUP_WORDS; q += K4_BS(NCH)) sup_l[q] = a.ix.excsup[q];
   if (a.ix.n_entries <= K4_LDS_ENTRIES)
     for (int q = tid; q < (int)a.ix.n_entries; q += K4_BS(NCH)) {
       ent_l[q] = a.ix.ent_start[q];
       ent_l[K4_LDS_ENTRIES + q] = a.ix.ent_end[q];
     }
+  if (K4_PLAN_IN_LDS(NCH))  // the plan of every length a lane of this class can hold
+    for (int q = tid; q <= 32 * NCH; q += K4_BS(NCH)) plan_l[q] = k4d_plan_pack(k4d_read_plan(a, q, step));
   __syncthreads();
+  if (a.ix.n_entries <= K4_LDS_ENTRIES) {  // coarse starts for the entry search, from the table just copied
+    for (int q = tid; q < K4_CIDX_BLOCKS; q += K4_BS(NCH)) {
+      const uint64_t t = (uint64_t)q << ln.eshift;
+      int lo_e = 0, hi_e = (int)a.ix.n_entries;  // number of entries that start at or before t
+      while (lo_e < hi_e) {
+        const int mid_e = (lo_e + hi_e) >> 1;
+        if (ent_l[mid_e] <= t) lo_e = mid_e + 1; else hi_e = mid_e;
+      }
+      cidx_l[q] = (uint8_t)(lo_e > 0 ? lo_e - 1 : 0);
+    }
+    __syncthreads();
+  }
   uint64_t* col = lds + tid;
   uint32_t n_lookup = 0, n_probe = 0, n_cand = 0, n_slow = 0, n_bases = 0, n_done = 0;
   const int64_t count = (FIRST && !(DEFER && in_ids != nullptr)) ? a.n_reads : (int64_t)*in_count;
@@ -455,7 +529,12 @@ __global__ void __launch_bounds__(K4_BS(NCH), (NCH >= 16 ? K4_STEP_WAVES_LONG : 
     int ext_from = -1;  // >= 0: every standard phase ran here without a result; the general kernel starts at the optional ones
     if (active) {
       const int len = (int)a.lens[i];
-      const K4ReadParams rp = k4d_read_params(a, len);
+      // the read's plan: one LDS load by length (a length outside 1..32*NCH takes the K4_RF_TOOLONG path below and has no use
+      // for a plan: it reads record 0), or the same function per lane
+      uint4 pr;
+      if (K4_PLAN_IN_LDS(NCH)) pr = plan_l[(len >= 1 && len <= 32 * NCH) ? len : 0];
+      else pr = k4d_plan_pack(k4d_read_plan(a, len, step));
+      const K4ReadParams rp = k4d_plan_params(a, pr);
       bool skip = false;
       if (FIRST) {
         if (!from_list) {  // (a read taken from the deferred list was counted when it was set aside)
@@ -507,18 +586,11 @@ __global__ void __launch_bounds__(K4_BS(NCH), (NCH >= 16 ? K4_STEP_WAVES_LONG : 
         col[NCH * K4_BS(NCH)] = 0;
         col[(NW + NCH) * K4_BS(NCH)] = 0;
       }
-      if (!skip && (rp.core_len < 1 || rp.max_hits < 1 || rp.max_hits > a.max_hits)) slow = true;  // the general kernel reports it
+      if (!skip && ((pr.w & K4_PLAN_NO_CORE) || rp.max_hits < 1 || rp.max_hits > a.max_hits)) slow = true;  // the general kernel reports it
       if (!skip && !slow) {
-        // which AlignReads phase is this read's step-th?  (SfxArray.cpp:7867-7891)
-        int n_esc = 0;
-        if (rp.tot_mm > 0)
-          for (; n_esc <= rp.tot_mm; n_esc++)
-            if (len / (n_esc + rp.mm_delta) <= rp.core_len) break;
-        const bool has_final = rp.tot_mm > 0 ? n_esc <= rp.tot_mm : true;
-        const int n_phases = n_esc + (has_final ? 1 : 0);
-        int allow, cl, delta;
-        if (step < n_esc) { allow = step; cl = len / (step + rp.mm_delta); delta = cl; }
-        else { allow = rp.tot_mm; cl = rp.core_len; delta = rp.core_delta; }
+        // which AlignReads phase is this read's step-th: k4d_read_plan
+        const int n_phases = (int)((pr.w >> 8) & 0xFF);
+        const int allow = (int)(pr.w & 0xFF), cl = (int)pr.x, delta = (int)pr.y;
         k4_hit* hits = a.hits + i * a.max_hits;
         int inst = 0, low = 0, nxt = 0;
         const uint32_t c0 = n_lookup, c1 = n_probe, c2 = n_cand;
@@ -688,7 +760,7 @@ static int launch_steps(k4_index* ix, K4AlignArgs& a, int n_steps, hipStream_t s
   uint64_t* const rows[2] = {w.rows[0].as<uint64_t>(), w.rows[1].as<uint64_t>()};
   uint32_t* const ctl = w.ctl.as<uint32_t>();
   const size_t lds = (size_t)2 * (NCH + 1) * K4_BS(NCH) * 8 + (size_t)K4_DEDUP_CAP * K4_BS(NCH) * 4 + (size_t)2 * K4_BS(NCH) * 8 + (size_t)2 * K4_LDS_ENTRIES * 8 +
-                     (size_t)K4_SUP_WORDS * 4 + 16;
+                     (size_t)K4_SUP_WORDS * 4 + 16 + (size_t)K4_PLAN_BYTES(NCH) + K4_CIDX_BLOCKS;
   if (lds > 48 * 1024) {
     K4_HIP(ix, hipFuncSetAttribute((const void*)k4k_align_step<EL, NCH, true, KT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     K4_HIP(ix, hipFuncSetAttribute((const void*)k4k_align_step<EL, NCH, true, KT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -134,6 +134,54 @@ K4_DEV K4ReadParams k4d_read_params(const K4AlignArgs& a, int len) {
   return p;
 }
 
+// What a step kernel needs of a read that depends on nothing but the read's length (and the launch's step): the
+// length-dependent K4ReadParams fields and this step's place in the AlignReads phase escalation, SfxArray.cpp:7867-7891.
+// The single definition: the step kernels evaluate it once per length and block into an LDS table (K4_PLAN_IN_LDS) or, in the
+// length classes whose LDS has no room for the table, per lane.
+struct K4ReadPlan {
+  int tot_mm, core_len, core_delta, max_slides;
+  int n_phases;          // phases this read can run: the escalation phases plus the final one where there is one
+  int allow, cl, delta;  // this step's MaxTotMM, CoreLen and CoreDelta
+};
+K4_DEV K4ReadPlan k4d_read_plan(const K4AlignArgs& a, int len, int step) {
+  const K4ReadParams rp = k4d_read_params(a, len);
+  K4ReadPlan pl;
+  pl.tot_mm = rp.tot_mm; pl.core_len = rp.core_len; pl.core_delta = rp.core_delta; pl.max_slides = rp.max_slides;
+  int n_esc = 0;
+  if (rp.tot_mm > 0)
+    for (; n_esc <= rp.tot_mm; n_esc++)
+      if (len / (n_esc + rp.mm_delta) <= rp.core_len) break;
+  const bool has_final = rp.tot_mm > 0 ? n_esc <= rp.tot_mm : true;
+  pl.n_phases = n_esc + (has_final ? 1 : 0);
+  if (step < n_esc) { pl.allow = step; pl.cl = len / (step + rp.mm_delta); pl.delta = pl.cl; }
+  else { pl.allow = rp.tot_mm; pl.cl = rp.core_len; pl.delta = rp.core_delta; }
+  return pl;
+}
+// The plan as the 16-byte record of the LDS table: {cl, delta, max_slides, allow | n_phases << 8 | tot_mm << 16 | no core << 24}
+// (TotMM is at most 63 in either mode, so a read has at most 65 phases).  The final phase's core_len / core_delta are this
+// step's cl / delta when the step is that phase and have no reader otherwise: only "core_len < 1" is kept of them.
+#define K4_PLAN_NO_CORE (1u << 24)
+K4_DEV uint4 k4d_plan_pack(const K4ReadPlan& pl) {
+  return make_uint4((uint32_t)pl.cl, (uint32_t)pl.delta, (uint32_t)pl.max_slides,
+                    (uint32_t)pl.allow | ((uint32_t)pl.n_phases << 8) | ((uint32_t)pl.tot_mm << 16) | (pl.core_len < 1 ? K4_PLAN_NO_CORE : 0u));
+}
+// the K4ReadParams of a step kernel's read: the fields that do not depend on the length from the (scalar) kernel arguments,
+// the others from the plan record -- core_len / core_delta are this step's, which is what k4d_lcm_fast is given beside them
+K4_DEV K4ReadParams k4d_plan_params(const K4AlignArgs& a, const uint4& pr) {
+  K4ReadParams p;
+  p.tot_mm = (int)((pr.w >> 16) & 0xFF); p.core_len = (int)pr.x; p.core_delta = (int)pr.y; p.max_slides = (int)pr.z;
+  if (a.mode == 0) {
+    p.mm_delta = a.ap.mm_delta; p.strand = a.ap.strand; p.max_hits = a.ap.max_hits;
+    p.min_core_len = a.ap.min_core_len; p.min_chimeric_len = a.ap.min_chimeric_len;
+    p.micro_indel_len = a.ap.micro_indel_len; p.max_splice_junct_len = a.ap.max_splice_junct_len;
+  } else {
+    p.mm_delta = a.kp.min_edit_dist; p.strand = a.kp.strand; p.max_hits = a.kp.max_ml < 1 ? 1 : a.kp.max_ml;
+    p.min_core_len = a.kp.min_core_len; p.min_chimeric_len = a.kp.min_chimeric_len;
+    p.micro_indel_len = a.kp.micro_indel_len; p.max_splice_junct_len = a.kp.max_splice_junct_len;
+  }
+  return p;
+}
+
 K4_DEV void k4d_store_hit(k4_hit* h, uint32_t chrom_id, uint32_t loci, int len, char strand, int mm, uint32_t ext = 0) {
   uint4 v;
   v.x = chrom_id;

@@ -69,8 +69,28 @@ typedef struct TAG_sIdentNode {  // libkit4b/SfxArray.h:144-147 (caller scratch;
   uint32_t TargSeqID;
   struct TAG_sIdentNode* pNxt;
 } tsIdentNode;
+#pragma pack(1)
+typedef struct TAG_sQueryAlignNodes {  // libkit4b/SfxArray.h:149-165 (41 bytes)
+  uint32_t AlignNodeID;
+  uint8_t FlgStrand : 1;
+  uint8_t FlgFirst2tRpt : 1;
+  uint8_t Flg2Rpt : 1;
+  uint8_t FlgScored : 1;
+  uint8_t FlgRedundant : 1;
+  int32_t QueryID;
+  uint32_t QueryStartOfs;
+  uint32_t AlignLen;
+  uint32_t TargSeqID;
+  uint32_t TargSeqLoci;
+  uint32_t NumMismatches;
+  int32_t HiScore;
+  uint32_t HiScorePathNextIdx;
+  uint32_t NxtHashMatch;
+} tsQueryAlignNodes;
+#pragma pack()
 #endif  // K4_HAVE_KIT4B_TYPES
 static_assert(sizeof(tsSegLoci) == 23 && sizeof(tsHitLoci) == 50 && sizeof(tsSfxHeaderV3) == 1224, "layouts must match libkit4b");
+static_assert(sizeof(tsQueryAlignNodes) == 41, "layouts must match libkit4b");
 
 class CSfxArray {
   k4_index* m_pIdx;
@@ -90,13 +110,42 @@ class CSfxArray {
     std::vector<k4_hit> hits;
     k4_seg2 seg2;  // the second segment of a microInDel / splice-junction hit (slot 0)
     bool done;
+    // a LocateQuerySeqs call travels the same way: qp instead of p, nodes instead of hits
+    bool query = false;
+    k4_query_params qp;
+    std::vector<k4_query_node> nodes;
   };
   std::mutex m_QMtx;
   std::condition_variable m_QCv;
   std::vector<Req*> m_Pending;
   bool m_LeaderActive = false;
 
+  void RunQueryGroup(std::vector<Req*>& g) {  // same parameters: one k4_locate_query_seqs_batch
+    const size_t n = g.size();
+    std::vector<uint8_t> cat;
+    std::vector<uint64_t> offs(n), node_offs(n + 1, 0);
+    std::vector<uint32_t> lens(n);
+    for (size_t i = 0; i < n; i++) {
+      offs[i] = cat.size();
+      lens[i] = g[i]->len;
+      cat.insert(cat.end(), g[i]->probe, g[i]->probe + g[i]->len);
+    }
+    cat.resize(cat.size() + 16);
+    std::vector<k4_query_node> nodes(n * (size_t)g[0]->qp.max_hits);  // (a query returns at most max_hits nodes)
+    int rc;
+    {
+      std::lock_guard<std::mutex> dev(m_Mtx);
+      rc = k4_locate_query_seqs_batch(m_pIdx, &g[0]->qp, (int64_t)n, cat.data(), offs.data(), lens.data(), node_offs.data(), nodes.data(),
+                                      (uint64_t)nodes.size());
+      if (rc != K4_OK) Fail(rc);
+    }
+    for (size_t i = 0; i < n; i++) {
+      g[i]->rc = rc;
+      if (rc == K4_OK) g[i]->nodes.assign(nodes.begin() + (ptrdiff_t)node_offs[i], nodes.begin() + (ptrdiff_t)node_offs[i + 1]);
+    }
+  }
   void RunGroup(std::vector<Req*>& g) {  // same parameters: one k4_align_reads_batch
+    if (g[0]->query) { RunQueryGroup(g); return; }
     const size_t n = g.size();
     std::vector<uint8_t> cat;
     std::vector<uint64_t> offs(n);
@@ -142,7 +191,12 @@ class CSfxArray {
         if (taken[i]) continue;
         std::vector<Req*> g;
         for (size_t j = i; j < batch.size(); j++)
-          if (!taken[j] && std::memcmp(&batch[j]->p, &batch[i]->p, sizeof(k4_align_params)) == 0) { g.push_back(batch[j]); taken[j] = 1; }
+          if (!taken[j] && batch[j]->query == batch[i]->query &&
+              (batch[i]->query ? std::memcmp(&batch[j]->qp, &batch[i]->qp, sizeof(k4_query_params))
+                               : std::memcmp(&batch[j]->p, &batch[i]->p, sizeof(k4_align_params))) == 0) {
+            g.push_back(batch[j]);
+            taken[j] = 1;
+          }
         RunGroup(g);
       }
       lk.lock();
@@ -152,6 +206,7 @@ class CSfxArray {
     }
   }
 
+  int m_OccKMerLen = 0, m_MaxKMerOccs = 0;  // InitOverOccKMers
   std::vector<uint16_t> m_IdentFlags;  // per entry, the flags half of tsSfxEntry.fBlockID (SfxArray.cpp:2048-2079)
 
   bool LoadIdentFlags() {
@@ -362,6 +417,51 @@ class CSfxArray {
     if (pHitInstances) *pHitInstances = inst;
     for (int i = 0; i < inst && i < MaxHits; i++) Expand(hits[(size_t)i], &pHits[i]);
     return rslt;
+  }
+
+  // CSfxArray::InitOverOccKMers, SfxArray.h:559-561.  The reference caches, per k-mer of KMerLen bases, whether it occurs 0,
+  // 1..MaxKMerOccs or more times, and LocateQuerySeqs skips a core of that length unless it is in the middle class.  Here no
+  // cache is built: for such calls the depth becomes min(CurMaxIter, MaxKMerOccs + 1), which skips the same ACGT cores.  A core
+  // that holds N is counted as it is (the reference's cache indexes N as A, and what it answers depends on which thread
+  // touched the k-mer first).
+  int InitOverOccKMers(int KMerLen, int MaxKMerOccs) {
+    if (!m_pIdx) return K4_ERR_INTERNAL;
+    if (KMerLen < 1 || MaxKMerOccs < 1) { m_OccKMerLen = m_MaxKMerOccs = 0; return K4_ERR_PARAMS; }
+    m_OccKMerLen = KMerLen; m_MaxKMerOccs = MaxKMerOccs;
+    return 0;
+  }
+
+  // CSfxArray::LocateQuerySeqs, SfxArray.h:779-790 -- identical parameter list (CBlitz's engine call, Blitz.cpp).  Returns the
+  // number of nodes left in pHits[0 ..]; AlignNodeID, QueryID and the cleared flags / scores as the reference leaves them,
+  // NxtHashMatch 0 (the reference leaves the chain links of before its compaction there).  Concurrent calls share a device batch.
+  int LocateQuerySeqs(uint32_t QuerySeqID, etSeqBase* pProbeSeq, uint32_t ProbeLen, uint32_t CoreLen, uint32_t CoreDelta,
+                      eALStrand Align2Strand, uint32_t MaxHits, tsQueryAlignNodes* pHits, uint32_t CurMaxIter, int BaseMatchPts,
+                      int BaseMismatchPts) {
+    if (!m_pIdx) return K4_ERR_INTERNAL;
+    if (!pProbeSeq || !pHits || MaxHits > 0x7fffffffu || CoreLen > 0x7fffffffu || CoreDelta > 0x7fffffffu) return K4_ERR_PARAMS;
+    uint32_t Depth = CurMaxIter > 0x7fffffffu ? 0x7fffffffu : CurMaxIter;
+    if (m_OccKMerLen > 0 && CoreLen == (uint32_t)m_OccKMerLen && Depth > (uint32_t)m_MaxKMerOccs + 1) Depth = (uint32_t)m_MaxKMerOccs + 1;
+    Req rq;
+    std::memset(&rq.p, 0, sizeof(rq.p));
+    std::memset(&rq.seg2, 0, sizeof(rq.seg2));
+    rq.query = true;
+    rq.qp = k4_query_params{(int32_t)CoreLen, (int32_t)CoreDelta, (int32_t)Align2Strand, (int32_t)MaxHits, (int32_t)Depth, BaseMatchPts,
+                            BaseMismatchPts};
+    rq.probe = pProbeSeq; rq.len = ProbeLen;
+    rq.rslt = rq.inst = rq.low = rq.nxt = 0; rq.rc = K4_OK; rq.done = false;
+    Submit(rq);
+    if (rq.rc != K4_OK) return rq.rc;
+    for (size_t i = 0; i < rq.nodes.size(); i++) {
+      const k4_query_node& n = rq.nodes[i];
+      tsQueryAlignNodes* h = &pHits[i];
+      std::memset(h, 0, sizeof(*h));  // the flags, HiScore, HiScorePathNextIdx, NxtHashMatch
+      h->AlignNodeID = n.slot;
+      h->FlgStrand = n.strand ? 1 : 0;
+      h->QueryID = (int32_t)QuerySeqID;
+      h->QueryStartOfs = n.query_start; h->AlignLen = n.align_len;
+      h->TargSeqID = n.targ_seq_id; h->TargSeqLoci = n.targ_loci; h->NumMismatches = n.n_mismatches;
+    }
+    return (int)rq.nodes.size();
   }
 
   // CSfxArray::AlignPairedRead, SfxArray.h:880-896 -- identical parameter list (CKAligner's mate rescue,

@@ -481,6 +481,43 @@ int k4_best_matches_batch_dev(k4_index* ix, const k4_align_params* p, int64_t n_
                               const void* d_reads, const void* d_offs, const void* d_lens, void* d_rslt, void* d_inst,
                               void* d_hits, void* stream);
 
+/* ---- blitz: seed and extend ----------------------------------------------------------------------------------
+ * k4_locate_query_seqs_batch <- CSfxArray::LocateQuerySeqs (SfxArray.h:779, SfxArray.cpp:6493-6833; CBlitz's engine call) for
+ * n_queries sequences of codes 0..4: exact cores of core_len bases every core_delta bases, each occurrence of a core that
+ * occurs fewer than max_iter times extended 5' and 3' (match_pts / mismatch_pts, 15 % mismatch cap) unless an earlier node of
+ * the same target holds it on its diagonal, overlapping nodes reduced by the reference's redundancy rules, at most max_hits
+ * nodes.  strand: 0 both ('+' first), 1 '+', 2 '-' ('-' nodes are in the coordinates of the reverse-complemented query).
+ * Output: the nodes of query i are nodes[node_offs[i] .. node_offs[i + 1]), in the reference's order; slot = the reference's
+ * AlignNodeID.  When the total exceeds nodes_cap the call returns K4_ERR_MEM, node_offs is complete (node_offs[n_queries] =
+ * the capacity needed) and nodes is not written.  max_iter is the call's CurMaxIter, not the index's MaxIter.
+ * k4_query_reserve sizes the per-query node slices of the workspace ahead of time (the batch calls grow it when needed; the
+ * index owns it, k4_close frees it).  k4_query_last_kernel_ms: device time of the last batch's kernels. */
+typedef struct {
+  int32_t core_len;     /* 8..100 */
+  int32_t core_delta;   /* >= 1 */
+  int32_t strand;
+  int32_t max_hits;     /* >= 1 */
+  int32_t max_iter;
+  int32_t match_pts;
+  int32_t mismatch_pts;
+} k4_query_params;
+typedef struct {
+  uint32_t query_start;
+  uint32_t align_len;
+  uint32_t targ_seq_id;
+  uint32_t targ_loci;
+  uint32_t n_mismatches;
+  uint32_t slot;
+  uint32_t strand;      /* 0 '+', 1 '-' */
+} k4_query_node;
+int k4_query_reserve(k4_index* ix, const k4_query_params* p, int64_t max_queries, uint32_t max_query_len);
+int k4_locate_query_seqs_batch(k4_index* ix, const k4_query_params* p, int64_t n_queries, const uint8_t* seqs, const uint64_t* offs,
+                               const uint32_t* lens, uint64_t* node_offs, k4_query_node* nodes, uint64_t nodes_cap);
+int k4_locate_query_seqs_batch_dev(k4_index* ix, const k4_query_params* p, int64_t n_queries, uint32_t max_query_len,
+                                   const void* d_seqs, const void* d_offs, const void* d_lens, void* d_node_offs, void* d_nodes,
+                                   uint64_t nodes_cap, void* stream);
+double k4_query_last_kernel_ms(const k4_index* ix);
+
 /* ---- paired ends -----------------------------------------------------------------------------------------
  * k4_mate_rescue_batch <- CSfxArray::AlignPairedRead (SfxArray.h:880, SfxArray.cpp:8571-8767; MinChimericLen 0, insert
  *                         window < 1000 => the linear-scan branch :8731-8766 with AdaptiveTrim's full-length rule :5612-5638)

@@ -197,7 +197,15 @@ ABI_SYMBOLS = [
     "k4_pe_insert_median_host", "k4_pba_run_dev", "k4_pba_classify_host", "k4_snp_run2_dev", "k4_marker_classify_host",
     "k4_load_contaminants", "k4_contam_match_host", "k4_contam_trims_dev", "k4_prepare_reads_contam_dev", "k4_pipeline_set_contaminants",
     "k4_pipeline_contam_totals", "k4_set_priority_regions", "k4_filter_priority_regions_dev", "k4_priority_times", "k4_priority_select_dev",
+    "k4_query_reserve", "k4_locate_query_seqs_batch", "k4_locate_query_seqs_batch_dev", "k4_query_last_kernel_ms",
 ]
+
+
+class QueryParams(C.Structure):  # k4_query_params
+    _fields_ = [(n, C.c_int32) for n in ("core_len", "core_delta", "strand", "max_hits", "max_iter", "match_pts", "mismatch_pts")]
+
+
+QUERY_NODE_DTYPE = np.dtype([(n, "<u4") for n in ("query_start", "align_len", "targ_seq_id", "targ_loci", "n_mismatches", "slot", "strand")])  # k4_query_node
 
 
 def build(verbose=False):
@@ -362,6 +370,11 @@ def lib():
     L.k4_abi_version.argtypes = []
     L.k4_global_error.argtypes = []
     L.k4_get_kernel_times_split.argtypes = [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(C.c_int32)]
+    L.k4_query_reserve.argtypes = [vp, C.POINTER(QueryParams), i64, u32]
+    L.k4_locate_query_seqs_batch.argtypes = [vp, C.POINTER(QueryParams), i64, vp, vp, vp, vp, vp, u64]
+    L.k4_locate_query_seqs_batch_dev.argtypes = [vp, C.POINTER(QueryParams), i64, u32, vp, vp, vp, vp, vp, u64, vp]
+    L.k4_query_last_kernel_ms.argtypes = [vp]
+    L.k4_query_last_kernel_ms.restype = dbl
     _lib = L
     return L
 
@@ -577,6 +590,34 @@ class SfxIndex:
         self._ck(lib().k4_best_matches_batch(self.h, C.byref(p), n, cat.ctypes.data, offs.ctypes.data, lens.ctypes.data,
                                              rslt.ctypes.data, inst.ctypes.data, hits.ctypes.data))
         return dict(rslt=rslt, inst=inst, hits=hits)
+
+    def locate_query_seqs(self, queries, core_len=20, core_delta=10, strand=STRAND_BOTH, max_hits=1000, max_iter=100, match_pts=1,
+                          mismatch_pts=3, nodes_cap=None):
+        """CSfxArray::LocateQuerySeqs (libkit4b/SfxArray.h:779) for a batch of query sequences: per query a QUERY_NODE_DTYPE array of
+        its nodes in the reference's order.  nodes_cap: capacity of the output (default: grown until everything fits); when it is
+        given and too small the K4Error (code -95) carries the capacity needed as `.needed`."""
+        cat, offs, lens = _flatten(queries)
+        n = len(lens)
+        p = QueryParams(core_len, core_delta, strand, max_hits, max_iter, match_pts, mismatch_pts)
+        node_offs = np.zeros(n + 1, dtype=np.uint64)
+        cap = max(1, 4 * n) if nodes_cap is None else int(nodes_cap)
+        while True:
+            nodes = np.zeros(max(cap, 1), dtype=QUERY_NODE_DTYPE)
+            rc = lib().k4_locate_query_seqs_batch(self.h, C.byref(p), n, cat.ctypes.data, offs.ctypes.data, lens.ctypes.data,
+                                                  node_offs.ctypes.data, nodes.ctypes.data, cap)
+            if rc == -95 and int(node_offs[n]) > cap:
+                if nodes_cap is None:
+                    cap = int(node_offs[n])
+                    continue
+                e = K4Error(rc, lib().k4_last_error(self.h).decode())
+                e.needed = int(node_offs[n])
+                raise e
+            self._ck(rc)
+            return [nodes[int(node_offs[i]):int(node_offs[i + 1])].copy() for i in range(n)]
+
+    def query_kernel_ms(self):
+        """device milliseconds of the last locate_query_seqs batch (its three kernels)"""
+        return lib().k4_query_last_kernel_ms(self.h)
 
     def kalign_batch(self, reads, max_subs=5, min_edit_dist=1, max_ns=1, pmode=0, strand=STRAND_BOTH, max_ml=1,
                      pe_mode=0, min_core_len=0, max_num_slides=0):

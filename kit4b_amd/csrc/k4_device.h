@@ -229,6 +229,28 @@ K4_DEV int k4d_map_entry(const K4DevIndex& ix, uint64_t ofs) {
   return -1;
 }
 
+// MapChunkHit2Entry (libkit4b/SfxArray.cpp:2609-2654) over the LDS copy of the entry table when there is one (starts, then ends
+// at + K4_LDS_ENTRIES): the general kernel's and the query kernel's lookup
+K4_DEV int k4d_map_entry_slow(const K4DevIndex& ix, const uint64_t* ent_lds, uint64_t ofs, uint64_t& e_start, uint64_t& e_end) {
+  if (!ent_lds) {
+    const int e = k4d_map_entry(ix, ofs);
+    e_start = e >= 0 ? ix.ent_start[e] : 0;
+    e_end = e >= 0 ? ix.ent_end[e] : 0;
+    return e;
+  }
+  int lo = 0, hi = (int)ix.n_entries - 1;
+  while (hi >= lo) {
+    const int mid = (hi + lo) >> 1;
+    const uint64_t s = ent_lds[mid];
+    if (s > ofs) { hi = mid - 1; continue; }
+    const uint64_t ev = ent_lds[K4_LDS_ENTRIES + mid];
+    if (ev >= ofs) { e_start = s; e_end = ev; return mid; }
+    lo = mid + 1;
+  }
+  e_start = e_end = 0;
+  return -1;
+}
+
 // mask of the bases [lo, hi) of a 32-base MSB-first chunk (0 <= lo, hi <= 32)
 K4_DEV uint64_t k4d_range_mask(int lo, int hi) {
   if (lo < 0) lo = 0;

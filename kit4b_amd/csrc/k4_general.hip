@@ -216,27 +216,6 @@ K4_DEV void k4d_lane_range(const K4DevIndex& ix, const uint8_t* probe, int jlo, 
   }
 }
 
-// MapChunkHit2Entry (libkit4b/SfxArray.cpp:2609-2654) over the LDS copy of the entry table when there is one
-K4_DEV int k4d_map_entry_slow(const K4DevIndex& ix, const uint64_t* ent_lds, uint64_t ofs, uint64_t& e_start, uint64_t& e_end) {
-  if (!ent_lds) {
-    const int e = k4d_map_entry(ix, ofs);
-    e_start = e >= 0 ? ix.ent_start[e] : 0;
-    e_end = e >= 0 ? ix.ent_end[e] : 0;
-    return e;
-  }
-  int lo = 0, hi = (int)ix.n_entries - 1;
-  while (hi >= lo) {
-    const int mid = (hi + lo) >> 1;
-    const uint64_t s = ent_lds[mid];
-    if (s > ofs) { hi = mid - 1; continue; }
-    const uint64_t ev = ent_lds[K4_LDS_ENTRIES + mid];
-    if (ev >= ofs) { e_start = s; e_end = ev; return mid; }
-    lo = mid + 1;
-  }
-  e_start = e_end = 0;
-  return -1;
-}
-
 // probe bytes -> sc.pk (call after every change of sc.probe); sc.packed = no symbol above T
 K4_DEV void k4d_pack_probe_wave(K4Slow& sc, int len) {
   const int nw = (len + 31) >> 5;

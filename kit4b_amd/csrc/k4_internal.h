@@ -126,6 +126,14 @@ struct k4_index {
   int32_t pe_cap_hits = 0;
   // staging of k4_mate_rescue_batch (grow-only)
   K4DevBuf rs_tasks, rs_reads, rs_res, rs_hits;
+  // LocateQuerySeqs (k4_query.hip): per-query node slices and counts (qry_cap_queries x qry_cap_slice slots), grow-only; then the
+  // staging of the host-pointer entry point
+  K4DevBuf qry_ws, qry_cnt;
+  int64_t qry_cap_queries = 0;
+  uint64_t qry_cap_slice = 0;
+  K4DevBuf qry_seqs, qry_offs, qry_lens, qry_node_offs, qry_nodes;
+  hipEvent_t qry_ev[2] = {nullptr, nullptr};
+  double qry_ms = 0;
   // k4_open_async: the arrays are uploaded and the device structures built by this thread; k4_open_wait joins it
   std::thread loader;
   int load_rc = 0;

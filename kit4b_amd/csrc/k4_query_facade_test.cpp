@@ -1,0 +1,96 @@
+// kit4b_amd/csrc/k4_query_facade_test.cpp -- include/k4_sfxarray.hpp's LocateQuerySeqs the way CBlitz calls CSfxArray's
+// (ngskit4b/Blitz.cpp: one call per query from each worker thread, pHits sized MaxHits).
+// usage: k4_query_facade_test index.sfx cases.txt
+// cases.txt, per query: "len core_len core_delta strand max_hits max_iter match_pts mismatch_pts n_nodes", the bases as one word of
+// digits ("-" when len is 0), then n_nodes lines "query_start align_len targ_seq_id targ_loci n_mismatches slot strand".
+// Eight threads run every query at once; each compares what it gets, in the reference's tsQueryAlignNodes layout, with the file.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <thread>
+#include <vector>
+#include "k4_sfxarray.hpp"
+
+struct Case {
+  std::vector<etSeqBase> q;
+  uint32_t p[8];
+  std::vector<std::vector<uint32_t>> want;
+};
+
+static int RunCase(CSfxArray* pSfx, const Case& c, uint32_t QueryID, uint32_t MaxIter) {
+  std::vector<etSeqBase> Probe = c.q;
+  Probe.resize(Probe.size() + 8);
+  std::vector<tsQueryAlignNodes> Hits((size_t)c.p[3] + 1);
+  memset(Hits.data(), 0xA5, Hits.size() * sizeof(tsQueryAlignNodes));
+  const int n = pSfx->LocateQuerySeqs(QueryID, Probe.data(), (uint32_t)c.q.size(), c.p[0], c.p[1], (eALStrand)c.p[2], c.p[3], Hits.data(), MaxIter,
+                                      (int)c.p[5], (int)c.p[6]);
+  if (MaxIter != c.p[4]) return n;  // (the caller only wants the count)
+  if (n != (int)c.want.size()) return -1000;
+  for (int k = 0; k < n; k++) {
+    const tsQueryAlignNodes& h = Hits[(size_t)k];
+    const std::vector<uint32_t>& w = c.want[(size_t)k];
+    if (h.QueryStartOfs != w[0] || h.AlignLen != w[1] || h.TargSeqID != w[2] || h.TargSeqLoci != w[3] || h.NumMismatches != w[4] ||
+        h.AlignNodeID != w[5] || h.FlgStrand != w[6] || h.QueryID != (int32_t)QueryID || h.FlgRedundant || h.FlgScored || h.Flg2Rpt ||
+        h.FlgFirst2tRpt || h.HiScore != 0 || h.HiScorePathNextIdx != 0 || h.NxtHashMatch != 0)
+      return -1001;
+  }
+  return n;
+}
+
+int main(int argc, char** argv) {
+  if (argc < 3) return 1;
+  CSfxArray* pSfx = new CSfxArray;
+  if (pSfx->Open(argv[1]) < 0) {
+    while (pSfx->NumErrMsgs()) fprintf(stderr, "%s\n", pSfx->GetErrMsg());
+    return 2;
+  }
+  if (pSfx->SetTargBlock(1) < 0) return 3;
+  FILE* f = fopen(argv[2], "r");
+  if (!f) return 4;
+  std::vector<Case> Cases;
+  for (;;) {
+    Case c;
+    unsigned len, nn;
+    if (fscanf(f, "%u %u %u %u %u %u %u %u %u", &len, &c.p[0], &c.p[1], &c.p[2], &c.p[3], &c.p[4], &c.p[5], &c.p[6], &nn) != 9) break;
+    std::vector<char> s(len + 2);
+    if (fscanf(f, "%s", s.data()) != 1) return 5;
+    for (unsigned j = 0; j < len; j++) c.q.push_back((etSeqBase)(s[j] - '0'));
+    for (unsigned k = 0; k < nn; k++) {
+      std::vector<uint32_t> w(7);
+      for (int j = 0; j < 7; j++)
+        if (fscanf(f, "%u", &w[(size_t)j]) != 1) return 5;
+      c.want.push_back(w);
+    }
+    Cases.push_back(c);
+  }
+  fclose(f);
+  const int NT = 8;
+  std::vector<int> Bad(NT, 0), Nodes(NT, 0);
+  auto Work = [&](int t) {
+    for (size_t i = 0; i < Cases.size(); i++) {
+      const size_t q = (i + (size_t)t * 7) % Cases.size();  // (the threads are at different cases at any one time)
+      const int n = RunCase(pSfx, Cases[q], (uint32_t)(q + 1), Cases[q].p[4]);
+      if (n < 0) Bad[(size_t)t]++; else Nodes[(size_t)t] += n;
+    }
+  };
+  std::vector<std::thread> Th;
+  for (int t = 0; t < NT; t++) Th.emplace_back(Work, t);
+  for (auto& t : Th) t.join();
+  int bad = 0;
+  for (int t = 0; t < NT; t++) bad += Bad[(size_t)t] + (Nodes[(size_t)t] != Nodes[0] ? 1 : 0);
+  printf("threads %d queries %zu nodes %d bad %d msgs %d\n", NT, Cases.size(), Nodes[0], bad, pSfx->NumErrMsgs());
+  // InitOverOccKMers(KMerLen, MaxKMerOccs): with CoreLen == KMerLen the depth is min(CurMaxIter, MaxKMerOccs + 1)
+  if (argc > 3) {
+    const int occs = atoi(argv[3]);
+    pSfx->InitOverOccKMers((int)Cases[0].p[0], occs);
+    printf("overocc %d:", occs);
+    for (size_t i = 0; i < Cases.size(); i++) printf(" %d", RunCase(pSfx, Cases[i], (uint32_t)(i + 1), 1000000u));
+    printf("\n");
+  }
+  tsQueryAlignNodes One;
+  etSeqBase Short[32] = {0};
+  const int Rslt = pSfx->LocateQuerySeqs(1, Short, 32, 7, 1, eALSboth, 1, &One, 10, 1, 3);
+  printf("core_len 7 -> %d msgs %d\n", Rslt, pSfx->NumErrMsgs());
+  delete pSfx;
+  return 0;
+}

@@ -518,6 +518,50 @@ int k4_locate_query_seqs_batch_dev(k4_index* ix, const k4_query_params* p, int64
                                    uint64_t nodes_cap, void* stream);
 double k4_query_last_kernel_ms(const k4_index* ix);
 
+/* ---- blitz: the path stage -----------------------------------------------------------------------------------
+ * k4_blitz_paths_batch <- what CBlitz (libkit4b/CBlitz.cpp) does with the nodes of a query before it writes a line: the nodes
+ * sorted (SortQueryAlignNodes), chained into scored paths per target and strand (IdentifyHighScorePaths, HighScoreSW), the best
+ * max_paths heads of the query kept, each path consolidated base by base against the target (ConsolidateNodes), characterised
+ * (CharacterisePath) and counted (BlocksAlignStats).  Input: the queries and the node_offs / nodes k4_locate_query_seqs_batch[_dev]
+ * produced for them (match_pts / mismatch_pts as in that call).  Nodes a caller made itself must lie inside their query and
+ * target; a query under 8 bases, which is shorter than any node, gets no path.  Output: the paths of query i are paths[path_offs[i] ..
+ * path_offs[i + 1]) in the reference's report order, the blocks of a path blocks[block_off .. block_off + n_blocks).  q_start ..
+ * t_end are inclusive and, on strand 1, in the coordinates of the reverse-complemented query, as CBlitz::Report passes them on.
+ * needed[0] / needed[1] (host, always written): the paths and blocks found.  When either exceeds its capacity the call returns
+ * K4_ERR_MEM and writes nothing to path_offs, paths and blocks.  Parameters outside their ranges give K4_ERR_PARAMS.
+ * The _dev form takes device pointers (needed stays a host pointer) and a stream, and returns when the stream has finished.
+ * The index owns the workspace.  k4_blitz_last_kernel_ms: device time of the last batch. */
+typedef struct {
+  int32_t match_pts;              /* 1..10 */
+  int32_t mismatch_pts;           /* 1..10 */
+  int32_t gap_open;               /* 1..50 */
+  int32_t min_path_score;         /* 0 = ((query length - 5) * match_pts) / 3; floored at 25 */
+  int32_t query_len_aligned_pct;  /* 1..100 */
+  int32_t max_paths;              /* 1..10 */
+  int32_t strand;                 /* 0 both, 1 '+', 2 '-' */
+} k4_blitz_params;
+typedef struct {
+  uint32_t query;        /* index in the batch */
+  uint32_t targ_seq_id;
+  uint32_t strand;       /* 0 '+', 1 '-' */
+  uint32_t score;
+  uint32_t matches, mismatches, n_count;
+  uint32_t q_num_insert, q_base_insert, t_num_insert, t_base_insert;
+  uint32_t q_start, q_end, t_start, t_end;
+  uint32_t n_blocks;
+  uint64_t block_off;
+} k4_blitz_path;
+typedef struct {
+  uint32_t len, q_start, t_start;
+} k4_blitz_block;
+int k4_blitz_paths_batch(k4_index* ix, const k4_blitz_params* p, int64_t n_queries, const uint8_t* seqs, const uint64_t* offs,
+                         const uint32_t* lens, const uint64_t* node_offs, const k4_query_node* nodes, uint64_t* path_offs,
+                         k4_blitz_path* paths, uint64_t paths_cap, k4_blitz_block* blocks, uint64_t blocks_cap, uint64_t* needed);
+int k4_blitz_paths_batch_dev(k4_index* ix, const k4_blitz_params* p, int64_t n_queries, const void* d_seqs, const void* d_offs,
+                             const void* d_lens, const void* d_node_offs, const void* d_nodes, void* d_path_offs, void* d_paths,
+                             uint64_t paths_cap, void* d_blocks, uint64_t blocks_cap, uint64_t* needed, void* stream);
+double k4_blitz_last_kernel_ms(const k4_index* ix);
+
 /* ---- paired ends -----------------------------------------------------------------------------------------
  * k4_mate_rescue_batch <- CSfxArray::AlignPairedRead (SfxArray.h:880, SfxArray.cpp:8571-8767; MinChimericLen 0, insert
  *                         window < 1000 => the linear-scan branch :8731-8766 with AdaptiveTrim's full-length rule :5612-5638)

@@ -198,6 +198,7 @@ ABI_SYMBOLS = [
     "k4_load_contaminants", "k4_contam_match_host", "k4_contam_trims_dev", "k4_prepare_reads_contam_dev", "k4_pipeline_set_contaminants",
     "k4_pipeline_contam_totals", "k4_set_priority_regions", "k4_filter_priority_regions_dev", "k4_priority_times", "k4_priority_select_dev",
     "k4_query_reserve", "k4_locate_query_seqs_batch", "k4_locate_query_seqs_batch_dev", "k4_query_last_kernel_ms",
+    "k4_blitz_paths_batch", "k4_blitz_paths_batch_dev", "k4_blitz_last_kernel_ms",
 ]
 
 
@@ -206,6 +207,39 @@ class QueryParams(C.Structure):  # k4_query_params
 
 
 QUERY_NODE_DTYPE = np.dtype([(n, "<u4") for n in ("query_start", "align_len", "targ_seq_id", "targ_loci", "n_mismatches", "slot", "strand")])  # k4_query_node
+
+
+class BlitzParams(C.Structure):  # k4_blitz_params
+    _fields_ = [(n, C.c_int32) for n in ("match_pts", "mismatch_pts", "gap_open", "min_path_score", "query_len_aligned_pct", "max_paths", "strand")]
+
+
+BLITZ_PATH_DTYPE = np.dtype([(n, "<u4") for n in ("query", "targ_seq_id", "strand", "score", "matches", "mismatches", "n_count", "q_num_insert",
+                                                  "q_base_insert", "t_num_insert", "t_base_insert", "q_start", "q_end", "t_start", "t_end",
+                                                  "n_blocks")] + [("block_off", "<u8")])  # k4_blitz_path
+BLITZ_BLOCK_DTYPE = np.dtype([(n, "<u4") for n in ("len", "q_start", "t_start")])  # k4_blitz_block
+PSL_HEADER = ("psLayout version 3", "")  # the two header lines of a PSL file that name no build
+
+
+def psl_lines(index, names, queries, paths, blocks):
+    """The PSL lines (CBlitz::ReportAsPSL, libkit4b/CBlitz.cpp:1925-2006; no newline) of the paths SfxIndex.blitz_paths / blitz returned
+    for `queries`, whose names are `names`: 21 tab-separated columns, repMatches 0, qStart / qEnd flipped on '-', every block list
+    ending in a comma.  Formatted on the host."""
+    ents = {}
+    out = []
+    for p in paths:
+        tid = int(p["targ_seq_id"])
+        if tid not in ents:
+            ents[tid] = index.entry(tid)
+        qlen, plus = len(queries[int(p["query"])]), int(p["strand"]) == 0
+        qs, qe = int(p["q_start"]), int(p["q_end"])
+        b = blocks[int(p["block_off"]):int(p["block_off"]) + int(p["n_blocks"])]
+        cols = [int(p["matches"]), int(p["mismatches"]), 0, int(p["n_count"]), int(p["q_num_insert"]), int(p["q_base_insert"]),
+                int(p["t_num_insert"]), int(p["t_base_insert"]), "+" if plus else "-", names[int(p["query"])], qlen,
+                qs if plus else qlen - (qe + 1), qe + 1 if plus else qlen - qs, ents[tid]["name"], ents[tid]["seq_len"], int(p["t_start"]),
+                int(p["t_end"]) + 1, int(p["n_blocks"])]
+        cols += ["".join("%d," % int(v) for v in b[f]) for f in ("len", "q_start", "t_start")]
+        out.append("\t".join(str(c) for c in cols))
+    return out
 
 
 def build(verbose=False):
@@ -375,6 +409,10 @@ def lib():
     L.k4_locate_query_seqs_batch_dev.argtypes = [vp, C.POINTER(QueryParams), i64, u32, vp, vp, vp, vp, vp, u64, vp]
     L.k4_query_last_kernel_ms.argtypes = [vp]
     L.k4_query_last_kernel_ms.restype = dbl
+    L.k4_blitz_paths_batch.argtypes = [vp, C.POINTER(BlitzParams), i64] + [vp] * 7 + [u64, vp, u64, vp]
+    L.k4_blitz_paths_batch_dev.argtypes = [vp, C.POINTER(BlitzParams), i64] + [vp] * 7 + [u64, vp, u64, vp, vp]
+    L.k4_blitz_last_kernel_ms.argtypes = [vp]
+    L.k4_blitz_last_kernel_ms.restype = dbl
     _lib = L
     return L
 
@@ -618,6 +656,91 @@ class SfxIndex:
     def query_kernel_ms(self):
         """device milliseconds of the last locate_query_seqs batch (its three kernels)"""
         return lib().k4_query_last_kernel_ms(self.h)
+
+    def blitz_paths(self, queries, node_offs, nodes, match_pts=1, mismatch_pts=2, gap_open=5, min_path_score=0, query_len_aligned_pct=75,
+                    max_paths=1, strand=STRAND_BOTH, paths_cap=None, blocks_cap=None):
+        """CBlitz's path stage (libkit4b/CBlitz.cpp) over the nodes locate_query_seqs found: (path_offs, paths, blocks) as uint64 /
+        BLITZ_PATH_DTYPE / BLITZ_BLOCK_DTYPE arrays; the paths of query i are paths[path_offs[i]:path_offs[i + 1]] in the reference's
+        report order.  nodes: one QUERY_NODE_DTYPE array behind node_offs, or the per-query list locate_query_seqs returns (node_offs
+        None).  A capacity that is given and too small raises K4Error -95 with `.needed` = (paths, blocks)."""
+        cat, offs, lens = _flatten(queries)
+        n = len(lens)
+        if node_offs is None:
+            node_offs = np.concatenate([[0], np.cumsum([len(a) for a in nodes])]).astype(np.uint64)
+            nodes = np.concatenate(list(nodes)) if n else np.zeros(0, QUERY_NODE_DTYPE)
+        node_offs = np.ascontiguousarray(node_offs, dtype=np.uint64)
+        nodes = np.ascontiguousarray(nodes, dtype=QUERY_NODE_DTYPE)
+        p = BlitzParams(match_pts, mismatch_pts, gap_open, min_path_score, query_len_aligned_pct, max_paths, strand)
+        caps = [n * max(1, max_paths) if paths_cap is None else int(paths_cap), len(nodes) if blocks_cap is None else int(blocks_cap)]
+        path_offs = np.zeros(n + 1, dtype=np.uint64)
+        paths = np.zeros(max(caps[0], 1), dtype=BLITZ_PATH_DTYPE)
+        blocks = np.zeros(max(caps[1], 1), dtype=BLITZ_BLOCK_DTYPE)
+        needed = np.zeros(2, dtype=np.uint64)
+        rc = lib().k4_blitz_paths_batch(self.h, C.byref(p), n, cat.ctypes.data, offs.ctypes.data, lens.ctypes.data, node_offs.ctypes.data,
+                                        nodes.ctypes.data, path_offs.ctypes.data, paths.ctypes.data, caps[0], blocks.ctypes.data, caps[1],
+                                        needed.ctypes.data)
+        if rc == -95:
+            e = K4Error(rc, lib().k4_last_error(self.h).decode())
+            e.needed = (int(needed[0]), int(needed[1]))
+            raise e
+        self._ck(rc)
+        return path_offs, paths[:int(needed[0])].copy(), blocks[:int(needed[1])].copy()
+
+    def blitz(self, queries, core_len=20, core_delta=10, max_hits=200000, max_iter=100, match_pts=1, mismatch_pts=2, gap_open=5,
+              min_path_score=0, query_len_aligned_pct=75, max_paths=1, strand=STRAND_BOTH):
+        """`ngskit4b blitz` for a batch of queries, both stages on the device with the nodes staying there in between: LocateQuerySeqs
+        (k4_locate_query_seqs_batch_dev), then the path stage (k4_blitz_paths_batch_dev).  Returns (path_offs, paths, blocks) as
+        blitz_paths does; psl_lines() makes the PSL text.  locate_ms / paths_ms of the call are left in self.blitz_ms."""
+        L = lib()
+        cat, offs, lens = _flatten(queries)
+        n = len(lens)
+        max_len = int(lens.max()) if n else 0
+        qp = QueryParams(core_len, core_delta, strand, max_hits, max_iter, match_pts, mismatch_pts)
+        bp = BlitzParams(match_pts, mismatch_pts, gap_open, min_path_score, query_len_aligned_pct, max_paths, strand)
+        held = []
+
+        def dev(nbytes, src=None):
+            d = C.c_void_p()
+            self._ck(L.k4_alloc_device(self.h, max(int(nbytes), 16), C.byref(d)))
+            held.append(d)
+            if src is not None and src.nbytes:
+                self._ck(L.k4_copy_to_device(self.h, d, src.ctypes.data, src.nbytes))
+            return d
+
+        try:
+            d_seqs, d_offs, d_lens = dev(cat.nbytes + 16, cat), dev(offs.nbytes, offs), dev(lens.nbytes, lens)
+            d_node_offs = dev((n + 1) * 8)
+            cap = max(64, 8 * n)
+            node_offs = np.zeros(n + 1, dtype=np.uint64)
+            while True:
+                d_nodes = dev(cap * QUERY_NODE_DTYPE.itemsize)
+                rc = L.k4_locate_query_seqs_batch_dev(self.h, C.byref(qp), n, max_len, d_seqs, d_offs, d_lens, d_node_offs, d_nodes, cap, None)
+                self._ck(L.k4_copy_to_host(self.h, node_offs.ctypes.data, d_node_offs, node_offs.nbytes))
+                if rc == -95 and int(node_offs[n]) > cap:
+                    cap = int(node_offs[n])
+                    continue
+                self._ck(rc)
+                break
+            locate_ms = L.k4_query_last_kernel_ms(self.h)
+            total = int(node_offs[n])
+            caps = [max(1, n * max_paths), max(1, total)]
+            d_path_offs, d_paths, d_blocks = dev((n + 1) * 8), dev(caps[0] * BLITZ_PATH_DTYPE.itemsize), dev(caps[1] * BLITZ_BLOCK_DTYPE.itemsize)
+            needed = np.zeros(2, dtype=np.uint64)
+            self._ck(L.k4_blitz_paths_batch_dev(self.h, C.byref(bp), n, d_seqs, d_offs, d_lens, d_node_offs, d_nodes, d_path_offs, d_paths, caps[0],
+                                                d_blocks, caps[1], needed.ctypes.data, None))
+            self.blitz_ms = (locate_ms, L.k4_blitz_last_kernel_ms(self.h))
+            path_offs = np.zeros(n + 1, dtype=np.uint64)
+            paths = np.zeros(int(needed[0]), dtype=BLITZ_PATH_DTYPE)
+            blocks = np.zeros(int(needed[1]), dtype=BLITZ_BLOCK_DTYPE)
+            self._ck(L.k4_copy_to_host(self.h, path_offs.ctypes.data, d_path_offs, path_offs.nbytes))
+            if len(paths):
+                self._ck(L.k4_copy_to_host(self.h, paths.ctypes.data, d_paths, paths.nbytes))
+            if len(blocks):
+                self._ck(L.k4_copy_to_host(self.h, blocks.ctypes.data, d_blocks, blocks.nbytes))
+            return path_offs, paths, blocks
+        finally:
+            for d in held:
+                L.k4_free_device(d)
 
     def kalign_batch(self, reads, max_subs=5, min_edit_dist=1, max_ns=1, pmode=0, strand=STRAND_BOTH, max_ml=1,
                      pe_mode=0, min_core_len=0, max_num_slides=0):

@@ -251,6 +251,18 @@ K4_DEV int k4d_map_entry_slow(const K4DevIndex& ix, const uint64_t* ent_lds, uin
   return -1;
 }
 
+// the query in the orientation of strand s: base j of the reverse complement is the complement of base len - 1 - j (N stays N)
+struct K4QSeq {
+  const uint8_t* q;
+  uint32_t len;
+  int s;
+  K4_DEV uint32_t at(uint32_t j) const {
+    if (!s) return q[j] & 0x0fu;
+    const uint32_t b = q[len - 1 - j] & 0x0fu;
+    return b <= 3 ? 3 - b : b;
+  }
+};
+
 // mask of the bases [lo, hi) of a 32-base MSB-first chunk (0 <= lo, hi <= 32)
 K4_DEV uint64_t k4d_range_mask(int lo, int hi) {
   if (lo < 0) lo = 0;

@@ -134,6 +134,13 @@ struct k4_index {
   K4DevBuf qry_seqs, qry_offs, qry_lens, qry_node_offs, qry_nodes;
   hipEvent_t qry_ev[2] = {nullptr, nullptr};
   double qry_ms = 0;
+  // blitz's path stage (k4_blitz.hip), grow-only: the sort's keys and values, the query of each node, the sorted nodes with their
+  // scores, the group and head lists, the chosen heads, per-query path counts and offsets, the path records with their block counts
+  // and offsets; then the outputs of the host-pointer entry point (its inputs go through the qry_* staging above)
+  K4DevBuf blz_keys[2], blz_vals[2], blz_qi, blz_nodes, blz_list, blz_heads, blz_sel, blz_cnt, blz_offs, blz_paths, blz_nb, blz_boffs;
+  K4DevBuf blz_out_offs, blz_out_paths, blz_out_blocks;
+  hipEvent_t blz_ev[2] = {nullptr, nullptr};
+  double blz_ms = 0;
   // k4_open_async: the arrays are uploaded and the device structures built by this thread; k4_open_wait joins it
   std::thread loader;
   int load_rc = 0;

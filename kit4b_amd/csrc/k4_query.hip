@@ -32,18 +32,6 @@ struct K4QueryArgs {
   uint32_t* cnt;      // [2 n]: NumMatches, then the nodes left after the compaction
 };
 
-// the query in the orientation of strand s: base j of the reverse complement is the complement of base len - 1 - j (N stays N)
-struct K4QSeq {
-  const uint8_t* q;
-  uint32_t len;
-  int s;
-  K4_DEV uint32_t at(uint32_t j) const {
-    if (!s) return q[j] & 0x0fu;
-    const uint32_t b = q[len - 1 - j] & 0x0fu;
-    return b <= 3 ? 3 - b : b;
-  }
-};
-
 // CmpProbeTarg (SfxArray.cpp:2508-2525) by one lane: the core at ofs against the suffix at pos
 K4_DEV int k4q_cmp(K4Tb& tb, const K4QSeq& qs, uint32_t ofs, int cl, uint64_t pos) {
   for (int j = 0; j < cl; j++) {

@@ -464,6 +464,38 @@ class CSfxArray {
     return (int)rq.nodes.size();
   }
 
+  // CSfxArray::LocateSfxHammings / LocateHammings, SfxArray.cpp:4107-4331 -- identical parameter lists (`ngskit4b hammings -m0`,
+  // hammings.cpp:1692-1694).  One call is one device batch of one span; pHammings[0, nth, 2 nth ..] is written and nothing else.
+  // The ident nodes are not needed.  0, or eBSFerrInternal (-1) where the reference returns it; K4_ERR_PARAMS for what the
+  // device form does not take (RHamm above 10, a core KMerLen / (RHamm + 1) under 8 bases).  LocateHammings takes SeqEntry 0 only.
+  int LocateSfxHammings(int RHamm, bool bSAHammings, int KMerLen, int SampleNth, int SrcSeqLen, uint32_t MinCoreDepth, uint32_t MaxCoreDepth,
+                        uint32_t EntryID, uint32_t EntryLoci, int IntraInterBoth, uint8_t* pHammings, int NumAllocdIdentNodes = 0,
+                        tsIdentNode* pAllocsIdentNodes = nullptr) {
+    (void)NumAllocdIdentNodes; (void)pAllocsIdentNodes;
+    if (!m_pIdx || EntryID == 0 || RHamm < 1 || KMerLen < 10 || KMerLen > 500 || SrcSeqLen < KMerLen || !pHammings) return K4_ERR_INTERNAL;
+    const k4_hamming_params p = {RHamm, KMerLen, SampleNth, bSAHammings ? 1 : 0, MinCoreDepth, MaxCoreDepth, IntraInterBoth};
+    const uint32_t len = (uint32_t)SrcSeqLen, nth = SampleNth > 0 ? (uint32_t)SampleNth : 1u;
+    const uint64_t off = 0;
+    std::lock_guard<std::mutex> dev(m_Mtx);
+    const int rc = k4_locate_sfx_hammings_batch(m_pIdx, &p, 1, &EntryID, &EntryLoci, &len, &off, pHammings,
+                                                (uint64_t)((len - (uint32_t)KMerLen) / nth) * nth + 1);
+    return rc == K4_OK ? 0 : Fail(rc);
+  }
+  int LocateHammings(int RHamm, bool bSAHammings, int KMerLen, int SampleNth, int SrcSeqLen, uint32_t MinCoreDepth, uint32_t MaxCoreDepth,
+                     etSeqBase* pSrcSeq, uint32_t SeqEntry, uint32_t SeqLoci, int IntraInterBoth, uint8_t* pHammings,
+                     int NumAllocdIdentNodes = 0, tsIdentNode* pAllocsIdentNodes = nullptr) {
+    (void)NumAllocdIdentNodes; (void)pAllocsIdentNodes; (void)SeqLoci;
+    if (!m_pIdx || RHamm < 1 || KMerLen < 10 || KMerLen > 500 || SrcSeqLen < KMerLen || !pSrcSeq || !pHammings) return K4_ERR_INTERNAL;
+    if (SeqEntry != 0) return K4_ERR_UNSUPPORTED;  // (a sequence of the index goes through LocateSfxHammings)
+    const k4_hamming_params p = {RHamm, KMerLen, SampleNth, bSAHammings ? 1 : 0, MinCoreDepth, MaxCoreDepth, IntraInterBoth};
+    const uint32_t len = (uint32_t)SrcSeqLen, nth = SampleNth > 0 ? (uint32_t)SampleNth : 1u;
+    const uint64_t off = 0;
+    std::lock_guard<std::mutex> dev(m_Mtx);
+    const int rc = k4_locate_hammings_batch(m_pIdx, &p, 1, pSrcSeq, &off, &len, &off, pHammings,
+                                            (uint64_t)((len - (uint32_t)KMerLen) / nth) * nth + 1);
+    return rc == K4_OK ? 0 : Fail(rc);
+  }
+
   // CSfxArray::AlignPairedRead, SfxArray.h:880-896 -- identical parameter list (CKAligner's mate rescue,
   // KAligner.cpp:3372-3386,3476-3490).  -1 errors, 0 no match, 1 placed with mismatches only.
   int AlignPairedRead(bool b3primeExtend, bool bAntisense, uint32_t ChromID, uint32_t StartLoci, uint32_t EndLoci, int MinInsertSize,

@@ -562,6 +562,43 @@ int k4_blitz_paths_batch_dev(k4_index* ix, const k4_blitz_params* p, int64_t n_q
                              uint64_t paths_cap, void* d_blocks, uint64_t blocks_cap, uint64_t* needed, void* stream);
 double k4_blitz_last_kernel_ms(const k4_index* ix);
 
+/* ---- restricted Hammings ---------------------------------------------------------------------------------------
+ * k4_locate_sfx_hammings_batch <- CSfxArray::LocateSfxHammings (SfxArray.cpp:4107-4220) and k4_locate_hammings_batch <-
+ * CSfxArray::LocateHammings (:4227-4331), both over LocateHamming (:4339-4627; `ngskit4b hammings -m0`): for every sample_nth-th
+ * K-mer of a span the number of substitutions to the nearest other K-mer of the index, found by the reference's escalation
+ * (0,1) -> (2,2) -> (3,3) -> (4,4) -> (5,rhamm) with its core depths, so it misses what the reference misses.  One call takes
+ * n_spans spans, each what one call of the reference takes:
+ *   sfx form   span i = span_lens[i] bases of entry entry_ids[i] from locus entry_locis[i]; the K-mers know their own place
+ *   seq form   span i = lens[i] codes (etSeqBase) at seqs + offs[i]; ProbeEntry 0: no self hit, no intra / inter filter
+ * and writes hammings[out_offs[i] + j] for j = 0, nth, 2 nth .. <= span length - kmer_len: every other byte of hammings stays
+ * as it was (the reference's callers fill it with 0xFF).  The sfx form clamps a byte at 20 as the reference does.
+ * Errors, nothing written: rhamm < 1, kmer_len outside 10..500, a null array, entry id 0 or unknown, a span that leaves its
+ * entry or is shorter than kmer_len give K4_ERR_INTERNAL (the reference's eBSFerrInternal); narrower than the reference, rhamm
+ * > 10, kmer_len / (rhamm + 1) < 8, intra_inter_both outside 0..2 or a span whose bytes leave hammings_len give K4_ERR_PARAMS.
+ * The span arrays are host memory in both forms; the _dev forms take hammings (and seqs) as device pointers and a stream and
+ * return when the stream has finished.  A batch goes out in launches of a fixed number of K-mers.  The index owns the
+ * workspace.  k4_hamming_last_kernel_ms: device time of the last batch's launches. */
+typedef struct {
+  int32_t rhamm;             /* 1..10 */
+  int32_t kmer_len;          /* 10..500, kmer_len / (rhamm + 1) >= 8 */
+  int32_t sample_nth;        /* <= 0: 1 */
+  int32_t both_strands;      /* bSAHammings */
+  uint32_t min_core_depth;
+  uint32_t max_core_depth;
+  int32_t intra_inter_both;  /* 0 both, 1 intra only, 2 inter only */
+} k4_hamming_params;
+int k4_locate_sfx_hammings_batch(k4_index* ix, const k4_hamming_params* p, int64_t n_spans, const uint32_t* entry_ids,
+                                 const uint32_t* entry_locis, const uint32_t* span_lens, const uint64_t* out_offs, uint8_t* hammings,
+                                 uint64_t hammings_len);
+int k4_locate_sfx_hammings_batch_dev(k4_index* ix, const k4_hamming_params* p, int64_t n_spans, const uint32_t* entry_ids,
+                                     const uint32_t* entry_locis, const uint32_t* span_lens, const uint64_t* out_offs, void* d_hammings,
+                                     uint64_t hammings_len, void* stream);
+int k4_locate_hammings_batch(k4_index* ix, const k4_hamming_params* p, int64_t n_spans, const uint8_t* seqs, const uint64_t* offs,
+                             const uint32_t* lens, const uint64_t* out_offs, uint8_t* hammings, uint64_t hammings_len);
+int k4_locate_hammings_batch_dev(k4_index* ix, const k4_hamming_params* p, int64_t n_spans, const void* d_seqs, const uint64_t* offs,
+                                 const uint32_t* lens, const uint64_t* out_offs, void* d_hammings, uint64_t hammings_len, void* stream);
+double k4_hamming_last_kernel_ms(const k4_index* ix);
+
 /* ---- paired ends -----------------------------------------------------------------------------------------
  * k4_mate_rescue_batch <- CSfxArray::AlignPairedRead (SfxArray.h:880, SfxArray.cpp:8571-8767; MinChimericLen 0, insert
  *                         window < 1000 => the linear-scan branch :8731-8766 with AdaptiveTrim's full-length rule :5612-5638)

@@ -199,7 +199,62 @@ ABI_SYMBOLS = [
     "k4_pipeline_contam_totals", "k4_set_priority_regions", "k4_filter_priority_regions_dev", "k4_priority_times", "k4_priority_select_dev",
     "k4_query_reserve", "k4_locate_query_seqs_batch", "k4_locate_query_seqs_batch_dev", "k4_query_last_kernel_ms",
     "k4_blitz_paths_batch", "k4_blitz_paths_batch_dev", "k4_blitz_last_kernel_ms",
+    "k4_locate_sfx_hammings_batch", "k4_locate_sfx_hammings_batch_dev", "k4_locate_hammings_batch", "k4_locate_hammings_batch_dev",
+    "k4_hamming_last_kernel_ms",
 ]
+
+
+class HammingParams(C.Structure):  # k4_hamming_params
+    _fields_ = [("rhamm", C.c_int32), ("kmer_len", C.c_int32), ("sample_nth", C.c_int32), ("both_strands", C.c_int32),
+                ("min_core_depth", C.c_uint32), ("max_core_depth", C.c_uint32), ("intra_inter_both", C.c_int32)]
+
+
+HAMMING_DEPTHS = ((200, 5000), (1000, 10000), (2000, 20000), (5000, 50000))  # eSensLess, Default, More, Ultra (hammings.cpp:2366-2386)
+
+
+def hamming_spans(entry_lens, kmer_len):
+    """The spans RestrictedHammingThread (ngskit4b/hammings.cpp:1600-1656) hands to LocateSfxHammings, in its order: (entry_id,
+    entry_loci, span_len, out_offs) arrays over one byte array that covers all entries.  MaxHammSeqLen = max(10000, total / 10000);
+    the next span starts 1 + CurSeqLen - KMerLen further on; an entry shorter than a K-mer gets none."""
+    total = int(sum(int(v) for v in entry_lens))
+    max_len = max(10000, total // 10000)
+    rows, base = [], 0
+    for eid, ln in enumerate((int(v) for v in entry_lens), 1):
+        if ln >= kmer_len:
+            ofs = 0
+            while True:
+                cur = min(max_len, ln - ofs)
+                rows.append((eid, ofs, cur, base + ofs))
+                ofs += 1 + cur - kmer_len
+                if ofs + kmer_len > ln:
+                    break
+        base += ln
+    a = np.array(rows, dtype=np.uint64).reshape(-1, 4)
+    return a[:, 0].astype(np.uint32), a[:, 1].astype(np.uint32), a[:, 2].astype(np.uint32), a[:, 3].astype(np.uint64)
+
+
+def hammings_csv(names, entry_lens, hammings, kmer_len):
+    """ReportRestrictedHammingsCSV (ngskit4b/hammings.cpp:1772-1833) over the byte array restricted_hammings returns, as text: runs of
+    equal bytes per entry.  As there, the run loop compares byte 0 with itself first and never reads the byte of the last K-mer.  Host
+    side; no founder prefix."""
+    out = ['"Chrom","StartLoci","Len","Hamming"\n']
+    base = 0
+    for name, ln in zip(names, (int(v) for v in entry_lens)):
+        h = hammings[base:base + ln]
+        base += ln
+        if ln < kmer_len:
+            continue
+        cur_len, cur, cur_loci, k = 0, int(h[0]), 0, 0
+        for loci in range(1, ln - kmer_len + 1):
+            v = int(h[k])
+            k += 1
+            if v == cur:
+                cur_len += 1
+                continue
+            out.append('"%s",%d,%d,%d\n' % (name, cur_loci, cur_len, cur))
+            cur_len, cur, cur_loci = 1, v, loci
+        out.append('"%s",%d,%d,%d\n' % (name, cur_loci, cur_len, cur))
+    return "".join(out)
 
 
 class QueryParams(C.Structure):  # k4_query_params
@@ -413,6 +468,12 @@ def lib():
     L.k4_blitz_paths_batch_dev.argtypes = [vp, C.POINTER(BlitzParams), i64] + [vp] * 7 + [u64, vp, u64, vp, vp]
     L.k4_blitz_last_kernel_ms.argtypes = [vp]
     L.k4_blitz_last_kernel_ms.restype = dbl
+    L.k4_locate_sfx_hammings_batch.argtypes = [vp, C.POINTER(HammingParams), i64, vp, vp, vp, vp, vp, u64]
+    L.k4_locate_sfx_hammings_batch_dev.argtypes = [vp, C.POINTER(HammingParams), i64, vp, vp, vp, vp, vp, u64, vp]
+    L.k4_locate_hammings_batch.argtypes = [vp, C.POINTER(HammingParams), i64, vp, vp, vp, vp, vp, u64]
+    L.k4_locate_hammings_batch_dev.argtypes = [vp, C.POINTER(HammingParams), i64, vp, vp, vp, vp, vp, u64, vp]
+    L.k4_hamming_last_kernel_ms.argtypes = [vp]
+    L.k4_hamming_last_kernel_ms.restype = dbl
     _lib = L
     return L
 
@@ -741,6 +802,55 @@ class SfxIndex:
         finally:
             for d in held:
                 L.k4_free_device(d)
+
+    def sfx_hammings(self, spans, kmer_len, rhamm, min_core_depth, max_core_depth, both_strands=False, sample_nth=1, intra_inter_both=0,
+                     out=None, out_offs=None):
+        """CSfxArray::LocateSfxHammings (libkit4b/SfxArray.cpp:4107) for a batch of spans [(entry_id, entry_loci, span_len)]: a list
+        of uint8 arrays of span_len bytes, 0xFF where the reference writes nothing.  With out (uint8) and out_offs the bytes go into
+        that array instead, which is returned."""
+        sp = np.array(spans, dtype=np.int64).reshape(-1, 3)
+        n = len(sp)
+        ids, locis, lens = (np.ascontiguousarray(sp[:, k].astype(np.uint32)) for k in range(3))
+        own = out is None
+        if own:
+            out_offs = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.uint64)]).astype(np.uint64) if n else np.zeros(0, np.uint64)
+            out = np.full(max(int(lens.sum()), 1), 0xFF, dtype=np.uint8)
+        out_offs = np.ascontiguousarray(out_offs, dtype=np.uint64)
+        p = HammingParams(rhamm, kmer_len, sample_nth, 1 if both_strands else 0, min_core_depth, max_core_depth, intra_inter_both)
+        self._ck(lib().k4_locate_sfx_hammings_batch(self.h, C.byref(p), n, ids.ctypes.data, locis.ctypes.data, lens.ctypes.data,
+                                                    out_offs.ctypes.data, out.ctypes.data, len(out)))
+        return [out[int(o):int(o) + int(l)].copy() for o, l in zip(out_offs, lens)] if own else out
+
+    def hammings(self, seqs, kmer_len, rhamm, min_core_depth, max_core_depth, both_strands=False, sample_nth=1, intra_inter_both=0):
+        """CSfxArray::LocateHammings (libkit4b/SfxArray.cpp:4227) with SeqEntry 0 for a batch of sequences (codes 0..4): per sequence
+        a uint8 array of its length, 0xFF where the reference writes nothing."""
+        cat, offs, lens = _flatten(seqs)
+        n = len(lens)
+        out = np.full(max(len(cat), 1), 0xFF, dtype=np.uint8)
+        cat = np.concatenate([cat, np.zeros(16, np.uint8)])
+        p = HammingParams(rhamm, kmer_len, sample_nth, 1 if both_strands else 0, min_core_depth, max_core_depth, intra_inter_both)
+        self._ck(lib().k4_locate_hammings_batch(self.h, C.byref(p), n, cat.ctypes.data, offs.ctypes.data, lens.ctypes.data, offs.ctypes.data,
+                                                out.ctypes.data, len(out)))
+        return [out[int(o):int(o) + int(l)].copy() for o, l in zip(offs, lens)]
+
+    def restricted_hammings(self, kmer_len, rhamm, sensitivity=0, both_strands=False, sample_nth=1, intra_inter_both=0):
+        """`ngskit4b hammings -m0` over the index itself (GenRestrictedHammings, ngskit4b/hammings.cpp:2313-2405): one byte per base of
+        every entry, 0xFF where no Hamming was generated.  sensitivity 0 default, 1 more, 2 ultra, 3 less (the reference's -s); the
+        spans are cut as its worker threads cut them (hamming_spans), which decides the sampled loci when sample_nth > 1.
+        hammings_csv() makes the report."""
+        depths = {0: HAMMING_DEPTHS[1], 1: HAMMING_DEPTHS[2], 2: HAMMING_DEPTHS[3], 3: HAMMING_DEPTHS[0]}[sensitivity]
+        n = self.info()["n_entries"]
+        lens = [self.entry(e)["seq_len"] for e in range(1, n + 1)]
+        out = np.full(max(sum(lens), 1), 0xFF, dtype=np.uint8)
+        ids, locis, sl, offs = hamming_spans(lens, kmer_len)
+        if len(ids):
+            self.sfx_hammings(np.stack([ids, locis, sl], axis=1), kmer_len, rhamm, depths[0], depths[1], both_strands, sample_nth,
+                              intra_inter_both, out=out, out_offs=offs)
+        return out[:sum(lens)]
+
+    def hamming_kernel_ms(self):
+        """device milliseconds of the last Hammings batch"""
+        return lib().k4_hamming_last_kernel_ms(self.h)
 
     def kalign_batch(self, reads, max_subs=5, min_edit_dist=1, max_ns=1, pmode=0, strand=STRAND_BOTH, max_ml=1,
                      pe_mode=0, min_core_len=0, max_num_slides=0):

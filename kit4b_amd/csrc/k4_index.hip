@@ -852,6 +852,8 @@ extern "C" void k4_close(k4_index* ix) {
     if (e) hipEventDestroy(e);
   for (hipEvent_t e : ix->blz_ev)
     if (e) hipEventDestroy(e);
+  for (hipEvent_t e : ix->hmm_ev)
+    if (e) hipEventDestroy(e);
   k4_pool_trim_current_device();  // the ingest / emit stages' cached scratch (k4_pool.h)
   if (ix->ws.h_small) hipHostFree(ix->ws.h_small);
   delete ix;  // (every device block of the index and its workspaces is a K4DevBuf member)

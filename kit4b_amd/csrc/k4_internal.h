@@ -141,6 +141,10 @@ struct k4_index {
   K4DevBuf blz_out_offs, blz_out_paths, blz_out_blocks;
   hipEvent_t blz_ev[2] = {nullptr, nullptr};
   double blz_ms = 0;
+  // restricted Hammings (k4_hamming.hip), grow-only: the span table of a batch, then the staging of the host-pointer entry points
+  K4DevBuf hmm_spans, hmm_seqs, hmm_out;
+  hipEvent_t hmm_ev[2] = {nullptr, nullptr};
+  double hmm_ms = 0;
   // k4_open_async: the arrays are uploaded and the device structures built by this thread; k4_open_wait joins it
   std::thread loader;
   int load_rc = 0;

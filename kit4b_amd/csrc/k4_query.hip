@@ -32,50 +32,6 @@ struct K4QueryArgs {
   uint32_t* cnt;      // [2 n]: NumMatches, then the nodes left after the compaction
 };
 
-// CmpProbeTarg (SfxArray.cpp:2508-2525) by one lane: the core at ofs against the suffix at pos
-K4_DEV int k4q_cmp(K4Tb& tb, const K4QSeq& qs, uint32_t ofs, int cl, uint64_t pos) {
-  for (int j = 0; j < cl; j++) {
-    const uint32_t t = tb.get((int64_t)(pos + (uint64_t)j));
-    if (t == 7) return -1;
-    const uint32_t pb = qs.at(ofs + (uint32_t)j);
-    if (pb != t) return pb > t ? 1 : -1;
-  }
-  return 0;
-}
-
-// NumExactKMers (SfxArray.cpp:8122-8224) by one lane: first suffix-array index of the core's run and its length, counted no
-// further than max_iter (the caller skips a core of max_iter occurrences or more)
-template <int EL>
-K4_DEV uint32_t k4q_count(const K4DevIndex& ix, K4Tb& tb, const K4QSeq& qs, uint32_t ofs, int cl, uint32_t max_iter, uint64_t& first) {
-  const int kk = min((int)ix.k, cl);
-  uint64_t lo = 0, hi = ix.n;  // [lo, hi)
-  uint64_t code = 0;
-  bool acgt = true;
-  for (int j = 0; j < kk; j++) {
-    const uint32_t b = qs.at(ofs + (uint32_t)j);
-    if (b > 3) { acgt = false; break; }
-    code = (code << 2) | b;
-  }
-  if (acgt) {  // (a core that holds N in its first k bases: the whole array is searched, as LocateFirstExact would)
-    const int sh = 2 * ((int)ix.k - kk);
-    lo = k4d_ktab_lb(ix, code << sh);
-    hi = k4d_ktab_lb(ix, (code + 1) << sh);
-  }
-  uint64_t a = lo, b = hi;
-  while (a < b) {  // lowest index whose suffix is not below the core
-    const uint64_t mid = (a + b) >> 1;
-    if (k4q_cmp(tb, qs, ofs, cl, k4d_sa_at<EL>(ix, mid)) > 0) a = mid + 1; else b = mid;
-  }
-  first = a;
-  if (a >= hi || k4q_cmp(tb, qs, ofs, cl, k4d_sa_at<EL>(ix, a)) != 0) return 0;
-  uint64_t c = a + 1, d = min(hi, a + (uint64_t)max_iter);
-  while (c < d) {  // lowest index behind the first whose suffix is above the core
-    const uint64_t mid = (c + d) >> 1;
-    if (k4q_cmp(tb, qs, ofs, cl, k4d_sa_at<EL>(ix, mid)) == 0) c = mid + 1; else d = mid;
-  }
-  return (uint32_t)(c - a);
-}
-
 // :6605-6623: is the core (query offset ofs, locus loci of target tid) inside a node of the chain that starts at node id idx, on
 // that node's diagonal?  Only the ids above `floor` are looked at (ids fall along a chain).
 K4_DEV bool k4q_contained(const K4QNode* ws, uint32_t idx, uint32_t floor, uint32_t tid, uint32_t ofs, uint32_t loci, uint32_t cl) {

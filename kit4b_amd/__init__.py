@@ -715,7 +715,8 @@ class SfxIndex:
             return [nodes[int(node_offs[i]):int(node_offs[i + 1])].copy() for i in range(n)]
 
     def query_kernel_ms(self):
-        """device milliseconds of the last locate_query_seqs batch (its three kernels)"""
+        """device milliseconds of the last locate_query_seqs batch (the locate kernel, rocPRIM's scan of the counts, the gather kernel);
+        0 for a batch of no queries"""
         return lib().k4_query_last_kernel_ms(self.h)
 
     def blitz_paths(self, queries, node_offs, nodes, match_pts=1, mismatch_pts=2, gap_open=5, min_path_score=0, query_len_aligned_pct=75,

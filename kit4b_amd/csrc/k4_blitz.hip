@@ -9,7 +9,6 @@
 //   path     one wave per reported path: ConsolidateNodes (:2157-2320) and CharacterisePath (:2666-2779) by lane 0, the counts of
 //            BlocksAlignStats (:1729-1849) across the lanes
 // DESIGN.md "blitz: the path stage" has the rest.
-#include <string.h>
 #include <algorithm>
 #include "k4_stage.h"
 
@@ -400,42 +399,41 @@ extern "C" int k4_blitz_paths_batch_dev(k4_index* ix, const k4_blitz_params* p, 
                                         uint64_t paths_cap, void* d_blocks, uint64_t blocks_cap, uint64_t* needed, void* stream) {
   int rc = check_blitz_params(ix, p);
   if (rc != K4_OK) return rc;
+  K4BlitzState& b = ix->blz;
+  b.timer.reset();
   if (n < 0 || n >= 0x7FFFFFFFll || !d_node_offs || !d_path_offs || !needed || (n > 0 && (!d_seqs || !d_offs || !d_lens)))
     return k4_fail(ix, K4_ERR_PARAMS, "blitz paths: null argument");
   if ((paths_cap > 0 && !d_paths) || (blocks_cap > 0 && !d_blocks)) return k4_fail(ix, K4_ERR_PARAMS, "blitz paths: a capacity without its buffer");
   K4_HIP(ix, hipSetDevice(ix->device));
   hipStream_t st = (hipStream_t)stream;
-  for (hipEvent_t& e : ix->blz_ev)
-    if (!e) K4_HIP(ix, hipEventCreate(&e));
   needed[0] = needed[1] = 0;
-  ix->blz_ms = 0;
   uint64_t total = 0;
   K4_TRY(k4s_read_back(ix, &total, (const uint64_t*)d_node_offs + n, st));
   if (total >= 0xFFFFFFFEull) return k4_fail(ix, K4_ERR_PARAMS, "blitz paths: at most 2^32-2 nodes per batch");
   if (total > 0 && !d_nodes) return k4_fail(ix, K4_ERR_PARAMS, "blitz paths: null argument");
   const uint64_t max_sel = (uint64_t)n * (uint64_t)p->max_paths;
-  K4_HIP(ix, ix->blz_cnt.reserve((size_t)(n + 1) * 4));
-  K4_HIP(ix, ix->blz_offs.reserve((size_t)(n + 1) * 8));
-  uint64_t* offs = ix->blz_offs.as<uint64_t>();
+  K4_HIP(ix, b.cnt.reserve((size_t)(n + 1) * 4));
+  K4_HIP(ix, b.offs.reserve((size_t)(n + 1) * 8));
+  uint64_t* offs = b.offs.as<uint64_t>();
   uint64_t n_paths = 0, n_blocks = 0;
-  K4_HIP(ix, hipEventRecord(ix->blz_ev[0], st));
-  if (total == 0) {
+  if (total == 0) {  // no work: every query's paths start at 0
     K4_HIP(ix, hipMemsetAsync(offs, 0, (size_t)(n + 1) * 8, st));
   } else {
-    for (K4DevBuf& b : ix->blz_keys) K4_HIP(ix, b.reserve((size_t)total * 8));
-    for (K4DevBuf& b : ix->blz_vals) K4_HIP(ix, b.reserve((size_t)total * 4));
-    K4_HIP(ix, ix->blz_qi.reserve((size_t)total * 4));
-    K4_HIP(ix, ix->blz_nodes.reserve((size_t)total * sizeof(K4BNode)));
-    K4_HIP(ix, ix->blz_list.reserve((size_t)total * 4 + 16));
-    K4_HIP(ix, ix->blz_heads.reserve((size_t)total * 4 + 16));
-    K4_HIP(ix, ix->blz_sel.reserve((size_t)std::max<uint64_t>(max_sel, 1) * 4));
+    K4_HIP(ix, b.timer.begin(st));
+    for (K4DevBuf& kv : b.keys) K4_HIP(ix, kv.reserve((size_t)total * 8));
+    for (K4DevBuf& kv : b.vals) K4_HIP(ix, kv.reserve((size_t)total * 4));
+    K4_HIP(ix, b.qi.reserve((size_t)total * 4));
+    K4_HIP(ix, b.nodes.reserve((size_t)total * sizeof(K4BNode)));
+    K4_HIP(ix, b.list.reserve((size_t)total * 4 + 16));
+    K4_HIP(ix, b.heads.reserve((size_t)total * 4 + 16));
+    K4_HIP(ix, b.sel.reserve((size_t)std::max<uint64_t>(max_sel, 1) * 4));
     const k4_query_node* nodes = (const k4_query_node*)d_nodes;
     const uint64_t* node_offs = (const uint64_t*)d_node_offs;
     const unsigned nb = (unsigned)((total + 255) / 256);
-    rocprim::double_buffer<uint64_t> keys(ix->blz_keys[0].as<uint64_t>(), ix->blz_keys[1].as<uint64_t>());
-    rocprim::double_buffer<uint32_t> vals(ix->blz_vals[0].as<uint32_t>(), ix->blz_vals[1].as<uint32_t>());
-    uint32_t* qi = ix->blz_qi.as<uint32_t>();
-    K4BNode* ws = ix->blz_nodes.as<K4BNode>();
+    rocprim::double_buffer<uint64_t> keys(b.keys[0].as<uint64_t>(), b.keys[1].as<uint64_t>());
+    rocprim::double_buffer<uint32_t> vals(b.vals[0].as<uint32_t>(), b.vals[1].as<uint32_t>());
+    uint32_t* qi = b.qi.as<uint32_t>();
+    K4BNode* ws = b.nodes.as<K4BNode>();
     hipLaunchKernelGGL(k4k_blitz_keys_lo, dim3(nb), dim3(256), 0, st, nodes, node_offs, n, total, keys.current(), vals.current(), qi);
     K4_TRY(k4s_sort_pairs<K4DevBuf>(ix, keys, vals, (size_t)total, 0, 64, st));
     hipLaunchKernelGGL(k4k_blitz_keys_hi, dim3(nb), dim3(256), 0, st, nodes, qi, vals.current(), total, keys.current());
@@ -443,8 +441,8 @@ extern "C" int k4_blitz_paths_batch_dev(k4_index* ix, const k4_blitz_params* p, 
     hipLaunchKernelGGL(k4k_blitz_gather, dim3(nb), dim3(256), 0, st, nodes, qi, vals.current(), node_offs, total, ws);
     K4_HIP(ix, hipGetLastError());
     // the groups, one wave each per strand
-    uint32_t* list = ix->blz_list.as<uint32_t>();
-    uint64_t* d_m = reinterpret_cast<uint64_t*>(ix->blz_list.as<char>() + (((size_t)total * 4 + 7) & ~(size_t)7));
+    uint32_t* list = b.list.as<uint32_t>();
+    uint64_t* d_m = reinterpret_cast<uint64_t*>(b.list.as<char>() + (((size_t)total * 4 + 7) & ~(size_t)7));
     uint64_t n_groups = 0;
     K4_TRY(k4s_select<K4DevBuf>(ix, rocprim::counting_iterator<uint32_t>(0), list, d_m, (size_t)total, K4BHasFlag{ws, K4B_GROUP}, st));
     K4_TRY(k4s_read_back(ix, &n_groups, d_m, st));
@@ -455,25 +453,25 @@ extern "C" int k4_blitz_paths_batch_dev(k4_index* ix, const k4_blitz_params* p, 
     hipLaunchKernelGGL(k4k_blitz_score, dim3((unsigned)n_groups, 2), dim3(64), 0, st, a, list, n_groups);
     K4_HIP(ix, hipGetLastError());
     // the heads, the first max_paths of each query, where each query's paths start
-    uint32_t* heads = ix->blz_heads.as<uint32_t>();
-    uint64_t* d_h = reinterpret_cast<uint64_t*>(ix->blz_heads.as<char>() + (((size_t)total * 4 + 7) & ~(size_t)7));
+    uint32_t* heads = b.heads.as<uint32_t>();
+    uint64_t* d_h = reinterpret_cast<uint64_t*>(b.heads.as<char>() + (((size_t)total * 4 + 7) & ~(size_t)7));
     uint64_t n_heads = 0;
     K4_TRY(k4s_select<K4DevBuf>(ix, rocprim::counting_iterator<uint32_t>(0), heads, d_h, (size_t)total, K4BHasFlag{ws, K4B_FIRST}, st));
     K4_TRY(k4s_read_back(ix, &n_heads, d_h, st));
-    uint32_t* cnt = ix->blz_cnt.as<uint32_t>();
-    uint32_t* sel = ix->blz_sel.as<uint32_t>();
+    uint32_t* cnt = b.cnt.as<uint32_t>();
+    uint32_t* sel = b.sel.as<uint32_t>();
     hipLaunchKernelGGL(k4k_blitz_pick, dim3((unsigned)(n + 1)), dim3(64), 0, st, ws, heads, n_heads, node_offs, n, (int)p->max_paths, sel, cnt);
     K4_HIP(ix, hipGetLastError());
     K4_TRY(k4s_exclusive_scan<K4DevBuf>(ix, cnt, offs, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st));
     K4_TRY(k4s_read_back(ix, &n_paths, offs + n, st));
     if (n_paths > 0) {
-      K4_HIP(ix, ix->blz_paths.reserve((size_t)n_paths * sizeof(k4_blitz_path)));
-      K4_HIP(ix, ix->blz_nb.reserve((size_t)(n_paths + 1) * 4));
-      K4_HIP(ix, ix->blz_boffs.reserve((size_t)(n_paths + 1) * 8));
-      uint32_t* nbk = ix->blz_nb.as<uint32_t>();
-      uint64_t* boffs = ix->blz_boffs.as<uint64_t>();
+      K4_HIP(ix, b.paths.reserve((size_t)n_paths * sizeof(k4_blitz_path)));
+      K4_HIP(ix, b.nb.reserve((size_t)(n_paths + 1) * 4));
+      K4_HIP(ix, b.boffs.reserve((size_t)(n_paths + 1) * 8));
+      uint32_t* nbk = b.nb.as<uint32_t>();
+      uint64_t* boffs = b.boffs.as<uint64_t>();
       hipLaunchKernelGGL(k4k_blitz_path, dim3((unsigned)(n + 1), (unsigned)p->max_paths), dim3(64), 0, st, a, sel, cnt, offs,
-                         ix->blz_paths.as<k4_blitz_path>(), nbk);
+                         b.paths.as<k4_blitz_path>(), nbk);
       K4_HIP(ix, hipGetLastError());
       K4_TRY(k4s_exclusive_scan<K4DevBuf>(ix, nbk, boffs, (uint64_t)0, (size_t)(n_paths + 1), rocprim::plus<uint64_t>(), st));
       K4_TRY(k4s_read_back(ix, &n_blocks, boffs + n_paths, st));
@@ -485,16 +483,14 @@ extern "C" int k4_blitz_paths_batch_dev(k4_index* ix, const k4_blitz_params* p, 
   if (fits) {
     K4_HIP(ix, hipMemcpyAsync(d_path_offs, offs, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, st));
     if (n_paths > 0)
-      hipLaunchKernelGGL(k4k_blitz_emit, dim3((unsigned)((n + 63) / 64), (unsigned)p->max_paths), dim3(64), 0, st, ix->blz_nodes.as<K4BNode>(),
-                         ix->blz_sel.as<uint32_t>(), ix->blz_cnt.as<uint32_t>(), offs, ix->blz_boffs.as<uint64_t>(), n, (int)p->max_paths,
-                         ix->blz_paths.as<k4_blitz_path>(), (k4_blitz_path*)d_paths, (k4_blitz_block*)d_blocks);
+      hipLaunchKernelGGL(k4k_blitz_emit, dim3((unsigned)((n + 63) / 64), (unsigned)p->max_paths), dim3(64), 0, st, b.nodes.as<K4BNode>(),
+                         b.sel.as<uint32_t>(), b.cnt.as<uint32_t>(), offs, b.boffs.as<uint64_t>(), n, (int)p->max_paths,
+                         b.paths.as<k4_blitz_path>(), (k4_blitz_path*)d_paths, (k4_blitz_block*)d_blocks);
     K4_HIP(ix, hipGetLastError());
   }
-  K4_HIP(ix, hipEventRecord(ix->blz_ev[1], st));
+  K4_HIP(ix, b.timer.end(st));
   K4_HIP(ix, hipStreamSynchronize(st));
-  float ms = 0;
-  K4_HIP(ix, hipEventElapsedTime(&ms, ix->blz_ev[0], ix->blz_ev[1]));
-  ix->blz_ms = ms;
+  K4_HIP(ix, b.timer.read());
   if (!fits)
     return k4_fail(ix, K4_ERR_MEM, "blitz paths: %llu paths and %llu blocks found, paths_cap is %llu and blocks_cap %llu", (unsigned long long)n_paths,
                    (unsigned long long)n_blocks, (unsigned long long)paths_cap, (unsigned long long)blocks_cap);
@@ -506,37 +502,31 @@ extern "C" int k4_blitz_paths_batch(k4_index* ix, const k4_blitz_params* p, int6
                                     k4_blitz_path* paths, uint64_t paths_cap, k4_blitz_block* blocks, uint64_t blocks_cap, uint64_t* needed) {
   int rc = check_blitz_params(ix, p);
   if (rc != K4_OK) return rc;
+  K4BlitzState& b = ix->blz;
+  b.timer.reset();
   if (n < 0 || !node_offs || !path_offs || !needed || (n > 0 && (!seqs || !offs || !lens)) || (node_offs[n] > 0 && !nodes) ||
       (paths_cap > 0 && !paths) || (blocks_cap > 0 && !blocks))
     return k4_fail(ix, K4_ERR_PARAMS, "blitz paths: null argument");
   K4_HIP(ix, hipSetDevice(ix->device));
-  uint64_t bytes = 0;
-  for (int64_t i = 0; i < n; i++) bytes = std::max<uint64_t>(bytes, offs[i] + lens[i]);
+  K4SeqStage& s = ix->seq_stage;
   const uint64_t total = node_offs[n];
   hipStream_t st = ix->stream;
-  K4_HIP(ix, ix->qry_seqs.reserve((size_t)bytes + 16));
-  K4_HIP(ix, ix->qry_offs.reserve((size_t)(n + 1) * 8));
-  K4_HIP(ix, ix->qry_lens.reserve((size_t)(n + 1) * 4));
-  K4_HIP(ix, ix->qry_node_offs.reserve((size_t)(n + 1) * 8));
-  K4_HIP(ix, ix->qry_nodes.reserve((size_t)std::max<uint64_t>(total, 1) * sizeof(k4_query_node)));
-  K4_HIP(ix, ix->blz_out_offs.reserve((size_t)(n + 1) * 8));
-  K4_HIP(ix, ix->blz_out_paths.reserve((size_t)std::max<uint64_t>(paths_cap, 1) * sizeof(k4_blitz_path)));
-  K4_HIP(ix, ix->blz_out_blocks.reserve((size_t)std::max<uint64_t>(blocks_cap, 1) * sizeof(k4_blitz_block)));
-  if (n > 0) {
-    K4_HIP(ix, hipMemcpyAsync(ix->qry_seqs.p, seqs, (size_t)bytes, hipMemcpyHostToDevice, st));
-    K4_HIP(ix, hipMemcpyAsync(ix->qry_offs.p, offs, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    K4_HIP(ix, hipMemcpyAsync(ix->qry_lens.p, lens, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  }
-  K4_HIP(ix, hipMemcpyAsync(ix->qry_node_offs.p, node_offs, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-  if (total) K4_HIP(ix, hipMemcpyAsync(ix->qry_nodes.p, nodes, (size_t)total * sizeof(k4_query_node), hipMemcpyHostToDevice, st));
-  rc = k4_blitz_paths_batch_dev(ix, p, n, ix->qry_seqs.p, ix->qry_offs.p, ix->qry_lens.p, ix->qry_node_offs.p, ix->qry_nodes.p, ix->blz_out_offs.p,
-                                ix->blz_out_paths.p, paths_cap, ix->blz_out_blocks.p, blocks_cap, needed, st);
+  K4_TRY(k4s_stage_seqs(ix, n, seqs, offs, lens, nullptr));
+  K4_HIP(ix, s.node_offs.reserve((size_t)(n + 1) * 8));
+  K4_HIP(ix, s.nodes.reserve((size_t)std::max<uint64_t>(total, 1) * sizeof(k4_query_node)));
+  K4_HIP(ix, b.out_offs.reserve((size_t)(n + 1) * 8));
+  K4_HIP(ix, b.out_paths.reserve((size_t)std::max<uint64_t>(paths_cap, 1) * sizeof(k4_blitz_path)));
+  K4_HIP(ix, b.out_blocks.reserve((size_t)std::max<uint64_t>(blocks_cap, 1) * sizeof(k4_blitz_block)));
+  K4_HIP(ix, hipMemcpyAsync(s.node_offs.p, node_offs, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+  if (total) K4_HIP(ix, hipMemcpyAsync(s.nodes.p, nodes, (size_t)total * sizeof(k4_query_node), hipMemcpyHostToDevice, st));
+  rc = k4_blitz_paths_batch_dev(ix, p, n, s.seqs.p, s.offs.p, s.lens.p, s.node_offs.p, s.nodes.p, b.out_offs.p, b.out_paths.p, paths_cap,
+                                b.out_blocks.p, blocks_cap, needed, st);
   if (rc != K4_OK) return rc;  // (nothing of the outputs has been written)
-  K4_HIP(ix, hipMemcpyAsync(path_offs, ix->blz_out_offs.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
-  if (needed[0]) K4_HIP(ix, hipMemcpyAsync(paths, ix->blz_out_paths.p, (size_t)needed[0] * sizeof(k4_blitz_path), hipMemcpyDeviceToHost, st));
-  if (needed[1]) K4_HIP(ix, hipMemcpyAsync(blocks, ix->blz_out_blocks.p, (size_t)needed[1] * sizeof(k4_blitz_block), hipMemcpyDeviceToHost, st));
+  K4_HIP(ix, hipMemcpyAsync(path_offs, b.out_offs.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (needed[0]) K4_HIP(ix, hipMemcpyAsync(paths, b.out_paths.p, (size_t)needed[0] * sizeof(k4_blitz_path), hipMemcpyDeviceToHost, st));
+  if (needed[1]) K4_HIP(ix, hipMemcpyAsync(blocks, b.out_blocks.p, (size_t)needed[1] * sizeof(k4_blitz_block), hipMemcpyDeviceToHost, st));
   K4_HIP(ix, hipStreamSynchronize(st));
   return K4_OK;
 }
 
-extern "C" double k4_blitz_last_kernel_ms(const k4_index* ix) { return ix ? ix->blz_ms : 0.0; }
+extern "C" double k4_blitz_last_kernel_ms(const k4_index* ix) { return ix ? ix->blz.timer.ms : 0.0; }

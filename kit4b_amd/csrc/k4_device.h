@@ -307,6 +307,32 @@ K4_DEV uint32_t k4q_count(const K4DevIndex& ix, K4Tb& tb, const K4QSeq& qs, uint
   return (uint32_t)(c - a);
 }
 
+// The ordered candidates of a group, for a block of ONE wave (k4k_query_locate, k4k_hammings): lane i holds run i of the suffix
+// array -- its first index and how many of its occurrences are taken, 0 without a run -- and the candidates are those occurrences,
+// run after run.  Into LDS: g_first[64] the first indices, g_pre[65] the candidates in front of each run, g_pre[64] the total.  No
+// barrier in here: the caller places one in front where an earlier pass may still read the arrays, and one behind.
+K4_DEV void k4d_runs_layout(int lane, uint64_t first, uint32_t take, uint64_t* g_first, uint32_t* g_pre) {
+  uint32_t x = take;
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t y = __shfl_up(x, (unsigned)d, 64);
+    if (lane >= d) x += y;
+  }
+  g_first[lane] = first;
+  g_pre[lane] = x - take;
+  if (lane == 63) g_pre[64] = x;
+}
+// candidate g (below the total) is occurrence occ of run item, the last run in 0 .. hi whose candidates start at or before g; any
+// hi at or behind the last run that has a candidate gives the same answer, the entries behind that run holding the total
+K4_DEV void k4d_runs_locate(uint32_t g, uint32_t hi, const uint32_t* g_pre, uint32_t& item, uint32_t& occ) {
+  uint32_t lo = 0;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (g_pre[mid] <= g) lo = mid; else hi = mid - 1;
+  }
+  item = lo;
+  occ = g - g_pre[lo];
+}
+
 // mask of the bases [lo, hi) of a 32-base MSB-first chunk (0 <= lo, hi <= 32)
 K4_DEV uint64_t k4d_range_mask(int lo, int hi) {
   if (lo < 0) lo = 0;

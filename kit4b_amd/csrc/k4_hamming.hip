@@ -6,7 +6,7 @@
 // CurHamming of the chunk's start; the first lane in order that brings it to RHammMin or below ends the stage, otherwise the
 // wave's minimum is the new CurHamming.  DESIGN.md "Restricted Hammings" has the rest.
 #include <algorithm>
-#include "k4_device.h"
+#include "k4_stage.h"
 
 #define K4H_MAX_KMER 500
 #define K4H_LAUNCH_KMERS 32768  // K-mers (waves) per launch: at the `ultra` preset one core may walk 500 000 suffixes
@@ -28,6 +28,13 @@ struct K4HammArgs {
   uint64_t k0, k1;  // this launch's K-mers
   k4_hamming_params p;
 };
+
+// is an exact match at locus loci of target tid one the reference passes over (:4411-4452, :4585-4601): the probe itself, which
+// only a sense pass knows, or a target the intra / inter filter leaves out
+K4_DEV bool k4h_filtered(uint32_t tid, uint32_t loci, uint32_t probe_entry, uint32_t probe_loci, int iib, bool sense) {
+  if (sense && tid == probe_entry && loci == probe_loci) return true;
+  return (iib == 1 && tid != probe_entry) || (iib == 2 && tid == probe_entry);
+}
 
 // one candidate of segment seg (LocateHamming :4533-4601): the suffix at pos holds the segment's core.  The mismatches of the
 // K-mer window around it, or K4H_SKIP.  The duplicate-segment test (:4546-4561) rides on the count: an earlier segment without a
@@ -53,11 +60,7 @@ K4_DEV uint32_t k4h_candidate(const K4DevIndex& ix, K4Tb& tb, const K4QSeq& qs, 
   }
   if (mm == 0 && sense && probe_entry > 0) {  // :4585-4601
     const int e = k4d_map_entry(ix, left);
-    if (e >= 0) {
-      const uint32_t tid = ix.ent_id[e];
-      if (tid == probe_entry && probe_loci == (uint32_t)(left - ix.ent_start[e])) return K4H_SKIP;
-      if ((iib == 1 && tid != probe_entry) || (iib == 2 && tid == probe_entry)) return K4H_SKIP;
-    }
+    if (e >= 0 && k4h_filtered(ix.ent_id[e], (uint32_t)(left - ix.ent_start[e]), probe_entry, probe_loci, iib, sense)) return K4H_SKIP;
   }
   return mm;
 }
@@ -87,11 +90,8 @@ K4_DEV uint32_t k4h_locate(const K4DevIndex& ix, K4Tb& tb, const uint8_t* pb, ui
         if (c0 + (uint32_t)lane < c) {
           const uint64_t pos = k4d_sa_at<EL>(ix, f + c0 + (uint32_t)lane);
           const int e = k4d_map_entry(ix, pos);
-          if (e >= 0) {
-            const uint32_t tid = ix.ent_id[e];
-            ok = !(s == 0 && tid == probe_entry && probe_loci == (uint32_t)(pos - ix.ent_start[e])) &&
-                 !(iib != 0 && ((iib == 1 && tid != probe_entry) || (iib == 2 && tid == probe_entry)));
-          }
+          // (the antisense run holds no self hit)
+          ok = e >= 0 && !k4h_filtered(ix.ent_id[e], (uint32_t)(pos - ix.ent_start[e]), probe_entry, probe_loci, iib, s == 0);
         }
         if (__ballot(ok)) return 0u;
       }
@@ -113,15 +113,8 @@ K4_DEV uint32_t k4h_locate(const K4DevIndex& ix, K4Tb& tb, const uint8_t* pb, ui
       take = min(run, max_cd);
       if (min_cd >= 2 && min_cd <= max_cd && (uint64_t)run + 1 >= min_cd && (uint64_t)run + 3 > (uint64_t)max_cd + min_cd) take = min_cd - 1;
     }
-    uint32_t x = take;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(x, (unsigned)d, 64);
-      if (lane >= d) x += y;
-    }
     __syncthreads();  // (the previous pass has done with g_first / g_pre)
-    g_first[lane] = first;
-    g_pre[lane] = x - take;
-    if (lane == 63) g_pre[64] = x;
+    k4d_runs_layout(lane, first, take, g_first, g_pre);
     __syncthreads();
     const uint32_t total = g_pre[64];
     // 2. the candidates in the reference's order, 64 at a time
@@ -129,13 +122,10 @@ K4_DEV uint32_t k4h_locate(const K4DevIndex& ix, K4Tb& tb, const uint8_t* pb, ui
       const uint32_t g = c0 + (uint32_t)lane;
       uint32_t mm = K4H_SKIP;
       if (g < total) {
-        uint32_t lo = 0, hi = n_seg - 1;  // the last segment whose candidates start at or before g
-        while (lo < hi) {
-          const uint32_t mid = (lo + hi + 1) >> 1;
-          if (g_pre[mid] <= g) lo = mid; else hi = mid - 1;
-        }
-        const uint64_t pos = k4d_sa_at<EL>(ix, g_first[lo] + (g - g_pre[lo]));
-        mm = k4h_candidate(ix, tb, qs, core_len, lo, pos, cur, s == 0, probe_entry, probe_loci, iib);
+        uint32_t seg, occ;
+        k4d_runs_locate(g, n_seg - 1, g_pre, seg, occ);
+        const uint64_t pos = k4d_sa_at<EL>(ix, g_first[seg] + occ);
+        mm = k4h_candidate(ix, tb, qs, core_len, seg, pos, cur, s == 0, probe_entry, probe_loci, iib);
       }
       // 3. in order: the first candidate at or under hmin ends the stage (nothing in front of it was), else the minimum stands
       const unsigned long long stop = __ballot(mm != K4H_SKIP && mm <= hmin);
@@ -230,14 +220,6 @@ static int check_hamming_params(k4_index* ix, const k4_hamming_params* p) {
   return K4_OK;
 }
 
-static const k4_entry* find_entry(const k4_index* ix, uint32_t id) {
-  if (id == 0) return nullptr;
-  if (id <= ix->entries.size() && ix->entries[id - 1].entry_id == id) return &ix->entries[id - 1];
-  for (const k4_entry& e : ix->entries)
-    if (e.entry_id == id) return &e;
-  return nullptr;
-}
-
 // the span table of a batch; sfx form when entry_ids is given, else the seq form over offs / lens
 static int hamming_spans(k4_index* ix, const k4_hamming_params* p, int64_t n, const uint32_t* entry_ids, const uint32_t* entry_locis,
                          const uint32_t* span_lens, const uint64_t* offs, const uint64_t* out_offs, uint64_t out_len, std::vector<K4HSpan>& t) {
@@ -249,7 +231,7 @@ static int hamming_spans(k4_index* ix, const k4_hamming_params* p, int64_t n, co
     if (sl < klen) return k4_fail(ix, K4_ERR_INTERNAL, "Hammings: span %lld of %u bases is shorter than kmer_len %u", (long long)i, sl, klen);
     K4HSpan& s = t[(size_t)i];
     if (entry_ids) {
-      const k4_entry* e = find_entry(ix, entry_ids[i]);
+      const k4_entry* e = k4i_entry_by_id(ix, entry_ids[i]);
       if (!e || e->seq_len == 0 || entry_locis[i] > e->seq_len || e->seq_len - entry_locis[i] < sl)
         return k4_fail(ix, K4_ERR_INTERNAL, "Hammings: span %lld (entry %u, locus %u, %u bases) is not inside an entry", (long long)i,
                        entry_ids[i], entry_locis[i], sl);
@@ -271,25 +253,44 @@ static int hamming_spans(k4_index* ix, const k4_hamming_params* p, int64_t n, co
   return K4_OK;
 }
 
-static int hamming_run(k4_index* ix, const k4_hamming_params* p, const std::vector<K4HSpan>& t, const void* d_seqs, void* d_out, hipStream_t st) {
-  const int64_t n = (int64_t)t.size() - 1;
+// One batch, for the four entry points.  sfx: the spans are (entry_ids, entry_locis, lens) of the index itself and seqs / offs stay
+// null; otherwise they are the lens[i] bases at seqs + offs[i].  on_host: seqs and hammings are the caller's own arrays and the
+// index's stream is used; hammings then goes up whole and comes back whole, so the bytes no K-mer owns return as they came.
+static int hamming_batch(k4_index* ix, const k4_hamming_params* p, bool sfx, bool on_host, int64_t n, const uint32_t* entry_ids,
+                         const uint32_t* entry_locis, const void* seqs, const uint64_t* offs, const uint32_t* lens, const uint64_t* out_offs,
+                         void* hammings, uint64_t hammings_len, hipStream_t st) {
+  int rc = check_hamming_params(ix, p);
+  if (rc != K4_OK) return rc;
+  K4HammState& h = ix->hmm;
+  h.timer.reset();
+  const bool src = sfx ? n == 0 || (entry_ids && entry_locis) : seqs && (n == 0 || offs);
+  if (n < 0 || !hammings || !src || (n > 0 && (!lens || !out_offs))) return k4_fail(ix, K4_ERR_INTERNAL, "Hammings: null argument");
+  K4_HIP(ix, hipSetDevice(ix->device));
+  std::vector<K4HSpan> t;
+  if ((rc = hamming_spans(ix, p, n, entry_ids, entry_locis, lens, offs, out_offs, hammings_len, t)) != K4_OK) return rc;
   const uint64_t total = t[(size_t)n].kbase;
-  for (hipEvent_t& e : ix->hmm_ev)
-    if (!e) K4_HIP(ix, hipEventCreate(&e));
-  ix->hmm_ms = 0;
   if (total == 0) return K4_OK;
-  K4_HIP(ix, hipStreamSynchronize(st));  // (a table about to be replaced may still be read by the batch before)
-  K4_HIP(ix, ix->hmm_spans.reserve(t.size() * sizeof(K4HSpan)));
-  K4_HIP(ix, hipMemcpyAsync(ix->hmm_spans.p, t.data(), t.size() * sizeof(K4HSpan), hipMemcpyHostToDevice, st));
   K4HammArgs a;
+  a.seqs = (const uint8_t*)seqs;  // (null: the sfx form)
+  a.out = (uint8_t*)hammings;
+  if (on_host) {
+    st = ix->stream;
+    K4_HIP(ix, hipStreamSynchronize(st));  // (the staging about to be replaced may still be read by the batch before)
+    K4_HIP(ix, h.out.reserve((size_t)hammings_len + 16));
+    K4_HIP(ix, hipMemcpyAsync(h.out.p, hammings, (size_t)hammings_len, hipMemcpyHostToDevice, st));
+    if (!sfx) K4_TRY(k4s_stage_seqs(ix, n, (const uint8_t*)seqs, offs, lens, nullptr));
+    a.seqs = sfx ? nullptr : ix->seq_stage.seqs.as<uint8_t>();
+    a.out = h.out.as<uint8_t>();
+  }
+  K4_HIP(ix, hipStreamSynchronize(st));  // (a table about to be replaced may still be read by the batch before)
+  K4_HIP(ix, h.spans.reserve(t.size() * sizeof(K4HSpan)));
+  K4_HIP(ix, hipMemcpyAsync(h.spans.p, t.data(), t.size() * sizeof(K4HSpan), hipMemcpyHostToDevice, st));
   a.ix = ix->d;
-  a.spans = ix->hmm_spans.as<K4HSpan>();
+  a.spans = h.spans.as<K4HSpan>();
   a.n_spans = n;
-  a.seqs = (const uint8_t*)d_seqs;
-  a.out = (uint8_t*)d_out;
   a.p = *p;
   if (a.p.sample_nth <= 0) a.p.sample_nth = 1;
-  K4_HIP(ix, hipEventRecord(ix->hmm_ev[0], st));
+  K4_HIP(ix, h.timer.begin(st));
   for (uint64_t k0 = 0; k0 < total; k0 += K4H_LAUNCH_KMERS) {
     a.k0 = k0;
     a.k1 = std::min<uint64_t>(total, k0 + K4H_LAUNCH_KMERS);
@@ -297,83 +298,36 @@ static int hamming_run(k4_index* ix, const k4_hamming_params* p, const std::vect
     else hipLaunchKernelGGL(k4k_hammings<5>, dim3((unsigned)(a.k1 - a.k0)), dim3(64), 0, st, a);
   }
   K4_HIP(ix, hipGetLastError());
-  K4_HIP(ix, hipEventRecord(ix->hmm_ev[1], st));
+  K4_HIP(ix, h.timer.end(st));
+  if (on_host) K4_HIP(ix, hipMemcpyAsync(hammings, h.out.p, (size_t)hammings_len, hipMemcpyDeviceToHost, st));
   K4_HIP(ix, hipStreamSynchronize(st));
-  float ms = 0;
-  K4_HIP(ix, hipEventElapsedTime(&ms, ix->hmm_ev[0], ix->hmm_ev[1]));
-  ix->hmm_ms = ms;
+  K4_HIP(ix, h.timer.read());
   return K4_OK;
 }
 
 extern "C" int k4_locate_sfx_hammings_batch_dev(k4_index* ix, const k4_hamming_params* p, int64_t n, const uint32_t* entry_ids,
                                                 const uint32_t* entry_locis, const uint32_t* span_lens, const uint64_t* out_offs,
                                                 void* d_hammings, uint64_t hammings_len, void* stream) {
-  int rc = check_hamming_params(ix, p);
-  if (rc != K4_OK) return rc;
-  if (n < 0 || !d_hammings || (n > 0 && (!entry_ids || !entry_locis || !span_lens || !out_offs)))
-    return k4_fail(ix, K4_ERR_INTERNAL, "Hammings: null argument");
-  K4_HIP(ix, hipSetDevice(ix->device));
-  std::vector<K4HSpan> t;
-  if ((rc = hamming_spans(ix, p, n, entry_ids, entry_locis, span_lens, nullptr, out_offs, hammings_len, t)) != K4_OK) return rc;
-  return hamming_run(ix, p, t, nullptr, d_hammings, (hipStream_t)stream);
+  return hamming_batch(ix, p, true, false, n, entry_ids, entry_locis, nullptr, nullptr, span_lens, out_offs, d_hammings, hammings_len,
+                       (hipStream_t)stream);
 }
 
 extern "C" int k4_locate_hammings_batch_dev(k4_index* ix, const k4_hamming_params* p, int64_t n, const void* d_seqs, const uint64_t* offs,
                                             const uint32_t* lens, const uint64_t* out_offs, void* d_hammings, uint64_t hammings_len,
                                             void* stream) {
-  int rc = check_hamming_params(ix, p);
-  if (rc != K4_OK) return rc;
-  if (n < 0 || !d_hammings || !d_seqs || (n > 0 && (!offs || !lens || !out_offs))) return k4_fail(ix, K4_ERR_INTERNAL, "Hammings: null argument");
-  K4_HIP(ix, hipSetDevice(ix->device));
-  std::vector<K4HSpan> t;
-  if ((rc = hamming_spans(ix, p, n, nullptr, nullptr, lens, offs, out_offs, hammings_len, t)) != K4_OK) return rc;
-  return hamming_run(ix, p, t, d_seqs, d_hammings, (hipStream_t)stream);
-}
-
-// the host-pointer forms: the caller's array goes up whole and comes back whole, so the bytes no K-mer owns return as they came
-static int hamming_host(k4_index* ix, const k4_hamming_params* p, const std::vector<K4HSpan>& t, const uint8_t* seqs, uint64_t seq_bytes,
-                        uint8_t* hammings, uint64_t hammings_len) {
-  hipStream_t st = ix->stream;
-  K4_HIP(ix, hipStreamSynchronize(st));
-  K4_HIP(ix, ix->hmm_out.reserve((size_t)hammings_len + 16));
-  K4_HIP(ix, hipMemcpyAsync(ix->hmm_out.p, hammings, (size_t)hammings_len, hipMemcpyHostToDevice, st));
-  if (seqs) {
-    K4_HIP(ix, ix->hmm_seqs.reserve((size_t)seq_bytes + 16));
-    K4_HIP(ix, hipMemcpyAsync(ix->hmm_seqs.p, seqs, (size_t)seq_bytes, hipMemcpyHostToDevice, st));
-  }
-  const int rc = hamming_run(ix, p, t, seqs ? ix->hmm_seqs.p : nullptr, ix->hmm_out.p, st);
-  if (rc != K4_OK) return rc;
-  K4_HIP(ix, hipMemcpyAsync(hammings, ix->hmm_out.p, (size_t)hammings_len, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
-  return K4_OK;
+  return hamming_batch(ix, p, false, false, n, nullptr, nullptr, d_seqs, offs, lens, out_offs, d_hammings, hammings_len, (hipStream_t)stream);
 }
 
 extern "C" int k4_locate_sfx_hammings_batch(k4_index* ix, const k4_hamming_params* p, int64_t n, const uint32_t* entry_ids,
                                             const uint32_t* entry_locis, const uint32_t* span_lens, const uint64_t* out_offs, uint8_t* hammings,
                                             uint64_t hammings_len) {
-  int rc = check_hamming_params(ix, p);
-  if (rc != K4_OK) return rc;
-  if (n < 0 || !hammings || (n > 0 && (!entry_ids || !entry_locis || !span_lens || !out_offs)))
-    return k4_fail(ix, K4_ERR_INTERNAL, "Hammings: null argument");
-  K4_HIP(ix, hipSetDevice(ix->device));
-  std::vector<K4HSpan> t;
-  if ((rc = hamming_spans(ix, p, n, entry_ids, entry_locis, span_lens, nullptr, out_offs, hammings_len, t)) != K4_OK) return rc;
-  if (n == 0) { ix->hmm_ms = 0; return K4_OK; }
-  return hamming_host(ix, p, t, nullptr, 0, hammings, hammings_len);
+  return hamming_batch(ix, p, true, true, n, entry_ids, entry_locis, nullptr, nullptr, span_lens, out_offs, hammings, hammings_len, nullptr);
 }
 
 extern "C" int k4_locate_hammings_batch(k4_index* ix, const k4_hamming_params* p, int64_t n, const uint8_t* seqs, const uint64_t* offs,
                                         const uint32_t* lens, const uint64_t* out_offs, uint8_t* hammings, uint64_t hammings_len) {
-  int rc = check_hamming_params(ix, p);
-  if (rc != K4_OK) return rc;
-  if (n < 0 || !hammings || !seqs || (n > 0 && (!offs || !lens || !out_offs))) return k4_fail(ix, K4_ERR_INTERNAL, "Hammings: null argument");
-  K4_HIP(ix, hipSetDevice(ix->device));
-  std::vector<K4HSpan> t;
-  if ((rc = hamming_spans(ix, p, n, nullptr, nullptr, lens, offs, out_offs, hammings_len, t)) != K4_OK) return rc;
-  if (n == 0) { ix->hmm_ms = 0; return K4_OK; }
-  uint64_t bytes = 0;
-  for (int64_t i = 0; i < n; i++) bytes = std::max<uint64_t>(bytes, offs[i] + lens[i]);
-  return hamming_host(ix, p, t, seqs, bytes, hammings, hammings_len);
+  return hamming_batch(ix, p, false, true, n, nullptr, nullptr, seqs, offs, lens, out_offs, hammings, hammings_len, nullptr);
 }
 
-extern "C" double k4_hamming_last_kernel_ms(const k4_index* ix) { return ix ? ix->hmm_ms : 0.0; }
+extern "C" double k4_hamming_last_kernel_ms(const k4_index* ix) { return ix ? ix->hmm.timer.ms : 0.0; }
+

@@ -848,15 +848,9 @@ extern "C" void k4_close(k4_index* ix) {
   for (hipEvent_t e : ix->ev0) hipEventDestroy(e);
   for (hipEvent_t e : ix->ev1) hipEventDestroy(e);
   for (hipEvent_t e : ix->ev2) hipEventDestroy(e);
-  for (hipEvent_t e : ix->qry_ev)
-    if (e) hipEventDestroy(e);
-  for (hipEvent_t e : ix->blz_ev)
-    if (e) hipEventDestroy(e);
-  for (hipEvent_t e : ix->hmm_ev)
-    if (e) hipEventDestroy(e);
   k4_pool_trim_current_device();  // the ingest / emit stages' cached scratch (k4_pool.h)
   if (ix->ws.h_small) hipHostFree(ix->ws.h_small);
-  delete ix;  // (every device block of the index and its workspaces is a K4DevBuf member)
+  delete ix;  // (every device block of the index and its workspaces is a K4DevBuf member, the search calls' events K4Timer members)
 }
 
 // ---- accessors ------------------------------------------------------------------------------------------------
@@ -881,6 +875,15 @@ extern "C" int k4_get_entry(const k4_index* ix, uint32_t entry_id, k4_entry* out
   if (entry_id < 1 || entry_id > ix->entries.size()) return K4_ERR_ENTRY;
   *out = ix->entries[entry_id - 1];
   return K4_OK;
+}
+
+// the entry that carries entry_id, wherever it sits (k4_get_entry above takes the id for the place in the table)
+const k4_entry* k4i_entry_by_id(const k4_index* ix, uint32_t entry_id) {
+  if (entry_id == 0) return nullptr;
+  if (entry_id <= ix->entries.size() && ix->entries[entry_id - 1].entry_id == entry_id) return &ix->entries[entry_id - 1];
+  for (const k4_entry& e : ix->entries)
+    if (e.entry_id == entry_id) return &e;
+  return nullptr;
 }
 
 extern "C" int k4_get_ident(const k4_index* ix, const char* name) {  // CSfxArray::GetIdent: case-insensitive

@@ -88,6 +88,29 @@ struct K4Workspace {
   int32_t* c_out = nullptr; k4_hit* c_hits = nullptr; bool c_small = false;
 };
 
+// The sequence batch of a host-pointer search call on the device (k4s_stage_seqs, k4_stage.h), grow-only: LocateQuerySeqs, blitz's
+// path stage and LocateHammings put their sequences here, the first two also the node table that goes from one to the other
+struct K4SeqStage { K4DevBuf seqs, offs, lens, node_offs, nodes; };
+// LocateQuerySeqs (k4_query.hip), grow-only: per-query node slices and counts (cap_queries x cap_slice slots; the counts end with
+// the zero the offsets' scan reads), the scan's temporary
+struct K4QueryState {
+  K4DevBuf ws, cnt;
+  int64_t cap_queries = 0;
+  uint64_t cap_slice = 0;
+  K4Scratch<K4DevBuf> scan;
+  K4Timer timer;
+};
+// blitz's path stage (k4_blitz.hip), grow-only: the sort's keys and values, the query of each node, the sorted nodes with their
+// scores, the group and head lists, the chosen heads, per-query path counts and offsets, the path records with their block counts
+// and offsets; then the outputs of the host-pointer entry point
+struct K4BlitzState {
+  K4DevBuf keys[2], vals[2], qi, nodes, list, heads, sel, cnt, offs, paths, nb, boffs;
+  K4DevBuf out_offs, out_paths, out_blocks;
+  K4Timer timer;
+};
+// restricted Hammings (k4_hamming.hip), grow-only: the span table of a batch, then the caller's byte array of the host-pointer forms
+struct K4HammState { K4DevBuf spans, out; K4Timer timer; };
+
 struct k4_index {
   int device = 0;
   K4DevIndex d{};
@@ -126,25 +149,11 @@ struct k4_index {
   int32_t pe_cap_hits = 0;
   // staging of k4_mate_rescue_batch (grow-only)
   K4DevBuf rs_tasks, rs_reads, rs_res, rs_hits;
-  // LocateQuerySeqs (k4_query.hip): per-query node slices and counts (qry_cap_queries x qry_cap_slice slots), grow-only; then the
-  // staging of the host-pointer entry point
-  K4DevBuf qry_ws, qry_cnt;
-  int64_t qry_cap_queries = 0;
-  uint64_t qry_cap_slice = 0;
-  K4DevBuf qry_seqs, qry_offs, qry_lens, qry_node_offs, qry_nodes;
-  hipEvent_t qry_ev[2] = {nullptr, nullptr};
-  double qry_ms = 0;
-  // blitz's path stage (k4_blitz.hip), grow-only: the sort's keys and values, the query of each node, the sorted nodes with their
-  // scores, the group and head lists, the chosen heads, per-query path counts and offsets, the path records with their block counts
-  // and offsets; then the outputs of the host-pointer entry point (its inputs go through the qry_* staging above)
-  K4DevBuf blz_keys[2], blz_vals[2], blz_qi, blz_nodes, blz_list, blz_heads, blz_sel, blz_cnt, blz_offs, blz_paths, blz_nb, blz_boffs;
-  K4DevBuf blz_out_offs, blz_out_paths, blz_out_blocks;
-  hipEvent_t blz_ev[2] = {nullptr, nullptr};
-  double blz_ms = 0;
-  // restricted Hammings (k4_hamming.hip), grow-only: the span table of a batch, then the staging of the host-pointer entry points
-  K4DevBuf hmm_spans, hmm_seqs, hmm_out;
-  hipEvent_t hmm_ev[2] = {nullptr, nullptr};
-  double hmm_ms = 0;
+  // the search-call families (DESIGN.md "Search-call families: shared scaffold"); their host-pointer forms share one staged batch
+  K4SeqStage seq_stage;
+  K4QueryState qry;
+  K4BlitzState blz;
+  K4HammState hmm;
   // k4_open_async: the arrays are uploaded and the device structures built by this thread; k4_open_wait joins it
   std::thread loader;
   int load_rc = 0;
@@ -161,6 +170,7 @@ int k4_check_hip(k4_index* ix, hipError_t e, const char* what);
 
 // k4_index.hip
 int k4i_build_device_structures(k4_index* ix, const void* d_seq_bytes, int kmer_k);
+const k4_entry* k4i_entry_by_id(const k4_index* ix, uint32_t entry_id);  // null when the table holds no such id
 // k4_align.hip
 #define K4_SMALL_STAGE (4u << 20)
 #define K4_SMALL_READS 4096

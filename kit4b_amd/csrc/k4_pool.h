@@ -162,3 +162,43 @@ struct K4DevBuf {
   hipError_t reserve(size_t bytes) { return p && cap >= bytes ? hipSuccess : alloc(bytes); }
   template <typename T> T* as() const { return (T*)p; }
 };
+
+// The device time of an entry point's last call, owned like a K4DevBuf (`delete ix` destroys the events).  The entry point calls
+// reset() first, so a call that fails or has no work reports 0; it brackets its launches with begin() and end() on their stream
+// and, behind its own synchronise of that stream, calls read().  end() and read() do nothing for a section that never began.
+struct K4Timer {
+  hipEvent_t ev[2] = {nullptr, nullptr};  // made by the first begin()
+  double ms = 0;
+  bool open = false;
+  K4Timer() = default;
+  K4Timer(const K4Timer&) = delete;
+  K4Timer& operator=(const K4Timer&) = delete;
+  ~K4Timer() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  void reset() { ms = 0; open = false; }
+  hipError_t begin(hipStream_t st) {
+    hipError_t rc = hipSuccess;
+    for (hipEvent_t& e : ev)
+      if (!e && rc == hipSuccess) rc = hipEventCreate(&e);
+    open = rc == hipSuccess;
+    return open ? hipEventRecord(ev[0], st) : rc;
+  }
+  hipError_t end(hipStream_t st) { return open ? hipEventRecord(ev[1], st) : hipSuccess; }
+  hipError_t read() {
+    float f = 0;
+    const hipError_t rc = open ? hipEventElapsedTime(&f, ev[0], ev[1]) : hipSuccess;
+    open = false;
+    ms = f;
+    return rc;
+  }
+};
+
+// The temporary of a rocPRIM call (k4_stage.h).  Every wrapper there makes one and lets go of it when it returns; a caller that
+// repeats a call hands in one that it keeps instead (k4s_exclusive_scan).
+template <typename B>
+struct K4Scratch {
+  B buf;
+  size_t bytes = 0;
+};

@@ -7,7 +7,7 @@
 // nodes accepted before the chunk and extends it when it is not held by one; lane 0 then replays the chunk in order (containment
 // against the nodes accepted inside the chunk, the redundancy rules, the append).  DESIGN.md "LocateQuerySeqs" has the rest.
 #include <algorithm>
-#include "k4_device.h"
+#include "k4_stage.h"
 
 #define K4Q_CHAINS 256  // TargHash: (TargSeqID & 0x7f) << 1 | strand
 #define K4Q_MAX_WS_BYTES (16ull << 30)
@@ -29,7 +29,7 @@ struct K4QueryArgs {
   K4QNode* ws;
   uint64_t slice;      // node slots per query
   uint32_t max_len;    // the query length the slices were sized for: a longer query yields nothing
-  uint32_t* cnt;      // [2 n]: NumMatches, then the nodes left after the compaction
+  uint32_t* cnt;      // [2 n]: NumMatches, then the nodes left after the compaction (the host puts a zero behind them for its scan)
 };
 
 // :6605-6623: is the core (query offset ofs, locus loci of target tid) inside a node of the chain that starts at node id idx, on
@@ -135,14 +135,7 @@ __global__ void __launch_bounds__(64) k4k_query_locate(K4QueryArgs a) {
         cnt = k4q_count<EL>(a.ix, tb, qs, ci * delta, (int)cl, max_iter, first);
         if (cnt >= max_iter) cnt = 0;  // :6590
       }
-      uint32_t x = cnt;
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, (unsigned)d, 64);
-        if (lane >= d) x += y;
-      }
-      g_first[lane] = first;
-      g_pre[lane] = x - cnt;
-      if (lane == 63) g_pre[64] = x;
+      k4d_runs_layout(lane, first, cnt, g_first, g_pre);
       __syncthreads();
       const uint32_t total = g_pre[64];
       // 2. the candidates in the reference's order, 64 at a time
@@ -151,13 +144,10 @@ __global__ void __launch_bounds__(64) k4k_query_locate(K4QueryArgs a) {
         const uint32_t nm0 = s_nm;
         bool ok = false;
         if (g < total) {
-          int lo = 0, hi = 63;  // the last core whose candidates start at or before g
-          while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (g_pre[mid] <= g) lo = mid; else hi = mid - 1;
-          }
-          const uint32_t ofs = (gb + (uint32_t)lo) * delta;
-          const uint64_t pos = k4d_sa_at<EL>(a.ix, g_first[lo] + (g - g_pre[lo]));
+          uint32_t core, occ;
+          k4d_runs_locate(g, 63u, g_pre, core, occ);  // (the lanes behind the group's last core hold no candidate)
+          const uint32_t ofs = (gb + core) * delta;
+          const uint64_t pos = k4d_sa_at<EL>(a.ix, g_first[core] + occ);
           uint64_t e_start, e_end;
           const int e = k4d_map_entry_slow(a.ix, ent_in_lds ? ent_s : nullptr, pos, e_start, e_end);
           if (e >= 0) {
@@ -225,25 +215,6 @@ __global__ void __launch_bounds__(64) k4k_query_locate(K4QueryArgs a) {
   if (lane == 0) { a.cnt[qi] = nm; a.cnt[a.n + qi] = kept; }
 }
 
-// node_offs[0 .. n] from the per-query counts: one block
-__global__ void __launch_bounds__(256) k4k_query_offsets(const uint32_t* __restrict__ kept, int64_t n, uint64_t* __restrict__ node_offs) {
-  __shared__ uint64_t part[256];
-  const int t = threadIdx.x;
-  const int64_t per = (n + 255) / 256, b = t * per < n ? t * per : n, e = b + per < n ? b + per : n;
-  uint64_t sum = 0;
-  for (int64_t i = b; i < e; i++) sum += kept[i];
-  part[t] = sum;
-  __syncthreads();
-  if (t == 0) {
-    uint64_t acc = 0;
-    for (int q = 0; q < 256; q++) { const uint64_t v = part[q]; part[q] = acc; acc += v; }
-    node_offs[n] = acc;
-  }
-  __syncthreads();
-  uint64_t acc = part[t];
-  for (int64_t i = b; i < e; i++) { node_offs[i] = acc; acc += kept[i]; }
-}
-
 // :6803-6824: the nodes that are not flagged, in slice order, behind one another; nothing when they do not all fit
 __global__ void __launch_bounds__(64) k4k_query_gather(const K4QNode* __restrict__ ws_all, uint64_t slice, const uint32_t* __restrict__ cnt,
                                                        int64_t n, const uint64_t* __restrict__ node_offs, k4_query_node* __restrict__ nodes,
@@ -293,20 +264,21 @@ extern "C" int k4_query_reserve(k4_index* ix, const k4_query_params* p, int64_t 
   if (rc != K4_OK) return rc;
   if (max_queries < 0 || max_queries >= 0x7FFFFFFFll) return k4_fail(ix, K4_ERR_PARAMS, "LocateQuerySeqs: at most 2^31-2 queries per batch");
   K4_HIP(ix, hipSetDevice(ix->device));
+  K4QueryState& q = ix->qry;
   const uint64_t slice = query_slice(p, max_query_len);
-  if (max_queries <= ix->qry_cap_queries && slice <= ix->qry_cap_slice) return K4_OK;
-  const int64_t nq = std::max<int64_t>(std::max<int64_t>(max_queries, ix->qry_cap_queries), 1);
-  const uint64_t sl = std::max<uint64_t>(slice, ix->qry_cap_slice);
+  if (max_queries <= q.cap_queries && slice <= q.cap_slice) return K4_OK;
+  const int64_t nq = std::max<int64_t>(std::max<int64_t>(max_queries, q.cap_queries), 1);
+  const uint64_t sl = std::max<uint64_t>(slice, q.cap_slice);
   if ((uint64_t)nq * sl > K4Q_MAX_WS_BYTES / sizeof(K4QNode))
     return k4_fail(ix, K4_ERR_MEM, "LocateQuerySeqs: %lld queries x %llu node slots exceed the %llu GiB workspace limit: split the batch or lower max_hits",
                    (long long)nq, (unsigned long long)sl, (unsigned long long)(K4Q_MAX_WS_BYTES >> 30));
-  ix->qry_cap_queries = 0;  // (zero until both have grown, K4DevBuf::reserve)
-  ix->qry_cap_slice = 0;
+  q.cap_queries = 0;  // (zero until both have grown, K4DevBuf::reserve)
+  q.cap_slice = 0;
   K4_HIP(ix, hipDeviceSynchronize());  // (a block about to be replaced may still be read by a batch on a caller's stream)
-  K4_HIP(ix, ix->qry_ws.reserve((size_t)nq * sl * sizeof(K4QNode)));
-  K4_HIP(ix, ix->qry_cnt.reserve((size_t)nq * 2 * sizeof(uint32_t)));
-  ix->qry_cap_queries = nq;
-  ix->qry_cap_slice = sl;
+  K4_HIP(ix, q.ws.reserve((size_t)nq * sl * sizeof(K4QNode)));
+  K4_HIP(ix, q.cnt.reserve(((size_t)nq * 2 + 1) * sizeof(uint32_t)));
+  q.cap_queries = nq;
+  q.cap_slice = sl;
   return K4_OK;
 }
 
@@ -315,37 +287,36 @@ extern "C" int k4_locate_query_seqs_batch_dev(k4_index* ix, const k4_query_param
                                               void* stream) {
   int rc = check_query_params(ix, p);
   if (rc != K4_OK) return rc;
+  K4QueryState& q = ix->qry;
+  q.timer.reset();
   if (n < 0 || !d_node_offs || (n > 0 && (!d_seqs || !d_offs || !d_lens))) return k4_fail(ix, K4_ERR_PARAMS, "LocateQuerySeqs: null argument");
   if (nodes_cap > 0 && !d_nodes) return k4_fail(ix, K4_ERR_PARAMS, "LocateQuerySeqs: nodes_cap without nodes");
   if ((rc = k4_query_reserve(ix, p, n, max_query_len)) != K4_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  for (hipEvent_t& e : ix->qry_ev)
-    if (!e) K4_HIP(ix, hipEventCreate(&e));
+  uint64_t* node_offs = (uint64_t*)d_node_offs;
   K4QueryArgs a;
   a.ix = ix->d;
   a.seqs = (const uint8_t*)d_seqs; a.offs = (const uint64_t*)d_offs; a.lens = (const uint32_t*)d_lens;
   a.n = n; a.p = *p;
-  a.ws = ix->qry_ws.as<K4QNode>();
+  a.ws = q.ws.as<K4QNode>();
   a.slice = query_slice(p, max_query_len);
   a.max_len = max_query_len;
-  a.cnt = ix->qry_cnt.as<uint32_t>();
-  K4_HIP(ix, hipEventRecord(ix->qry_ev[0], st));
-  if (n > 0) {
+  a.cnt = q.cnt.as<uint32_t>();
+  if (n > 0) {  // (a batch of no queries has no work to time)
+    K4_HIP(ix, q.timer.begin(st));
     if (ix->d.el == 4) hipLaunchKernelGGL(k4k_query_locate<4>, dim3((unsigned)n), dim3(64), 0, st, a);
     else hipLaunchKernelGGL(k4k_query_locate<5>, dim3((unsigned)n), dim3(64), 0, st, a);
   }
-  hipLaunchKernelGGL(k4k_query_offsets, dim3(1), dim3(256), 0, st, a.cnt + n, n, (uint64_t*)d_node_offs);
+  // node_offs[0 .. n] from the counts of the nodes kept, cnt[n .. 2 n), and a zero behind them
+  K4_HIP(ix, hipMemsetAsync(a.cnt + 2 * n, 0, 4, st));
+  K4_TRY(k4s_exclusive_scan<K4DevBuf>(ix, a.cnt + n, node_offs, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st, &q.scan));
   if (n > 0)
-    hipLaunchKernelGGL(k4k_query_gather, dim3((unsigned)n), dim3(64), 0, st, a.ws, a.slice, a.cnt, n, (const uint64_t*)d_node_offs,
-                       (k4_query_node*)d_nodes, nodes_cap);
+    hipLaunchKernelGGL(k4k_query_gather, dim3((unsigned)n), dim3(64), 0, st, a.ws, a.slice, a.cnt, n, node_offs, (k4_query_node*)d_nodes, nodes_cap);
   K4_HIP(ix, hipGetLastError());
-  K4_HIP(ix, hipEventRecord(ix->qry_ev[1], st));
+  K4_HIP(ix, q.timer.end(st));
   uint64_t total = 0;
-  K4_HIP(ix, hipMemcpyAsync(&total, (const uint64_t*)d_node_offs + n, 8, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
-  float ms = 0;
-  K4_HIP(ix, hipEventElapsedTime(&ms, ix->qry_ev[0], ix->qry_ev[1]));
-  ix->qry_ms = ms;
+  K4_TRY(k4s_read_back(ix, &total, node_offs + n, st));
+  K4_HIP(ix, q.timer.read());
   if (total > nodes_cap)
     return k4_fail(ix, K4_ERR_MEM, "LocateQuerySeqs: %llu nodes found, nodes_cap is %llu", (unsigned long long)total, (unsigned long long)nodes_cap);
   return K4_OK;
@@ -355,35 +326,24 @@ extern "C" int k4_locate_query_seqs_batch(k4_index* ix, const k4_query_params* p
                                           const uint32_t* lens, uint64_t* node_offs, k4_query_node* nodes, uint64_t nodes_cap) {
   int rc = check_query_params(ix, p);
   if (rc != K4_OK) return rc;
+  ix->qry.timer.reset();
   if (n < 0 || !node_offs || (n > 0 && (!seqs || !offs || !lens)) || (nodes_cap > 0 && !nodes))
     return k4_fail(ix, K4_ERR_PARAMS, "LocateQuerySeqs: null argument");
   K4_HIP(ix, hipSetDevice(ix->device));
-  uint64_t bytes = 0;
-  uint32_t max_len = 0;
-  for (int64_t i = 0; i < n; i++) {
-    bytes = std::max<uint64_t>(bytes, offs[i] + lens[i]);
-    max_len = std::max(max_len, lens[i]);
-  }
+  K4SeqStage& s = ix->seq_stage;
   hipStream_t st = ix->stream;
+  uint32_t max_len = 0;
+  K4_TRY(k4s_stage_seqs(ix, n, seqs, offs, lens, &max_len));
   if ((rc = k4_query_reserve(ix, p, n, max_len)) != K4_OK) return rc;  // (so that K4_ERR_MEM below can only mean nodes_cap)
-  K4_HIP(ix, ix->qry_seqs.reserve((size_t)bytes + 16));
-  K4_HIP(ix, ix->qry_offs.reserve((size_t)(n + 1) * 8));
-  K4_HIP(ix, ix->qry_lens.reserve((size_t)(n + 1) * 4));
-  K4_HIP(ix, ix->qry_node_offs.reserve((size_t)(n + 1) * 8));
-  K4_HIP(ix, ix->qry_nodes.reserve((size_t)std::max<uint64_t>(nodes_cap, 1) * sizeof(k4_query_node)));
-  if (n > 0) {
-    K4_HIP(ix, hipMemcpyAsync(ix->qry_seqs.p, seqs, (size_t)bytes, hipMemcpyHostToDevice, st));
-    K4_HIP(ix, hipMemcpyAsync(ix->qry_offs.p, offs, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    K4_HIP(ix, hipMemcpyAsync(ix->qry_lens.p, lens, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  }
-  rc = k4_locate_query_seqs_batch_dev(ix, p, n, max_len, ix->qry_seqs.p, ix->qry_offs.p, ix->qry_lens.p, ix->qry_node_offs.p, ix->qry_nodes.p,
-                                      nodes_cap, st);
+  K4_HIP(ix, s.node_offs.reserve((size_t)(n + 1) * 8));
+  K4_HIP(ix, s.nodes.reserve((size_t)std::max<uint64_t>(nodes_cap, 1) * sizeof(k4_query_node)));
+  rc = k4_locate_query_seqs_batch_dev(ix, p, n, max_len, s.seqs.p, s.offs.p, s.lens.p, s.node_offs.p, s.nodes.p, nodes_cap, st);
   if (rc != K4_OK && rc != K4_ERR_MEM) return rc;
-  K4_HIP(ix, hipMemcpyAsync(node_offs, ix->qry_node_offs.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+  K4_HIP(ix, hipMemcpyAsync(node_offs, s.node_offs.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
   K4_HIP(ix, hipStreamSynchronize(st));
   if (rc != K4_OK) return rc;
-  if (node_offs[n]) K4_HIP(ix, hipMemcpy(nodes, ix->qry_nodes.p, (size_t)node_offs[n] * sizeof(k4_query_node), hipMemcpyDeviceToHost));
+  if (node_offs[n]) K4_HIP(ix, hipMemcpy(nodes, s.nodes.p, (size_t)node_offs[n] * sizeof(k4_query_node), hipMemcpyDeviceToHost));
   return K4_OK;
 }
 
-extern "C" double k4_query_last_kernel_ms(const k4_index* ix) { return ix ? ix->qry_ms : 0.0; }
+extern "C" double k4_query_last_kernel_ms(const k4_index* ix) { return ix ? ix->qry.timer.ms : 0.0; }

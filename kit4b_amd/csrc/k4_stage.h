@@ -9,6 +9,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>  // (rocprim/iterator/texture_cache_iterator.hpp calls memset without it)
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -28,6 +29,29 @@ int k4s_read_back(k4_index* ix, T* host, const void* dev, hipStream_t st) {
   static_assert(std::is_trivially_copyable<T>::value, "k4s_read_back copies bytes");
   K4_HIP(ix, hipMemcpyAsync(host, dev, sizeof(T), hipMemcpyDeviceToHost, st));
   K4_HIP(ix, hipStreamSynchronize(st));
+  return K4_OK;
+}
+
+// The sequence batch of a host-pointer search call (sequence i: lens[i] bytes at seqs + offs[i]) sent up on the index's stream into
+// ix->seq_stage; *max_len (may be null) = the longest.  The buffers grow without a wait: only that stream uses them, and every call
+// that does ends with it waited for.
+inline int k4s_stage_seqs(k4_index* ix, int64_t n, const uint8_t* seqs, const uint64_t* offs, const uint32_t* lens, uint32_t* max_len) {
+  uint64_t bytes = 0;
+  uint32_t longest = 0;
+  for (int64_t i = 0; i < n; i++) {
+    bytes = bytes > offs[i] + lens[i] ? bytes : offs[i] + lens[i];
+    longest = longest > lens[i] ? longest : lens[i];
+  }
+  if (max_len) *max_len = longest;
+  K4SeqStage& s = ix->seq_stage;
+  K4_HIP(ix, s.seqs.reserve((size_t)bytes + 16));
+  K4_HIP(ix, s.offs.reserve((size_t)(n + 1) * 8));
+  K4_HIP(ix, s.lens.reserve((size_t)(n + 1) * 4));
+  if (n > 0) {
+    K4_HIP(ix, hipMemcpyAsync(s.seqs.p, seqs, (size_t)bytes, hipMemcpyHostToDevice, ix->stream));
+    K4_HIP(ix, hipMemcpyAsync(s.offs.p, offs, (size_t)n * 8, hipMemcpyHostToDevice, ix->stream));
+    K4_HIP(ix, hipMemcpyAsync(s.lens.p, lens, (size_t)n * 4, hipMemcpyHostToDevice, ix->stream));
+  }
   return K4_OK;
 }
 
@@ -56,15 +80,7 @@ inline int k4s_read_set(k4_index* ix, int pe, int64_t n, const void* d_rr, const
   return K4_OK;
 }
 
-// The temporary of a rocPRIM call.  Every wrapper below makes one and lets go of it when it returns; a caller that repeats a
-// call in a loop hands in one that it keeps instead (k4s_exclusive_scan).
-template <typename B>
-struct K4Scratch {
-  B buf;
-  size_t bytes = 0;
-};
-
-// rocPRIM's two calls: `call(tmp, bytes)` is the rocPRIM function with the rest of its arguments bound; a null tmp asks for the size
+// rocPRIM's two calls (K4Scratch, the temporary, is in k4_pool.h): `call(tmp, bytes)` is the rocPRIM function with the rest of its arguments bound; a null tmp asks for the size
 template <typename B, typename F>
 int k4s_two_calls(k4_index* ix, const char* what, F call, K4Scratch<B>* keep = nullptr, bool size_only = false) {
   K4Scratch<B> own;

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import blitz_ref
 import hamm_craft as hc
 import hamm_ref
 import manytargets as mt
@@ -159,6 +160,51 @@ def test_mixed_batch_equals_the_restatement(k4, ix, ref_index):
             ix.sfx_hammings(bad, klen, out=out, out_offs=np.zeros(len(bad), np.uint64), **_kw(p))
         assert e.value.code == -1
     assert (out == 0xAB).all()
+
+
+def test_host_pointer_calls_of_the_three_families_share_their_staging(k4, sfx_path, ref_index):
+    """on a fresh handle: LocateHammings over a short batch, LocateQuerySeqs, blitz's path stage, LocateHammings over a longer batch
+    (the staged batch grows): each the restatement's answer, so no family reads what another left in the shared buffers; then each
+    family's device time is 0 behind a batch of nothing"""
+    _, ts = hc.targets()
+    klen, rhamm, mn, mx = 24, 2, 3, 4
+    x = k4.SfxIndex.open(sfx_path)
+    try:
+        def hamm(seqs):
+            got = x.hammings(seqs, klen, rhamm, mn, mx, both_strands=True)
+            for s, g in zip(seqs, got):
+                want = np.full(len(s), 0xFF, dtype=np.uint8)
+                assert hamm_ref.locate_hammings(ref_index, rhamm, True, klen, 1, s, mn, mx, 0, want) == 0
+                assert np.array_equal(g, want), (len(s), g, want)
+            return got
+
+        near = ts[0][400:400 + klen + 3].copy()
+        near[5] = (near[5] + 1) % 4
+        short = hamm([near, ts[2][50:50 + klen + 3].copy()])
+        assert int(short[0][0]) == 1 and int(short[1][0]) == 0 and x.hamming_kernel_ms() > 0
+        qs = [ts[1][100:400].copy(), query_ref.revcomp(ts[3][700:900]), ts[0][2000:2090].copy()]
+        lp = (20, 10, 0, 1000, 100, 1, 3)
+        nodes = x.locate_query_seqs(qs, *lp)
+        want_nodes = [query_ref.locate_query_seqs(ref_index, q, *lp) for q in qs]
+        assert [[tuple(int(r[f]) for f in query_ref.NODE_FIELDS) for r in a] for a in nodes] == want_nodes and all(want_nodes)
+        assert x.query_kernel_ms() > 0
+        path_offs, paths, blocks = x.blitz_paths(qs, None, nodes)
+        want_paths, want_blocks = [], []
+        for i, q in enumerate(qs):
+            ps, bs = blitz_ref.blitz_paths(ref_index, q, want_nodes[i], query_idx=i)
+            want_paths += [p[:16] + (p[16] + len(want_blocks),) for p in ps]
+            want_blocks += bs
+        assert [tuple(int(r[f]) for f in blitz_ref.PATH_FIELDS) for r in paths] == want_paths and len(want_paths) == len(qs)
+        assert [tuple(int(r[f]) for f in blitz_ref.BLOCK_FIELDS) for r in blocks] == want_blocks
+        assert [int(v) for v in path_offs] == [0, 1, 2, 3] and k4.lib().k4_blitz_last_kernel_ms(x.h) > 0
+        far = ts[3][3000:3120].copy()
+        far[::7] = (far[::7] + 2) % 4
+        hamm([ts[0][280:400].copy(), far, ts[1][1900:2000].copy(), near])
+        assert x.hammings([], klen, rhamm, mn, mx) == [] and x.hamming_kernel_ms() == 0
+        assert x.locate_query_seqs([], *lp) == [] and x.query_kernel_ms() == 0
+        assert len(x.blitz_paths([], None, [])[1]) == 0 and k4.lib().k4_blitz_last_kernel_ms(x.h) == 0
+    finally:
+        x.close()
 
 
 def test_parameter_errors(k4, ix):

@@ -127,6 +127,31 @@ def test_mixed_batch_equals_each_query_alone_and_the_restatement(ix, ref_index, 
     assert sum(len(a) for a in got) > (0 if strand == 2 else 5)  # (one query of the batch is a reverse complement, the others are not)
 
 
+def test_batches_without_a_core_give_all_zero_offsets(k4, ix):
+    """a batch of no queries, and one whose queries are all no longer than core_len: node_offs comes back all zero and no node is
+    written; then a batch one query shorter than the one before it, whose total is read where that one kept a count"""
+    L = k4.lib()
+    p = k4.QueryParams(*qc._p())
+    core_len = dict(zip(qc.PARAM_NAMES, qc._p()))["core_len"]
+    rng = np.random.default_rng(11)
+    for qs in ([], [rng.integers(0, 4, m).astype(np.uint8) for m in (0, 1, core_len - 1, core_len, core_len)]):
+        cat, offs, lens = k4._flatten(qs)
+        cat = np.concatenate([cat, np.zeros(16, np.uint8)])
+        n = len(qs)
+        node_offs = np.full(n + 1, 0xEEEEEEEEEEEEEEEE, dtype=np.uint64)
+        nodes = np.full(8 * 28, 0xEE, dtype=np.uint8).view(k4.QUERY_NODE_DTYPE)
+        assert L.k4_locate_query_seqs_batch(ix.h, C.byref(p), n, cat.ctypes.data, offs.ctypes.data, lens.ctypes.data, node_offs.ctypes.data,
+                                            nodes.ctypes.data, len(nodes)) == 0
+        assert not node_offs.any() and (nodes.view(np.uint8) == 0xEE).all(), n
+        got = ix.locate_query_seqs(qs, **_params(qc._p()))
+        assert len(got) == n and all(len(a) == 0 for a in got)
+    qs, pq = qc.batch()
+    full = ix.locate_query_seqs(qs, **_params(pq))
+    assert len(full[len(qs) - 2]) > 0  # (its count sits where the shorter batch's scan ends)
+    part = ix.locate_query_seqs(qs[:-1], **_params(pq))
+    assert [_rows(a) for a in part] == [_rows(a) for a in full[:-1]]
+
+
 @pytest.fixture(scope="module")
 def built(k4, oracle):
     made = []

@@ -10,6 +10,7 @@
 #ifndef K4_SFXARRAY_HPP
 #define K4_SFXARRAY_HPP
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <condition_variable>
@@ -88,7 +89,27 @@ typedef struct TAG_sQueryAlignNodes {  // libkit4b/SfxArray.h:149-165 (41 bytes)
   uint32_t NxtHashMatch;
 } tsQueryAlignNodes;
 #pragma pack()
+const int cMaxCultivars = 20000;         // libkit4b/SfxArray.h:186-189
+const int cMinCultivarPreSufLen = 5;
+const int cMaxCultivarPreSufLen = 200;
+const int cTotCultivarKMerLen = 300;
+typedef struct TAG_sKMerCultCnts {  // libkit4b/SfxArray.h:262-266
+  uint32_t EntryID;
+  uint32_t SenseCnts;
+  uint32_t AntisenseCnts;
+} tsKMerCultDist;
+typedef struct TAG_sKMerCultsCnts {  // libkit4b/SfxArray.h:268-275
+  uint64_t SenseCnts;
+  uint64_t AntisenseCnts;
+  uint32_t NumCultivars;
+  uint32_t TotCultivars;
+  etSeqBase KMerSeq[cTotCultivarKMerLen + 1];
+  tsKMerCultDist CultCnts[cMaxCultivars];
+} tsKMerCultsCnts;
 #endif  // K4_HAVE_KIT4B_TYPES
+static_assert(sizeof(tsKMerCultDist) == 12 && sizeof(tsKMerCultsCnts) == 240328 && offsetof(tsKMerCultsCnts, CultCnts) == 328 &&
+                  offsetof(tsKMerCultsCnts, KMerSeq) == 24,
+              "layouts must match libkit4b");
 static_assert(sizeof(tsSegLoci) == 23 && sizeof(tsHitLoci) == 50 && sizeof(tsSfxHeaderV3) == 1224, "layouts must match libkit4b");
 static_assert(sizeof(tsQueryAlignNodes) == 41, "layouts must match libkit4b");
 
@@ -226,6 +247,22 @@ class CSfxArray {
     const char* m = m_pIdx ? k4_last_error(m_pIdx) : k4_global_error();
     m_Errs.push_back(m ? m : "");
     return rc;
+  }
+  // n symbols of the concatenation from offset psn, for GenKMerCultThreadRange: what lies behind the end of psn's sequence reads as
+  // `fill`, a code that is no base
+  void ConcatBases(uint64_t psn, int n, etSeqBase fill, std::vector<etSeqBase>& out) {
+    out.assign((size_t)n, fill);
+    k4_info_t inf;
+    if (k4_info(m_pIdx, &inf) != K4_OK) return;
+    uint32_t lo = 1, hi = inf.n_entries;
+    while (lo <= hi) {  // (the table is sorted by start_ofs, entry ids 1..n in that order)
+      const uint32_t mid = (lo + hi) / 2;
+      k4_entry e;
+      if (k4_get_entry(m_pIdx, mid, &e) != K4_OK) return;
+      if (e.start_ofs > psn) hi = mid - 1;
+      else if (e.start_ofs + e.seq_len <= psn) lo = mid + 1;
+      else { k4_get_seq(m_pIdx, mid, (uint32_t)(psn - e.start_ofs), out.data(), (uint32_t)n); return; }
+    }
   }
   // the flat records -> tsHitLoci as LocateCoreMultiples (SfxArray.cpp:6264-6307, chimeric :6123-6146), LocateInDels
   // (:7800-7825) and LocateSpliceJuncts (:7501-7516) leave it
@@ -462,6 +499,87 @@ class CSfxArray {
       h->TargSeqID = n.targ_seq_id; h->TargSeqLoci = n.targ_loci; h->NumMismatches = n.n_mismatches;
     }
     return (int)rq.nodes.size();
+  }
+
+  // CSfxArray::GenKMerCultThreadRange, SfxArray.cpp:2733-2801, on the host from the few elements and bases it looks at.  As there,
+  // the inclusive end it returns is the first element of the NEXT K-mer, so a K-mer that straddles two ranges is located by both.
+  int GenKMerCultThreadRange(int KMerLen, int ThreadInst, int NumThreads, int64_t StartSfxIdx, int64_t* pEndSfxIdx) {
+    if (NumThreads < 1 || NumThreads > 64 || ThreadInst < 1 || ThreadInst > NumThreads || StartSfxIdx < 0 || pEndSfxIdx == nullptr) return -1;
+    *pEndSfxIdx = 0;
+    k4_info_t inf;
+    if (!m_pIdx || k4_info(m_pIdx, &inf) != K4_OK) return -1;
+    const int64_t NumSfxEls = (int64_t)inf.concat_len;
+    if (StartSfxIdx >= NumSfxEls) return -1;
+    if ((NumSfxEls - StartSfxIdx) < 50000) { *pEndSfxIdx = NumSfxEls - 1; return 1; }
+    int64_t PutativeEndSfxEl = StartSfxIdx + (NumSfxEls - StartSfxIdx) / (1 + NumThreads - ThreadInst);
+    if ((PutativeEndSfxEl + 25000) >= NumSfxEls) { *pEndSfxIdx = NumSfxEls - 1; return 1; }
+    std::lock_guard<std::mutex> lk(m_Mtx);
+    std::vector<etSeqBase> El1, El2;
+    uint64_t TargPsn1 = 0, TargPsn2 = 0;
+    if (k4_get_sfx_els(m_pIdx, (uint64_t)PutativeEndSfxEl, 1, &TargPsn1) != K4_OK) return -1;
+    ConcatBases(TargPsn1, KMerLen, 0x0f, El1);
+    for (PutativeEndSfxEl += 1; PutativeEndSfxEl < NumSfxEls; PutativeEndSfxEl++) {
+      if (k4_get_sfx_els(m_pIdx, (uint64_t)PutativeEndSfxEl, 1, &TargPsn2) != K4_OK) return -1;
+      if ((int64_t)TargPsn2 + KMerLen >= NumSfxEls) { *pEndSfxIdx = PutativeEndSfxEl; return 1; }
+      ConcatBases(TargPsn2, KMerLen, 0x0e, El2);
+      for (int Ofs = 0; Ofs < KMerLen; Ofs++)
+        if ((El1[Ofs] & 0x0f) > eBaseT || (El1[Ofs] & 0x0f) != (El2[Ofs] & 0x0f)) { *pEndSfxIdx = PutativeEndSfxEl; return 1; }
+    }
+    return 0;
+  }
+
+  // CSfxArray::GenKMerCultsCnts, SfxArray.cpp:2804-3079 -- identical parameter list (`ngskit4b kmermarkers`, MarkerKMers.cpp:874).
+  // The resumable device call is repeated; every reported K-mer is rebuilt as the dense tsKMerCultsCnts the reference hands over
+  // (TotCultivars entries with EntryID = place + 1, zero elsewhere), held on the heap, and only the entries a K-mer touched are
+  // cleared for the next.  A callback result below 0 ends the call with that value.  MaxHomozygotic > 0 with a suffix is not
+  // built (K4_ERR_UNSUPPORTED, with a message); without a suffix it is ignored as the reference ignores it.
+  int64_t GenKMerCultsCnts(bool bSenseOnly, int64_t StartSfxIdx, int64_t EndSfxIdx, int PrefixKMerLen, int SuffixKMerLen, int MinCultivars,
+                           int MaxHomozygotic, void* pThis, int (*pCallback)(void* pThis, tsKMerCultsCnts* pCultsCnts)) {
+    if (!m_pIdx || !pCallback) return -1;
+    k4_info_t inf;
+    if (k4_info(m_pIdx, &inf) != K4_OK) return -1;
+    const k4_cults_params p = {PrefixKMerLen, SuffixKMerLen, MinCultivars, bSenseOnly ? 1 : 0, 0, MaxHomozygotic};
+    const uint64_t max_kmers = 1u << 16, max_dist = std::max<uint64_t>(inf.n_entries, 8 * max_kmers);  // (a call's windows follow its room)
+    const int klen = PrefixKMerLen + SuffixKMerLen;
+    std::vector<k4_cult_kmer> kmers(max_kmers);
+    std::vector<uint8_t> bases((size_t)max_kmers * (size_t)(klen > 0 && klen <= cTotCultivarKMerLen ? klen : 1));
+    std::vector<k4_cult_dist> dist(max_dist);
+    const k4_cults_out out = {kmers.data(), bases.data(), dist.data()};
+    const k4_cults_caps caps = {max_kmers, max_dist};
+    std::vector<uint8_t> mem(sizeof(tsKMerCultsCnts), 0);
+    tsKMerCultsCnts* pCnts = reinterpret_cast<tsKMerCultsCnts*>(mem.data());
+    pCnts->TotCultivars = inf.n_entries;
+    for (uint32_t i = 0; i < inf.n_entries && i < (uint32_t)cMaxCultivars; i++) pCnts->CultCnts[i].EntryID = i + 1;
+    int64_t NumKMersLocated = 0;
+    for (;;) {
+      k4_cults_totals tot;
+      {
+        std::lock_guard<std::mutex> lk(m_Mtx);
+        const int rc = k4_kmer_cults_batch(m_pIdx, &p, StartSfxIdx, EndSfxIdx, &out, &caps, &tot);
+        if (rc != K4_OK) return Fail(rc);
+      }
+      NumKMersLocated += tot.n_located;
+      for (uint64_t i = 0; i < tot.n_kmers; i++) {
+        const k4_cult_kmer& k = kmers[i];
+        pCnts->SenseCnts = k.sense_cnts; pCnts->AntisenseCnts = k.antisense_cnts; pCnts->NumCultivars = k.num_cultivars;
+        memcpy(pCnts->KMerSeq, &bases[(size_t)i * klen], (size_t)klen);
+        pCnts->KMerSeq[klen] = eBaseEOS;
+        for (uint32_t j = 0; j < k.num_cultivars; j++) {
+          const k4_cult_dist& d = dist[k.dist_ofs + j];
+          pCnts->CultCnts[d.entry_id - 1].SenseCnts = d.sense;
+          pCnts->CultCnts[d.entry_id - 1].AntisenseCnts = d.antisense;
+        }
+        const int Rslt = (*pCallback)(pThis, pCnts);
+        if (Rslt < 0) return Rslt;
+        for (uint32_t j = 0; j < k.num_cultivars; j++) {
+          const k4_cult_dist& d = dist[k.dist_ofs + j];
+          pCnts->CultCnts[d.entry_id - 1].SenseCnts = pCnts->CultCnts[d.entry_id - 1].AntisenseCnts = 0;
+        }
+      }
+      if (tot.done) break;
+      StartSfxIdx = (int64_t)tot.next_sfx_idx;
+    }
+    return NumKMersLocated;
   }
 
   // CSfxArray::LocateSfxHammings / LocateHammings, SfxArray.cpp:4107-4331 -- identical parameter lists (`ngskit4b hammings -m0`,

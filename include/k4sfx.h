@@ -599,6 +599,56 @@ int k4_locate_hammings_batch_dev(k4_index* ix, const k4_hamming_params* p, int64
                                  const uint32_t* lens, const uint64_t* out_offs, void* d_hammings, uint64_t hammings_len, void* stream);
 double k4_hamming_last_kernel_ms(const k4_index* ix);
 
+/* ---- K-mer cultivar counts -------------------------------------------------------------------------------------
+ * k4_kmer_cults_batch <- CSfxArray::GenKMerCultsCnts with AntisenseKMerCultsCnts (SfxArray.cpp:2804-3133; `ngskit4b kmermarkers`),
+ * MaxHomozygotic 0: over the suffix array elements start_sfx_idx .. end_sfx_idx (inclusive; 0 or beyond the array: to its end)
+ * every run of suffixes that share an ACGT-only prefix of prefix_len bases and are followed by suffix_len more ACGT bases is one
+ * located K-mer; per entry ("cultivar") its sense occurrences inside the range and, unless sense_only, the occurrences of the
+ * prefix's reverse complement in the whole index.  A K-mer found in min_cultivars entries or more (0: all) is reported, in
+ * suffix order:
+ *   kmers[i]  the suffix index of its first element, its totals (saturating at 2^32 - 1), how many entries hold it, and where
+ *             its counts start in dist
+ *   bases     prefix_len + suffix_len codes per K-mer
+ *   dist      {entry_id, sense, antisense} of the entries with a count, by ascending place in the entry table
+ * The call is resumable: it writes whole K-mers while caps hold them and returns in totals how many K-mers it located
+ * (reported or not), how many records it wrote, and next_sfx_idx, the first element it did not process -- always the start of a
+ * run, so a call that starts there continues with the records one big call would have written next; done != 0: the range is
+ * finished.  The range goes through in windows of at most max_window elements (0: 2^20; capped at 2^24), whatever the length
+ * of a run, and the workspace, which the index owns, is sized by the window and the number of entries alone.
+ * A window holds no more elements than the outputs have room left (floor 4096), so little room means little work per call; one
+ * call writes at most 2^21 K-mers and 2^25 counts whatever the caps say, and the host-pointer form stages that much on the device.
+ * Errors, nothing written: the reference's own (prefix_len outside 5..200, suffix_len outside 0..200, their sum above 300,
+ * min_cultivars below 0 or above the number of entries, more than 20000 entries, a negative index, start_sfx_idx beyond the
+ * array) give K4_ERR_INTERNAL, the reference's -1; max_homozygotic > 0 with a suffix (the homozygotic check depends on the
+ * order of the sequential walk) gives K4_ERR_UNSUPPORTED, and without a suffix it is ignored as the reference ignores it; a
+ * null argument, max_window < 0, max_kmers < 1 or max_dist below the number of entries give K4_ERR_PARAMS.
+ * The _dev form takes device pointers in its k4_cults_out and a stream and returns when the stream has finished.
+ * k4_cults_last_kernel_ms: device time of the last call's launches.  k4_get_sfx_els: n suffix array elements from `first`
+ * (SfxOfsToLoci), for GenKMerCultThreadRange on the host. */
+typedef struct {
+  int32_t prefix_len;       /* 5..200 */
+  int32_t suffix_len;       /* 0..200, prefix_len + suffix_len <= 300 */
+  int32_t min_cultivars;    /* 0: all entries */
+  int32_t sense_only;
+  int32_t max_window;       /* 0: the default */
+  int32_t max_homozygotic;  /* 0, or anything without a suffix */
+} k4_cults_params;
+typedef struct {
+  uint64_t head_sfx_idx;
+  uint64_t dist_ofs;
+  uint32_t sense_cnts, antisense_cnts, num_cultivars, reserved;
+} k4_cult_kmer;
+typedef struct { uint32_t entry_id, sense, antisense; } k4_cult_dist;
+typedef struct { k4_cult_kmer* kmers; uint8_t* bases; k4_cult_dist* dist; } k4_cults_out;
+typedef struct { uint64_t max_kmers, max_dist; } k4_cults_caps;
+typedef struct { int64_t n_located; uint64_t n_kmers, n_dist, next_sfx_idx; int32_t done, reserved; } k4_cults_totals;
+int k4_kmer_cults_batch(k4_index* ix, const k4_cults_params* p, int64_t start_sfx_idx, int64_t end_sfx_idx, const k4_cults_out* out,
+                        const k4_cults_caps* caps, k4_cults_totals* totals);
+int k4_kmer_cults_batch_dev(k4_index* ix, const k4_cults_params* p, int64_t start_sfx_idx, int64_t end_sfx_idx, const k4_cults_out* d_out,
+                            const k4_cults_caps* caps, k4_cults_totals* totals, void* stream);
+double k4_cults_last_kernel_ms(const k4_index* ix);
+int k4_get_sfx_els(k4_index* ix, uint64_t first, uint64_t n, uint64_t* els);
+
 /* ---- paired ends -----------------------------------------------------------------------------------------
  * k4_mate_rescue_batch <- CSfxArray::AlignPairedRead (SfxArray.h:880, SfxArray.cpp:8571-8767; MinChimericLen 0, insert
  *                         window < 1000 => the linear-scan branch :8731-8766 with AdaptiveTrim's full-length rule :5612-5638)

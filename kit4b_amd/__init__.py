@@ -5,6 +5,7 @@ the hand-written HIP kernels for gfx950.  It exists for the tests and bench.py; 
 and the C++ ``CSfxArray`` facade in include/k4_sfxarray.hpp.  There is no CPU fallback: importing works anywhere,
 every compute call needs the library and a GPU and raises ``K4Error`` otherwise.
 """
+import bisect
 import ctypes as C
 import os
 import subprocess
@@ -201,12 +202,144 @@ ABI_SYMBOLS = [
     "k4_blitz_paths_batch", "k4_blitz_paths_batch_dev", "k4_blitz_last_kernel_ms",
     "k4_locate_sfx_hammings_batch", "k4_locate_sfx_hammings_batch_dev", "k4_locate_hammings_batch", "k4_locate_hammings_batch_dev",
     "k4_hamming_last_kernel_ms",
+    "k4_kmer_cults_batch", "k4_kmer_cults_batch_dev", "k4_cults_last_kernel_ms", "k4_get_sfx_els",
 ]
 
 
 class HammingParams(C.Structure):  # k4_hamming_params
     _fields_ = [("rhamm", C.c_int32), ("kmer_len", C.c_int32), ("sample_nth", C.c_int32), ("both_strands", C.c_int32),
                 ("min_core_depth", C.c_uint32), ("max_core_depth", C.c_uint32), ("intra_inter_both", C.c_int32)]
+
+
+class CultsParams(C.Structure):  # k4_cults_params
+    _fields_ = [("prefix_len", C.c_int32), ("suffix_len", C.c_int32), ("min_cultivars", C.c_int32), ("sense_only", C.c_int32),
+                ("max_window", C.c_int32), ("max_homozygotic", C.c_int32)]
+
+
+class CultsOut(C.Structure):  # k4_cults_out
+    _fields_ = [("kmers", C.c_void_p), ("bases", C.c_void_p), ("dist", C.c_void_p)]
+
+
+class CultsCaps(C.Structure):  # k4_cults_caps
+    _fields_ = [("max_kmers", C.c_uint64), ("max_dist", C.c_uint64)]
+
+
+class CultsTotals(C.Structure):  # k4_cults_totals
+    _fields_ = [("n_located", C.c_int64), ("n_kmers", C.c_uint64), ("n_dist", C.c_uint64), ("next_sfx_idx", C.c_uint64),
+                ("done", C.c_int32), ("reserved", C.c_int32)]
+
+
+CULT_KMER_DTYPE = np.dtype([("head_sfx_idx", "<u8"), ("dist_ofs", "<u8"), ("sense_cnts", "<u4"), ("antisense_cnts", "<u4"),
+                            ("num_cultivars", "<u4"), ("reserved", "<u4")])  # k4_cult_kmer
+CULT_DIST_DTYPE = np.dtype([("entry_id", "<u4"), ("sense", "<u4"), ("antisense", "<u4")])  # k4_cult_dist
+
+
+def kmer_cult_thread_range(n_els, sa_at, bases_at, kmer_len, thread_inst, num_threads, start_sfx_idx):
+    """CSfxArray::GenKMerCultThreadRange (libkit4b/SfxArray.cpp:2733-2801) over sa_at(i) -> locus and bases_at(locus, n) -> up to n
+    codes (fewer at the end of a sequence: what follows is no base).  Returns (rc, end_sfx_idx): -1 on a bad argument, 0 when
+    nothing is left for this thread, 1 with the inclusive end -- which, as there, is the first element of the NEXT K-mer."""
+    if num_threads < 1 or num_threads > 64 or thread_inst < 1 or thread_inst > num_threads or start_sfx_idx < 0 or start_sfx_idx >= n_els:
+        return -1, 0
+    if n_els - start_sfx_idx < 50000:
+        return 1, n_els - 1
+    end = start_sfx_idx + (n_els - start_sfx_idx) // (1 + num_threads - thread_inst)
+    if end + 25000 >= n_els:
+        return 1, n_els - 1
+    psn1 = sa_at(end)
+    el1 = [int(b) & 0x0F for b in bases_at(psn1, kmer_len)]
+    end += 1
+    while end < n_els:
+        psn2 = sa_at(end)
+        if psn2 + kmer_len >= n_els:
+            return 1, end
+        el2 = [int(b) & 0x0F for b in bases_at(psn2, kmer_len)]
+        for ofs in range(kmer_len):
+            a = el1[ofs] if ofs < len(el1) else 0x0F
+            b = el2[ofs] if ofs < len(el2) else 0x0E
+            if a > 3 or a != b:
+                return 1, end
+        end += 1
+    return 0, 0
+
+
+def _revcomp_codes(seq):
+    return bytes(3 - b if b <= 3 else b for b in reversed(seq))
+
+
+def kmermarkers_fasta(index, kmer_len, prefix_len=None, min_shared=0, sense_only=False, threads=1):
+    """`ngskit4b kmermarkers -S0` as text: the sweep (index.kmer_cult_thread_range / index.kmer_cults per thread range, as
+    CMarkerKMers::LocKMers partitions it, ngskit4b/MarkerKMers.cpp:449-458), then on the host what LocKMers does with the putative
+    markers (:576-664): the sort by sequence, the duplicate / overlap / antisense flags (IsMarkerOverlapping and GetMarkerAntisense
+    as written, :690-795), the sort by cultivars and counts, and ReportMarker's records (:237-258) for the unflagged ones.  Python's
+    sorts are stable where the reference's qsort leaves ties in no fixed order."""
+    prefix_len = kmer_len if prefix_len is None else prefix_len
+    suffix_len = kmer_len - prefix_len
+    n_entries = index.info()["n_entries"]
+    min_with = n_entries if min_shared == 0 or min_shared > n_entries else min_shared
+    marks = []  # [seq bytes, sense, antisense, cultivars, flags, id]
+    start = 0
+    for t in range(threads):
+        rc, end = index.kmer_cult_thread_range(prefix_len, t + 1, threads, start)
+        if rc < 0:
+            raise K4Error(rc, "GenKMerCultThreadRange")
+        if rc < 1:
+            break
+        r = index.kmer_cults(prefix_len, suffix_len, min_with, sense_only=sense_only, start_sfx_idx=start, end_sfx_idx=end)
+        for k, b in zip(r["kmers"], r["bases"]):
+            marks.append([bytes(b[:prefix_len].tolist()), int(k["sense_cnts"]), int(k["antisense_cnts"]), int(k["num_cultivars"]), 0, len(marks) + 1])
+        start = end + 1
+    n = len(marks)
+    order = list(range(n))
+    if n > 1:
+        order.sort(key=lambda i: marks[i][0])
+        for rank, i in enumerate(order):
+            marks[i][5] = rank + 1
+        seqs = [marks[i][0] for i in order]
+
+        def find(key, width, self_id):  # the binary search of IsMarkerOverlapping / GetMarkerAntisense: the other marker's place, or None
+            lo, hi = 0, n - 1
+            while hi >= lo:
+                t = (lo + hi) // 2
+                c = seqs[t][:width]
+                if key == c:
+                    if marks[order[t]][5] != self_id:
+                        return t
+                    for u in (t - 1, t + 1):
+                        if 0 <= u < n and seqs[u][:width] == key:
+                            return u
+                    return None
+                if key < c:
+                    hi = t - 1
+                else:
+                    lo = t + 1
+            return None
+
+        for idx, i in enumerate(order):
+            m = marks[i]
+            if idx < n - 1 and seqs[idx + 1] == m[0]:
+                m[4] |= 1  # cMarkerDupFlg
+            if find(m[0][1:], prefix_len - 1, m[5]) is not None:
+                m[4] |= 2  # cMarkerOvlFlg
+            if not sense_only:
+                t = find(_revcomp_codes(m[0]), prefix_len, m[5])
+                if t is not None:
+                    anti = marks[order[t]]
+                    if anti[5] < m[5] or m[4] & 4:
+                        continue
+                    if m[4] & 0xFF:
+                        m[4] |= 4  # cMarkerAntiFlg
+                    else:
+                        anti[4] |= 4
+        order.sort(key=lambda i: (-marks[i][3], -((marks[i][1] + marks[i][2]) & 0xFFFFFFFF)))
+    out, mid = [], 0
+    trunc = min(prefix_len, 200)  # cMaxKMerLen
+    for i in order:
+        m = marks[i]
+        if m[4] & 0xFF:
+            continue
+        mid += 1
+        out.append(">KMerM%d %d|%d|%d|%d|%d\n%s\n" % (mid, trunc, kmer_len, m[3], m[1], m[2], "".join("ACGTN"[min(b, 4)] for b in m[0][:trunc])))
+    return "".join(out)
 
 
 HAMMING_DEPTHS = ((200, 5000), (1000, 10000), (2000, 20000), (5000, 50000))  # eSensLess, Default, More, Ultra (hammings.cpp:2366-2386)
@@ -474,6 +607,11 @@ def lib():
     L.k4_locate_hammings_batch_dev.argtypes = [vp, C.POINTER(HammingParams), i64, vp, vp, vp, vp, vp, u64, vp]
     L.k4_hamming_last_kernel_ms.argtypes = [vp]
     L.k4_hamming_last_kernel_ms.restype = dbl
+    L.k4_kmer_cults_batch.argtypes = [vp, C.POINTER(CultsParams), i64, i64, C.POINTER(CultsOut), C.POINTER(CultsCaps), C.POINTER(CultsTotals)]
+    L.k4_kmer_cults_batch_dev.argtypes = [vp, C.POINTER(CultsParams), i64, i64, C.POINTER(CultsOut), C.POINTER(CultsCaps), C.POINTER(CultsTotals), vp]
+    L.k4_cults_last_kernel_ms.argtypes = [vp]
+    L.k4_cults_last_kernel_ms.restype = dbl
+    L.k4_get_sfx_els.argtypes = [vp, u64, u64, vp]
     _lib = L
     return L
 
@@ -852,6 +990,66 @@ class SfxIndex:
     def hamming_kernel_ms(self):
         """device milliseconds of the last Hammings batch"""
         return lib().k4_hamming_last_kernel_ms(self.h)
+
+    def sfx_els(self, first, n):
+        """n suffix array elements from `first` (SfxOfsToLoci)"""
+        out = np.zeros(n, dtype=np.uint64)
+        self._ck(lib().k4_get_sfx_els(self.h, first, n, out.ctypes.data))
+        return out
+
+    def kmer_cults(self, prefix_len, suffix_len=0, min_cultivars=0, sense_only=False, start_sfx_idx=0, end_sfx_idx=0, max_window=0,
+                   max_homozygotic=0, max_kmers=1 << 16, max_dist=None):
+        """CSfxArray::GenKMerCultsCnts (libkit4b/SfxArray.cpp:2804) over suffix array elements start_sfx_idx .. end_sfx_idx: a dict
+        of n_located (the reference's return value) and, for the K-mers it would hand to its callback, in its order, `kmers`
+        (CULT_KMER_DTYPE), `bases` (n x K codes) and `dist` (CULT_DIST_DTYPE; K-mer i owns dist[dist_ofs : dist_ofs + num_cultivars]).
+        The resumable call is repeated with room for max_kmers K-mers and max_dist counts until the range is done."""
+        n_entries = self.info()["n_entries"]
+        klen = prefix_len + suffix_len
+        p = CultsParams(prefix_len, suffix_len, min_cultivars, 1 if sense_only else 0, max_window, max_homozygotic)
+        max_dist = max(n_entries, 8 * max_kmers) if max_dist is None else max_dist
+        kmers = np.zeros(max_kmers, dtype=CULT_KMER_DTYPE)
+        bases = np.zeros((max_kmers, max(klen, 1)), dtype=np.uint8)
+        dist = np.zeros(max_dist, dtype=CULT_DIST_DTYPE)
+        out = CultsOut(kmers.ctypes.data, bases.ctypes.data, dist.ctypes.data)
+        caps, tot = CultsCaps(max_kmers, max_dist), CultsTotals()
+        parts, located, cur, n_dist = [], 0, start_sfx_idx, 0
+        while True:
+            self._ck(lib().k4_kmer_cults_batch(self.h, C.byref(p), cur, end_sfx_idx, C.byref(out), C.byref(caps), C.byref(tot)))
+            k = kmers[:tot.n_kmers].copy()
+            k["dist_ofs"] += n_dist
+            parts.append((k, bases[:tot.n_kmers].copy(), dist[:tot.n_dist].copy()))
+            located += tot.n_located
+            n_dist += tot.n_dist
+            if tot.done:
+                break
+            cur = tot.next_sfx_idx
+        return dict(n_located=located, kmers=np.concatenate([q[0] for q in parts]), bases=np.concatenate([q[1] for q in parts]),
+                    dist=np.concatenate([q[2] for q in parts]))
+
+    def kmer_cult_thread_range(self, kmer_len, thread_inst, num_threads, start_sfx_idx):
+        """CSfxArray::GenKMerCultThreadRange (libkit4b/SfxArray.cpp:2733): (rc, end_sfx_idx), on the host from a few elements and bases"""
+        inf = self.info()
+        if getattr(self, "_ent_starts", None) is None:  # (the table does not change while the index is open)
+            ents = [self.entry(i + 1) for i in range(inf["n_entries"])]
+            self._ent_starts, self._ents = [e["start_ofs"] for e in ents], ents
+        block = {}
+
+        def sa_at(i):  # elements come down 256 at a time: the walk looks at neighbours
+            b0 = i - i % 256
+            if b0 not in block:
+                block.clear()
+                block[b0] = self.sfx_els(b0, min(256, inf["concat_len"] - b0))
+            return int(block[b0][i - b0])
+
+        def bases_at(psn, n):
+            e = self._ents[max(bisect.bisect_right(self._ent_starts, psn) - 1, 0)]
+            return self.get_seq(e["entry_id"], psn - e["start_ofs"], n) if e["start_ofs"] <= psn < e["start_ofs"] + e["seq_len"] else []
+
+        return kmer_cult_thread_range(inf["concat_len"], sa_at, bases_at, kmer_len, thread_inst, num_threads, start_sfx_idx)
+
+    def cults_kernel_ms(self):
+        """device milliseconds of the last kmer_cults call's launches"""
+        return lib().k4_cults_last_kernel_ms(self.h)
 
     def kalign_batch(self, reads, max_subs=5, min_edit_dist=1, max_ns=1, pmode=0, strand=STRAND_BOTH, max_ml=1,
                      pe_mode=0, min_core_len=0, max_num_slides=0):

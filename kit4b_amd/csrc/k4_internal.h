@@ -110,6 +110,16 @@ struct K4BlitzState {
 };
 // restricted Hammings (k4_hamming.hip), grow-only: the span table of a batch, then the caller's byte array of the host-pointer forms
 struct K4HammState { K4DevBuf spans, out; K4Timer timer; };
+// K-mer cultivar counts (k4_cults.hip), grow-only and sized by the window and the entries, never by the range: a window's flags,
+// entries and segment starts with the select's count, the count pass's answers and their scans, the histogram slices for indexes
+// of more entries than the LDS histogram holds, the scans' temporary; then the outputs of the host-pointer entry point
+struct K4CultState {
+  K4DevBuf flags, ent, starts, count, loc, rep, nnz, loc_pre, rep_pre, dist_pre, hist;
+  K4DevBuf out_kmers, out_bases, out_dist;
+  K4Scratch<K4DevBuf> scan;
+  K4Timer timer;
+  double ms = 0;  // the sections of the last call, summed
+};
 
 struct k4_index {
   int device = 0;
@@ -154,6 +164,7 @@ struct k4_index {
   K4QueryState qry;
   K4BlitzState blz;
   K4HammState hmm;
+  K4CultState cul;
   // k4_open_async: the arrays are uploaded and the device structures built by this thread; k4_open_wait joins it
   std::thread loader;
   int load_rc = 0;

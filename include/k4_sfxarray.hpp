@@ -93,6 +93,7 @@ const int cMaxCultivars = 20000;         // libkit4b/SfxArray.h:186-189
 const int cMinCultivarPreSufLen = 5;
 const int cMaxCultivarPreSufLen = 200;
 const int cTotCultivarKMerLen = 300;
+#pragma pack(1)                     // (libkit4b/SfxArray.h:227-320 is one pack(1) region)
 typedef struct TAG_sKMerCultCnts {  // libkit4b/SfxArray.h:262-266
   uint32_t EntryID;
   uint32_t SenseCnts;
@@ -106,8 +107,9 @@ typedef struct TAG_sKMerCultsCnts {  // libkit4b/SfxArray.h:268-275
   etSeqBase KMerSeq[cTotCultivarKMerLen + 1];
   tsKMerCultDist CultCnts[cMaxCultivars];
 } tsKMerCultsCnts;
+#pragma pack()
 #endif  // K4_HAVE_KIT4B_TYPES
-static_assert(sizeof(tsKMerCultDist) == 12 && sizeof(tsKMerCultsCnts) == 240328 && offsetof(tsKMerCultsCnts, CultCnts) == 328 &&
+static_assert(sizeof(tsKMerCultDist) == 12 && sizeof(tsKMerCultsCnts) == 240325 && offsetof(tsKMerCultsCnts, CultCnts) == 325 &&
                   offsetof(tsKMerCultsCnts, KMerSeq) == 24,
               "layouts must match libkit4b");
 static_assert(sizeof(tsSegLoci) == 23 && sizeof(tsHitLoci) == 50 && sizeof(tsSfxHeaderV3) == 1224, "layouts must match libkit4b");

@@ -686,8 +686,9 @@ static uint32_t next_pow2(uint64_t v) {
 
 // slots of one survivor buffer for batches of up to cap reads (see k4_reserve)
 static size_t k4_survivor_slots(size_t cap) {
-  static_assert(K4_CHUNK * 7 >= 8 * 63, "cap / 7 must cover the abandoned chunk tails");
-  return cap + cap / 7 + (size_t)2048 * 4 * K4_CHUNK + K4_CHUNK;
+  static_assert((K4_CHUNK - 63) * 8 >= K4_CHUNK * 7, "cap / 7 must cover the abandoned chunk tails");
+  static_assert(2048 * (256 / 64) == 4096 * (128 / 64), "waves of a full grid, in every length class");
+  return cap + cap / 7 + (size_t)2 * 2048 * 4 * K4_CHUNK + K4_CHUNK;
 }
 
 static int nch_for(int max_len) {
@@ -716,8 +717,12 @@ extern "C" int k4_reserve(k4_index* ix, int64_t max_reads, int32_t max_read_len,
     // Survivors of step t (ids + packed rows) ping-pong between two buffers.  Slots are handed out K4_CHUNK at a time
     // per wave; a wave abandons the tail of its chunk (at most 63 slots) when the next ballot does not fit, and leaves
     // one partly used chunk behind when it ends.  Step t+1 walks over step t's slots, holes included, but places only
-    // real survivors again.  So every chunk a wave has moved on from holds at least K4_CHUNK - 63 real entries: a step
-    // uses at most n * K4_CHUNK / (K4_CHUNK - 63) slots plus one chunk per wave of the (at most 2048-block) grid.
+    // real survivors again.  So every chunk a wave has moved on from holds at least K4_CHUNK - 63 real entries: a launch
+    // that places s survivors uses at most s * K4_CHUNK / (K4_CHUNK - 63) slots plus one chunk per wave of its grid, which
+    // has at most 2048 * 4 waves.  Step 0 of an index with repeat families is two launches that append to one list (and
+    // place n survivors between them at the most): two partly used chunks per wave, which the bound for one launch does not
+    // cover.  tests/bigbatch.py restates this arithmetic, tests/test_bigbatch_cpu.py holds it against this bound.  The
+    // deferred list of that step (ids[1]) is one launch's.
     const size_t slots = k4_survivor_slots((size_t)cap);
     for (int b = 0; b < 2; b++) {
       K4_HIP(ix, w.ids[b].reserve(slots * 4));

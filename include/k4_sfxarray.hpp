@@ -616,6 +616,66 @@ class CSfxArray {
     return rc == K4_OK ? 0 : Fail(rc);
   }
 
+  // CSfxArray::IterateExacts, SfxArray.cpp:3381-3458 -- the five-argument form (`ngskit4b kmarkers`, LocKMers.cpp:1105).  PrevHitIdx 0
+  // is one device batch of one probe (k4_exact_ranges_batch); otherwise the probe is compared on the host with the suffix at
+  // PrevHitIdx, as CmpProbeTarg does (:2508-2525).  Returns the hit index (1..n), 0 without a (further) hit.
+  int64_t IterateExacts(etSeqBase* pProbeSeq, uint32_t ProbeLen, int64_t PrevHitIdx, uint32_t* pTargEntryID, uint32_t* pHitLoci) {
+    *pHitLoci = 0;
+    *pTargEntryID = 0;
+    k4_info_t inf;
+    if (!m_pIdx || k4_info(m_pIdx, &inf) != K4_OK || PrevHitIdx < 0 || (uint64_t)PrevHitIdx >= inf.concat_len) return 0;
+    uint64_t Idx = (uint64_t)PrevHitIdx, Psn = 0;
+    std::lock_guard<std::mutex> dev(m_Mtx);
+    if (!PrevHitIdx) {
+      const uint64_t off = 0;
+      uint32_t cnt = 0;
+      if (k4_exact_ranges_batch(m_pIdx, 1, pProbeSeq, &off, &ProbeLen, &Idx, &cnt) != K4_OK) return Fail(0);
+      if (!cnt) return 0;
+    }
+    if (k4_get_sfx_els(m_pIdx, Idx, 1, &Psn) != K4_OK) return Fail(0);
+    if (PrevHitIdx) {
+      std::vector<etSeqBase> Targ;
+      ConcatBases(Psn, (int)ProbeLen, eBaseEOS, Targ);
+      for (uint32_t k = 0; k < ProbeLen; k++)
+        if ((Targ[k] & 0x0f) == eBaseEOS || (pProbeSeq[k] & 0x0f) != (Targ[k] & 0x0f)) return 0;
+    }
+    for (uint32_t e = 1; e <= inf.n_entries; e++) {
+      k4_entry ent;
+      if (k4_get_entry(m_pIdx, e, &ent) == K4_OK && ent.start_ofs <= Psn && Psn < ent.start_ofs + ent.seq_len) {
+        *pTargEntryID = ent.entry_id;
+        *pHitLoci = (uint32_t)(Psn - ent.start_ofs);
+        return (int64_t)Idx + 1;
+      }
+    }
+    return 0;
+  }
+
+  // CSfxArray::MatchesOtherChroms, SfxArray.cpp:5094-5235 -- both overloads, each one device batch of one probe: 1 when a core of
+  // the probe hits an entry that is not among the ids where the probe can be laid over it, else 0; below 0 on errors.
+  int MatchesOtherChroms(int NumProbeIDs, int* pProbeChromIDs, int MaxTotMM, int ProbeLen, etSeqBase* pProbe) {
+    if (!m_pIdx || NumProbeIDs < 0 || ProbeLen < 0 || !pProbe) return K4_ERR_PARAMS;
+    std::vector<uint32_t> Ids(pProbeChromIDs, pProbeChromIDs + NumProbeIDs);
+    const uint64_t off = 0;
+    const uint32_t len = (uint32_t)ProbeLen;
+    int32_t m = 0;
+    std::lock_guard<std::mutex> dev(m_Mtx);
+    const int rc = k4_matches_other_chroms_batch(m_pIdx, NumProbeIDs, Ids.data(), MaxTotMM, 1, pProbe, &off, &len, &m);
+    return rc == K4_OK ? m : Fail(rc);
+  }
+  int MatchesOtherChroms(int ProbeChromID, int MaxTotMM, int ProbeLen, etSeqBase* pProbe) {
+    return MatchesOtherChroms(1, &ProbeChromID, MaxTotMM, ProbeLen, pProbe);
+  }
+
+  // The throughput form of `ngskit4b kmarkers` (CLocKMers::LocateSpeciesUniqueKMers as one thread runs it): one status byte per start
+  // locus of every target, in the order of pTargetIDs, and the front end's tallies; k4sfx.h has the statuses.
+  int SpeciesKMersBatch(const k4_kmarkers_params& Pars, int NumTargets, const uint32_t* pTargetIDs, uint8_t* pStatus, uint64_t StatusLen,
+                        k4_kmarkers_totals* pTotals) {
+    if (!m_pIdx) return K4_ERR_PARAMS;
+    std::lock_guard<std::mutex> dev(m_Mtx);
+    const int rc = k4_species_kmers_batch(m_pIdx, &Pars, NumTargets, pTargetIDs, pStatus, StatusLen, pTotals);
+    return rc == K4_OK ? 0 : Fail(rc);
+  }
+
   // CSfxArray::AlignPairedRead, SfxArray.h:880-896 -- identical parameter list (CKAligner's mate rescue,
   // KAligner.cpp:3372-3386,3476-3490).  -1 errors, 0 no match, 1 placed with mismatches only.
   int AlignPairedRead(bool b3primeExtend, bool bAntisense, uint32_t ChromID, uint32_t StartLoci, uint32_t EndLoci, int MinInsertSize,

@@ -649,6 +649,58 @@ int k4_kmer_cults_batch_dev(k4_index* ix, const k4_cults_params* p, int64_t star
 double k4_cults_last_kernel_ms(const k4_index* ix);
 int k4_get_sfx_els(k4_index* ix, uint64_t first, uint64_t n, uint64_t* els);
 
+/* ---- kmarkers: exact ranges and the species scan -----------------------------------------------------------------
+ * k4_exact_ranges_batch <- CSfxArray::IterateExacts walked to its end (SfxArray.cpp:3381-3458): for probe i (lens[i] codes at
+ * seqs + offs[i], compared on the low nibble as CmpProbeTarg does, never across an end-of-sequence symbol) firsts[i] = the suffix
+ * index of its first exact match and counts[i] = how many suffixes match (saturating at 2^32 - 1); 0 and 0 without a match or for
+ * an empty probe.  firsts[i] + 1 is what IterateExacts(probe, len, 0, ..) returns, and the hits it then iterates are the
+ * elements firsts[i] .. firsts[i] + counts[i] - 1.  The _dev form takes every array as a device pointer.
+ * k4_matches_other_chroms_batch <- CSfxArray::MatchesOtherChroms (:5094-5235), probe i against the entries whose ids are not among
+ * ids[0 .. n_ids): matches[i] = 1 or 0, as the reference returns it -- a hit of a core (CoreLen = max(8, len / (1 + max_tot_mm)),
+ * offsets 0, CoreLen, .. below len - CoreLen) on another entry over which the probe can be laid returns 1 whatever the flanks
+ * hold.  n_ids 0..50, probes of at most 500 bases, else K4_ERR_PARAMS.  Host pointers.
+ * k4_species_kmers_batch <- CLocKMers::LocateSpeciesUniqueKMers (ngskit4b/LocKMers.cpp:1085-1232; `ngskit4b kmarkers`) as ONE thread
+ * runs it: status[pre(t) + l] for start locus l of target t, the targets in the order of target_ids (the front end's: sorted by
+ * name without case), pre(t) = the summed lengths of the targets in front.  A status is the first of
+ *   1  fewer than kmer_len ACGT bases from here to the next other symbol or the entry's end
+ *   2  the K-mer's first exact hit is in an entry that is no target
+ *   3  duplicate: the K-mer or, where the reverse complement's first hit is in a target, its reverse complement stands at an
+ *      earlier (target, locus); a K-mer that is its own reverse complement is one wherever it stands
+ *   4  a hit of the K-mer, or a hit of its reverse complement other than that strand's first, is in an entry that is no target
+ *   5  min_hamming > 1 and MatchesOtherChroms(targets, min_hamming - 1, K-mer) or (.., reverse complement) is 1
+ *   6  mode 2: fewer than min_with_prefix (0, or more than there are: all) entries that are no targets hold the first prefix_len
+ *      bases of the K-mer or of its reverse complement
+ *   7  accepted
+ * totals: processed (status > 1), cultivar_specific (> 4), hamming_retained (> 5), accepted = the markers the front end writes:
+ * the accepted K-mers in modes 0 and 2, in mode 1 the runs of adjacent accepted K-mers that a later accepted K-mer of the same ACGT
+ * run follows (the front end never flushes the last).  Nothing is written into the index.  status_len >= the summed lengths of
+ * the targets; the bytes behind them are not touched.  K4_ERR_PARAMS: kmer_len outside 20..100, min_hamming outside 1..5, mode
+ * outside 0..2, in mode 2 prefix_len outside 10..kmer_len - 10, an unknown or repeated target id, more than 50 targets, targets
+ * that are all the entries, a null argument, status_len too small.  K4_ERR_UNSUPPORTED: an ACGT run of 0x7fffe bases or more in
+ * a target (the front end stops handing out blocks there), mode 2 over more than 2048 entries.  The _dev form takes status as a
+ * device pointer and a stream and returns when the stream has finished.  k4_kmarkers_last_kernel_ms: device time of the last of
+ * these calls' launches. */
+typedef struct {
+  int32_t kmer_len;         /* 20..100 */
+  int32_t min_hamming;      /* 1..5 */
+  int32_t mode;             /* 0 | 1 | 2 */
+  int32_t prefix_len;       /* mode 2: 10..kmer_len - 10 */
+  int32_t min_with_prefix;  /* mode 2; 0: every entry that is no target */
+  int32_t reserved;
+} k4_kmarkers_params;
+typedef struct { uint64_t processed, cultivar_specific, hamming_retained, accepted; } k4_kmarkers_totals;
+int k4_exact_ranges_batch(k4_index* ix, int64_t n, const uint8_t* seqs, const uint64_t* offs, const uint32_t* lens, uint64_t* firsts,
+                          uint32_t* counts);
+int k4_exact_ranges_batch_dev(k4_index* ix, int64_t n, const void* d_seqs, const void* d_offs, const void* d_lens, void* d_firsts,
+                              void* d_counts, void* stream);
+int k4_matches_other_chroms_batch(k4_index* ix, int32_t n_ids, const uint32_t* ids, int32_t max_tot_mm, int64_t n, const uint8_t* seqs,
+                                  const uint64_t* offs, const uint32_t* lens, int32_t* matches);
+int k4_species_kmers_batch(k4_index* ix, const k4_kmarkers_params* p, int32_t n_targets, const uint32_t* target_ids, uint8_t* status,
+                           uint64_t status_len, k4_kmarkers_totals* totals);
+int k4_species_kmers_batch_dev(k4_index* ix, const k4_kmarkers_params* p, int32_t n_targets, const uint32_t* target_ids, void* d_status,
+                               uint64_t status_len, k4_kmarkers_totals* totals, void* stream);
+double k4_kmarkers_last_kernel_ms(const k4_index* ix);
+
 /* ---- paired ends -----------------------------------------------------------------------------------------
  * k4_mate_rescue_batch <- CSfxArray::AlignPairedRead (SfxArray.h:880, SfxArray.cpp:8571-8767; MinChimericLen 0, insert
  *                         window < 1000 => the linear-scan branch :8731-8766 with AdaptiveTrim's full-length rule :5612-5638)

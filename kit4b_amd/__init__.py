@@ -203,12 +203,80 @@ ABI_SYMBOLS = [
     "k4_locate_sfx_hammings_batch", "k4_locate_sfx_hammings_batch_dev", "k4_locate_hammings_batch", "k4_locate_hammings_batch_dev",
     "k4_hamming_last_kernel_ms",
     "k4_kmer_cults_batch", "k4_kmer_cults_batch_dev", "k4_cults_last_kernel_ms", "k4_get_sfx_els",
+    "k4_exact_ranges_batch", "k4_exact_ranges_batch_dev", "k4_matches_other_chroms_batch", "k4_species_kmers_batch",
+    "k4_species_kmers_batch_dev", "k4_kmarkers_last_kernel_ms",
 ]
 
 
 class HammingParams(C.Structure):  # k4_hamming_params
     _fields_ = [("rhamm", C.c_int32), ("kmer_len", C.c_int32), ("sample_nth", C.c_int32), ("both_strands", C.c_int32),
                 ("min_core_depth", C.c_uint32), ("max_core_depth", C.c_uint32), ("intra_inter_both", C.c_int32)]
+
+
+class KMarkersParams(C.Structure):  # k4_kmarkers_params
+    _fields_ = [("kmer_len", C.c_int32), ("min_hamming", C.c_int32), ("mode", C.c_int32), ("prefix_len", C.c_int32),
+                ("min_with_prefix", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KMarkersTotals(C.Structure):  # k4_kmarkers_totals
+    _fields_ = [("processed", C.c_uint64), ("cultivar_specific", C.c_uint64), ("hamming_retained", C.c_uint64), ("accepted", C.c_uint64)]
+
+
+KMER_NOT_KMER, KMER_FIRST_FOREIGN, KMER_DUPLICATE, KMER_FOREIGN_HIT, KMER_HAMMING, KMER_PREFIX, KMER_ACCEPTED = range(1, 8)
+
+
+def kmarkers_fasta(index, cultivar, chrom_names, kmer_len=50, mode=0, prefix_len=None, min_shared=0, min_hamming=2):
+    """The marker file `ngskit4b kmarkers -T1 -c cultivar -C chrom_names -k -m -p -s -K` writes, as bytes: the species scan
+    (index.species_kmers over the targets in the front end's order, its qsort by stricmp of the names, LocKMers.cpp:587) and on the
+    host ReportMarker's records (:192-223), one per accepted K-mer in modes 0 and 2 and per flushed run in mode 1 (:1209-1231: the
+    mode the help text calls "no extension" is the one that extends, and a run is written when a later accepted K-mer of the same
+    ACGT run starts the next one -- the last run of a sequence never is).
+    The front end hands MinHamming and MinWithPrefix to LocKMers in each other's place (genkmarkers.cpp:516 against LocKMers.cpp:525):
+    -s (min_shared; modes 0 and 1 leave it at 0) is the Hamming separation that is tested and printed, 0 and 1 testing nothing, and -K
+    (min_hamming) is the number of other entries that must share the prefix.  This function does the same, as the recorded files
+    require.  index: anything with info(), entry(), get_seq() and species_kmers(), SfxIndex or a restatement."""
+    if mode not in (0, 1, 2):
+        raise K4Error(-100, "Processing mode '-m%d' specified outside of range 0..2" % mode)
+    if mode == 2:
+        prefix_len = kmer_len // 2 if prefix_len is None else prefix_len
+    else:
+        prefix_len, min_shared = 0, 0
+    if not 1 <= min_hamming <= 5 or min_shared < 0:
+        raise K4Error(-100, "Minimum Hamming separation '-K%d' must be in range 1..5" % min_hamming)
+    n_entries = index.info()["n_entries"]
+    by_name = {}
+    for e in range(1, n_entries + 1):
+        by_name.setdefault(index.entry(e)["name"].lower(), index.entry(e))
+    names = sorted(chrom_names, key=lambda s: s.lower())
+    if any(a.lower() == b.lower() for a, b in zip(names, names[1:])) or any(n.lower() not in by_name for n in names):
+        raise K4Error(-100, "a target name twice, or one the index does not hold")
+    targets = [by_name[n.lower()] for n in names]
+    status, _ = index.species_kmers([t["entry_id"] for t in targets], kmer_len, max(min_shared, 1), mode, prefix_len, min_hamming)
+    out, base, n_markers = [], 0, 0
+
+    def report(t, loc, length):
+        nonlocal n_markers
+        n_markers += 1
+        seq = index.get_seq(t["entry_id"], loc, min(length, 4000))
+        out.append(">%sM%d %d|%d|%d\n%s\n" % (cultivar, n_markers, len(seq), kmer_len, min_shared, "".join("ACGTN"[min(int(b) & 0x0F, 4)] for b in seq)))
+
+    for t in targets:
+        st = status[base:base + t["seq_len"]]
+        base += t["seq_len"]
+        acc = np.flatnonzero(st == KMER_ACCEPTED)
+        if mode != 1:
+            for loc in acc:
+                report(t, int(loc), kmer_len)
+            continue
+        run_start = prev = None
+        for loc in (int(x) for x in acc):
+            new_seq = prev is None or (st[prev:loc] == KMER_NOT_KMER).any()  # (K - 1 such bytes end every ACGT run)
+            if not new_seq and loc > prev + 1:
+                report(t, run_start, kmer_len + prev - run_start)
+            if new_seq or loc > prev + 1:
+                run_start = loc
+            prev = loc
+    return "".join(out).encode()
 
 
 class CultsParams(C.Structure):  # k4_cults_params
@@ -611,6 +679,13 @@ def lib():
     L.k4_kmer_cults_batch_dev.argtypes = [vp, C.POINTER(CultsParams), i64, i64, C.POINTER(CultsOut), C.POINTER(CultsCaps), C.POINTER(CultsTotals), vp]
     L.k4_cults_last_kernel_ms.argtypes = [vp]
     L.k4_cults_last_kernel_ms.restype = dbl
+    L.k4_exact_ranges_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    L.k4_exact_ranges_batch_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.k4_matches_other_chroms_batch.argtypes = [vp, C.c_int32, vp, C.c_int32, i64, vp, vp, vp, vp]
+    L.k4_species_kmers_batch.argtypes = [vp, C.POINTER(KMarkersParams), C.c_int32, vp, vp, C.c_uint64, C.POINTER(KMarkersTotals)]
+    L.k4_species_kmers_batch_dev.argtypes = [vp, C.POINTER(KMarkersParams), C.c_int32, vp, vp, C.c_uint64, C.POINTER(KMarkersTotals), vp]
+    L.k4_kmarkers_last_kernel_ms.argtypes = [vp]
+    L.k4_kmarkers_last_kernel_ms.restype = dbl
     L.k4_get_sfx_els.argtypes = [vp, u64, u64, vp]
     _lib = L
     return L
@@ -1050,6 +1125,47 @@ class SfxIndex:
     def cults_kernel_ms(self):
         """device milliseconds of the last kmer_cults call's launches"""
         return lib().k4_cults_last_kernel_ms(self.h)
+
+    def exact_ranges(self, probes):
+        """CSfxArray::IterateExacts walked to its end for a batch of probes (codes): (firsts uint64, counts uint32) -- the suffix
+        index of a probe's first exact match and how many suffixes match; 0, 0 without one.  firsts + 1 is IterateExacts' return."""
+        cat, offs, lens = _flatten(probes)
+        n = len(lens)
+        firsts, counts = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+        cat = np.concatenate([cat, np.zeros(16, np.uint8)])
+        self._ck(lib().k4_exact_ranges_batch(self.h, n, cat.ctypes.data, offs.ctypes.data, lens.ctypes.data, firsts.ctypes.data, counts.ctypes.data))
+        return firsts, counts
+
+    def matches_other_chroms(self, probe_ids, max_tot_mm, probes):
+        """CSfxArray::MatchesOtherChroms (libkit4b/SfxArray.cpp:5094-5235) for a batch of probes against the entries whose ids are
+        not in probe_ids (an id or a list): an int32 array of the reference's 1 / 0"""
+        ids = np.ascontiguousarray(np.atleast_1d(probe_ids), dtype=np.uint32)
+        cat, offs, lens = _flatten(probes)
+        n = len(lens)
+        out = np.zeros(n, dtype=np.int32)
+        cat = np.concatenate([cat, np.zeros(16, np.uint8)])
+        self._ck(lib().k4_matches_other_chroms_batch(self.h, len(ids), ids.ctypes.data, max_tot_mm, n, cat.ctypes.data, offs.ctypes.data,
+                                                     lens.ctypes.data, out.ctypes.data))
+        return out
+
+    def species_kmers(self, target_ids, kmer_len, min_hamming=1, mode=0, prefix_len=0, min_with_prefix=0):
+        """CLocKMers::LocateSpeciesUniqueKMers (ngskit4b/LocKMers.cpp:1085-1232) as one thread runs it over the targets in the order
+        given: (status bytes, one per start locus of every target, KMER_NOT_KMER .. KMER_ACCEPTED; the front end's tallies as a dict)"""
+        ids = np.ascontiguousarray(target_ids, dtype=np.uint32)
+        total = 0
+        for t in ids.tolist():
+            e = Entry()
+            if lib().k4_get_entry(self.h, t, C.byref(e)) == 0 and e.entry_id == t:
+                total += e.seq_len
+        status = np.zeros(max(total, 1), dtype=np.uint8)
+        p = KMarkersParams(kmer_len, min_hamming, mode, prefix_len, min_with_prefix, 0)
+        tot = KMarkersTotals()
+        self._ck(lib().k4_species_kmers_batch(self.h, C.byref(p), len(ids), ids.ctypes.data, status.ctypes.data, len(status), C.byref(tot)))
+        return status[:total], {f[0]: int(getattr(tot, f[0])) for f in KMarkersTotals._fields_}
+
+    def kmarkers_kernel_ms(self):
+        """device milliseconds of the last exact_ranges / matches_other_chroms / species_kmers call's launches"""
+        return lib().k4_kmarkers_last_kernel_ms(self.h)
 
     def kalign_batch(self, reads, max_subs=5, min_edit_dist=1, max_ns=1, pmode=0, strand=STRAND_BOTH, max_ml=1,
                      pe_mode=0, min_core_len=0, max_num_slides=0):

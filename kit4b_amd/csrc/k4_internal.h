@@ -121,6 +121,10 @@ struct K4CultState {
   double ms = 0;  // the sections of the last call, summed
 };
 
+// kmarkers (k4_kmarkers.hip), grow-only: the rank of every entry in the target list, the outputs of the host-pointer entry points
+// (status bytes; first indices and counts; MatchesOtherChroms answers), the four tallies and the long-run flag
+struct K4MarkState { K4DevBuf rank, out, ctl; K4Timer timer; };
+
 struct k4_index {
   int device = 0;
   K4DevIndex d{};
@@ -165,6 +169,7 @@ struct k4_index {
   K4BlitzState blz;
   K4HammState hmm;
   K4CultState cul;
+  K4MarkState kmk;
   // k4_open_async: the arrays are uploaded and the device structures built by this thread; k4_open_wait joins it
   std::thread loader;
   int load_rc = 0;

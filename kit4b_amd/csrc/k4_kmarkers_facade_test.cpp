@@ -1,0 +1,94 @@
+// kit4b_amd/csrc/k4_kmarkers_facade_test.cpp -- include/k4_sfxarray.hpp's IterateExacts, MatchesOtherChroms and SpeciesKMersBatch the way
+// CLocKMers calls CSfxArray's (ngskit4b/LocKMers.cpp:1105-1188): a probe is walked until IterateExacts returns 0.
+// usage: k4_kmarkers_facade_test index.sfx calls.txt scan.txt
+// calls.txt, per probe: "len digits n_ids id.. mm m1 mn n_hits" and n_hits times "idx entry loci" (the reference's returns)
+// scan.txt: "klen min_hamming mode prefix_len min_with_prefix n_targets id.. processed specific retained accepted total" and one word
+// of `total` status digits
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "k4_sfxarray.hpp"
+
+int main(int argc, char** argv) {
+  if (argc < 4) return 1;
+  CSfxArray* pSfx = new CSfxArray;
+  if (pSfx->Open(argv[1]) < 0) {
+    while (pSfx->NumErrMsgs()) fprintf(stderr, "%s\n", pSfx->GetErrMsg());
+    return 2;
+  }
+  if (pSfx->SetTargBlock(1) < 0) return 3;
+  FILE* f = fopen(argv[2], "r");
+  if (!f) return 4;
+  int nProbes = 0, badWalk = 0, badM1 = 0, badMn = 0;
+  long nHits = 0;
+  for (;;) {
+    unsigned len, nIds;
+    if (fscanf(f, "%u", &len) != 1) break;
+    std::vector<char> s(len + 2);
+    if (fscanf(f, "%s %u", s.data(), &nIds) != 2) return 5;
+    std::vector<etSeqBase> Probe(len + 8, 0);
+    for (unsigned j = 0; j < len; j++) Probe[j] = (etSeqBase)(s[j] - '0');
+    std::vector<int> Ids(nIds);
+    for (unsigned j = 0; j < nIds; j++)
+      if (fscanf(f, "%d", &Ids[j]) != 1) return 5;
+    int mm, m1, mn;
+    unsigned nWant;
+    if (fscanf(f, "%d %d %d %u", &mm, &m1, &mn, &nWant) != 4) return 5;
+    int64_t PrevHitIdx = 0, NxtHitIdx;
+    uint32_t TargHitID, TargHitLoci;
+    unsigned got = 0;
+    bool ok = true;
+    while ((NxtHitIdx = pSfx->IterateExacts(Probe.data(), len, PrevHitIdx, &TargHitID, &TargHitLoci)) > 0) {
+      long long idx;
+      unsigned e, l;
+      if (got < nWant) {
+        if (fscanf(f, "%lld %u %u", &idx, &e, &l) != 3) return 5;
+        ok = ok && idx == NxtHitIdx && e == TargHitID && l == TargHitLoci;
+      }
+      got++;
+      PrevHitIdx = NxtHitIdx;
+    }
+    for (unsigned k = got; k < nWant; k++) {
+      long long idx;
+      unsigned e, l;
+      if (fscanf(f, "%lld %u %u", &idx, &e, &l) != 3) return 5;
+    }
+    if (!ok || got != nWant) badWalk++;
+    nHits += got;
+    if (pSfx->MatchesOtherChroms(Ids[0], mm, (int)len, Probe.data()) != m1) badM1++;
+    if (pSfx->MatchesOtherChroms((int)nIds, Ids.data(), mm, (int)len, Probe.data()) != mn) badMn++;
+    nProbes++;
+  }
+  fclose(f);
+  printf("probes %d hits %ld bad walks %d bad single %d bad list %d\n", nProbes, nHits, badWalk, badM1, badMn);
+  if (!(f = fopen(argv[3], "r"))) return 4;
+  k4_kmarkers_params P;
+  memset(&P, 0, sizeof(P));
+  int nT;
+  if (fscanf(f, "%d %d %d %d %d %d", &P.kmer_len, &P.min_hamming, &P.mode, &P.prefix_len, &P.min_with_prefix, &nT) != 6) return 5;
+  std::vector<uint32_t> T((size_t)nT);
+  for (int j = 0; j < nT; j++)
+    if (fscanf(f, "%u", &T[(size_t)j]) != 1) return 5;
+  unsigned long long w[4], total;
+  if (fscanf(f, "%llu %llu %llu %llu %llu", &w[0], &w[1], &w[2], &w[3], &total) != 5) return 5;
+  std::vector<char> want(total + 2);
+  if (fscanf(f, "%s", want.data()) != 1) return 5;
+  fclose(f);
+  std::vector<uint8_t> Status(total + 4, 0xee);
+  k4_kmarkers_totals Tot;
+  const int Rslt = pSfx->SpeciesKMersBatch(P, nT, T.data(), Status.data(), total + 4, &Tot);
+  unsigned long long bad = 0;
+  for (unsigned long long k = 0; k < total; k++) bad += Status[k] != (uint8_t)(want[k] - '0');
+  const bool fill = Status[total] == 0xee && Status[total + 3] == 0xee;
+  printf("scan %d bad %llu tallies %d fill %d\n", Rslt, bad,
+         Tot.processed == w[0] && Tot.cultivar_specific == w[1] && Tot.hamming_retained == w[2] && Tot.accepted == w[3] ? 1 : 0, fill ? 1 : 0);
+  P.kmer_len = 19;
+  printf("errors %d", pSfx->SpeciesKMersBatch(P, nT, T.data(), Status.data(), total + 4, &Tot));
+  P.kmer_len = 20;
+  T[0] = 999;
+  const int Unknown = pSfx->SpeciesKMersBatch(P, nT, T.data(), Status.data(), total + 4, &Tot);
+  printf(" %d msgs %d\n", Unknown, pSfx->NumErrMsgs());
+  delete pSfx;
+  return 0;
+}

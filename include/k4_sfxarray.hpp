@@ -676,6 +676,40 @@ class CSfxArray {
     return rc == K4_OK ? 0 : Fail(rc);
   }
 
+  // CSfxArray::LocateAllNearMatches, SfxArray.h:823-837 -- identical parameter list (`genzygosity`, genzygosity.cpp:1193): one device
+  // batch of one probe.  -1 when the probe is not unique to ProbeEntry or has more than MaxMatches matches elsewhere, else the
+  // matches in other entries; a K4_ERR_* below -1 on errors.  pEntryMatches is zeroed and its first min(NumEntries, entries of the
+  // index) places filled.  The ident-node scratch is not used; its count is honoured as the limit.  The probe is left as given.
+  int LocateAllNearMatches(int MaxTotMM, int CoreLen, int CoreDelta, int MaxNumCoreSlides, int MaxMatches, int NumEntries, uint32_t* pEntryMatches,
+                           uint32_t ProbeEntry, uint32_t ProbeOfs, int ProbeLen, etSeqBase* pProbeSeq, int CurMaxIter, int NumAllocdIdentNodes,
+                           tsIdentNode* pAllocsIdentNodes) {
+    (void)pAllocsIdentNodes;
+    k4_info_t inf;
+    if (!m_pIdx || k4_info(m_pIdx, &inf) != K4_OK || ProbeLen < 0 || !pProbeSeq) return K4_ERR_PARAMS;
+    if (pEntryMatches && NumEntries >= 1) std::memset(pEntryMatches, 0, sizeof(uint32_t) * (size_t)NumEntries);
+    const k4_near_params p = {MaxTotMM, CoreLen, CoreDelta, MaxNumCoreSlides, MaxMatches, CurMaxIter, NumAllocdIdentNodes, 0};
+    const uint64_t off = 0;
+    const uint32_t len = (uint32_t)ProbeLen;
+    int32_t rslt = 0;
+    std::vector<uint32_t> Counts(pEntryMatches && NumEntries >= 1 ? inf.n_entries : 0);
+    std::lock_guard<std::mutex> dev(m_Mtx);
+    const int rc = k4_all_near_matches_batch(m_pIdx, &p, 1, pProbeSeq, &off, &len, &ProbeEntry, &ProbeOfs, &rslt, Counts.empty() ? nullptr : Counts.data(),
+                                             Counts.size());
+    if (rc != K4_OK) return Fail(rc);
+    for (size_t e = 0; e < Counts.size() && e < (size_t)NumEntries; e++) pEntryMatches[e] = Counts[e];
+    return rslt;
+  }
+
+  // The throughput form of `genzygosity` (ThreadedCoredApprox over every window of the source entries): the sources x entries
+  // matrix, the unique windows per source, optionally one status byte per start locus; k4sfx.h has the statuses.
+  int ZygosityBatch(const k4_zygosity_params& Pars, int SrcFirst, int SrcCount, uint32_t* pMatrix, uint32_t* pSubseqs, uint8_t* pStatus,
+                    uint64_t StatusLen, k4_zygosity_totals* pTotals) {
+    if (!m_pIdx) return K4_ERR_PARAMS;
+    std::lock_guard<std::mutex> dev(m_Mtx);
+    const int rc = k4_zygosity_batch(m_pIdx, &Pars, SrcFirst, SrcCount, pMatrix, pSubseqs, pStatus, StatusLen, pTotals);
+    return rc == K4_OK ? 0 : Fail(rc);
+  }
+
   // CSfxArray::AlignPairedRead, SfxArray.h:880-896 -- identical parameter list (CKAligner's mate rescue,
   // KAligner.cpp:3372-3386,3476-3490).  -1 errors, 0 no match, 1 placed with mismatches only.
   int AlignPairedRead(bool b3primeExtend, bool bAntisense, uint32_t ChromID, uint32_t StartLoci, uint32_t EndLoci, int MinInsertSize,

@@ -701,6 +701,59 @@ int k4_species_kmers_batch_dev(k4_index* ix, const k4_kmarkers_params* p, int32_
                                uint64_t status_len, k4_kmarkers_totals* totals, void* stream);
 double k4_kmarkers_last_kernel_ms(const k4_index* ix);
 
+/* ---- genzygosity: LocateAllNearMatches and the scan ----------------------------------------------------------------
+ * k4_all_near_matches_batch <- CSfxArray::LocateAllNearMatches (SfxArray.cpp:4820-5091): probe i (lens[i] codes at seqs + offs[i],
+ * compared on the low nibble) came from entry id probe_entries[i] at probe_ofs[i].  Both strands; cores of core_len at 0, then
+ * every core_delta, the last one right-aligned (:4906-4917), at most max_core_slides per strand; a candidate is extended over the
+ * whole probe with at most max_tot_mm mismatches and never across an end-of-sequence symbol.  rslts[i] = -1 when a match lies in
+ * the probe's own entry at another locus, or when a match in another entry arrives after max_matches (> 0) of them; else the
+ * number of matches in other entries.  counts (may be null): counts[i * n_entries + id - 1] = matches in the entry with that id
+ * (ids above n_entries are not counted), on a -1 as the reference's walk had them when it returned.  cur_max_iter (0: none) and
+ * n_ident_nodes limit the walk as CurMaxIter and NumAllocdIdentNodes do, the check at the 100th iteration included.
+ * K4_ERR_PARAMS: a probe over 1000 bases or shorter than core_len, core_len or core_delta below 1, max_core_slides outside
+ * 1..32, a limit below 0, a null argument, counts_cap < n * n_entries with counts given.
+ * k4_zygosity_batch <- genzygosity (genzygosity/genzygosity.cpp:1122-1236, the derivation of :681-697 and :998-1027): every
+ * subseq_len window of the source entries src_first .. src_first + src_count - 1 (ordinals 1..n_entries of the entry table) is
+ * passed over when it holds a code above N or more than max_ns N, else asked with CoreLen = max(MinCoreLen, subseq_len /
+ * (max_subs + 1)), MaxIter and the slides of `mode`, and 1 024 000 ident nodes.  matrix[r * n_entries + id - 1] = the windows of
+ * source r unique to it that matched the entry with that id, subseqs[r] = its unique windows.  status (may be null), one byte per
+ * start locus of the source entries in order: 0 passed over (or no window starts here), 1 the call returned -1, 2 unique
+ * without a match elsewhere, 3 unique with.  An entry shorter than subseq_len has no windows (the reference's front end never
+ * gets past such an entry); no window fits into it either, so its row and its column stay 0.  totals.ordered: the windows that
+ * needed the sequential walk; second_launch: those among them whose dedupe set went to device memory.  K4_ERR_PARAMS: subseq_len outside 20..1000, max_subs outside
+ * 0..min(30, subseq_len - 18), max_ns outside 0..5, max_matches outside 0..1000000, mode outside 0..3, source entries outside
+ * 1..n_entries, status_len below the source entries' loci, a null argument.  K4_ERR_UNSUPPORTED: more than 16384 entries.
+ * Nothing is written into the index.  The _dev forms take every array as a device pointer and a stream, and return when the
+ * stream has finished.  k4_zygosity_last_kernel_ms: the time on the stream from the first launch of the last of these calls to
+ * its last, 0 when it launched none.  Between them the host looks at the list of deferred probes, once in a given-probe call and
+ * once per 64 launches (1 048 576 start loci) of the scan: that wait is in the figure. */
+typedef struct {
+  int32_t max_tot_mm, core_len, core_delta, max_core_slides;
+  int32_t max_matches;    /* 0: no limit */
+  int32_t cur_max_iter;   /* 0: no limit */
+  int32_t n_ident_nodes;  /* NumAllocdIdentNodes */
+  int32_t reserved;
+} k4_near_params;
+typedef struct {
+  int32_t subseq_len;   /* -l 20..1000 */
+  int32_t max_subs;     /* -s */
+  int32_t max_ns;       /* -n 0..5 */
+  int32_t max_matches;  /* -x 0..1000000, 0: no limit */
+  int32_t mode;         /* -m 0..3 */
+  int32_t reserved;
+} k4_zygosity_params;
+typedef struct { uint64_t windows, passed_over, rejected, unique, unique_matched, ordered, second_launch; } k4_zygosity_totals;
+int k4_all_near_matches_batch(k4_index* ix, const k4_near_params* p, int64_t n, const uint8_t* seqs, const uint64_t* offs, const uint32_t* lens,
+                              const uint32_t* probe_entries, const uint32_t* probe_ofs, int32_t* rslts, uint32_t* counts, uint64_t counts_cap);
+int k4_all_near_matches_batch_dev(k4_index* ix, const k4_near_params* p, int64_t n, const void* d_seqs, const void* d_offs, const void* d_lens,
+                                  const void* d_probe_entries, const void* d_probe_ofs, void* d_rslts, void* d_counts, uint64_t counts_cap,
+                                  void* stream);
+int k4_zygosity_batch(k4_index* ix, const k4_zygosity_params* p, int32_t src_first, int32_t src_count, uint32_t* matrix, uint32_t* subseqs,
+                      uint8_t* status, uint64_t status_len, k4_zygosity_totals* totals);
+int k4_zygosity_batch_dev(k4_index* ix, const k4_zygosity_params* p, int32_t src_first, int32_t src_count, void* d_matrix, void* d_subseqs,
+                          void* d_status, uint64_t status_len, k4_zygosity_totals* totals, void* stream);
+double k4_zygosity_last_kernel_ms(const k4_index* ix);
+
 /* ---- paired ends -----------------------------------------------------------------------------------------
  * k4_mate_rescue_batch <- CSfxArray::AlignPairedRead (SfxArray.h:880, SfxArray.cpp:8571-8767; MinChimericLen 0, insert
  *                         window < 1000 => the linear-scan branch :8731-8766 with AdaptiveTrim's full-length rule :5612-5638)

@@ -205,6 +205,7 @@ ABI_SYMBOLS = [
     "k4_kmer_cults_batch", "k4_kmer_cults_batch_dev", "k4_cults_last_kernel_ms", "k4_get_sfx_els",
     "k4_exact_ranges_batch", "k4_exact_ranges_batch_dev", "k4_matches_other_chroms_batch", "k4_species_kmers_batch",
     "k4_species_kmers_batch_dev", "k4_kmarkers_last_kernel_ms",
+    "k4_all_near_matches_batch", "k4_all_near_matches_batch_dev", "k4_zygosity_batch", "k4_zygosity_batch_dev", "k4_zygosity_last_kernel_ms",
 ]
 
 
@@ -220,6 +221,49 @@ class KMarkersParams(C.Structure):  # k4_kmarkers_params
 
 class KMarkersTotals(C.Structure):  # k4_kmarkers_totals
     _fields_ = [("processed", C.c_uint64), ("cultivar_specific", C.c_uint64), ("hamming_retained", C.c_uint64), ("accepted", C.c_uint64)]
+
+
+class NearParams(C.Structure):  # k4_near_params
+    _fields_ = [("max_tot_mm", C.c_int32), ("core_len", C.c_int32), ("core_delta", C.c_int32), ("max_core_slides", C.c_int32),
+                ("max_matches", C.c_int32), ("cur_max_iter", C.c_int32), ("n_ident_nodes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ZygosityParams(C.Structure):  # k4_zygosity_params
+    _fields_ = [("subseq_len", C.c_int32), ("max_subs", C.c_int32), ("max_ns", C.c_int32), ("max_matches", C.c_int32), ("mode", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class ZygosityTotals(C.Structure):  # k4_zygosity_totals
+    _fields_ = [("windows", C.c_uint64), ("passed_over", C.c_uint64), ("rejected", C.c_uint64), ("unique", C.c_uint64),
+                ("unique_matched", C.c_uint64), ("ordered", C.c_uint64), ("second_launch", C.c_uint64)]
+
+
+ZYG_PASSED_OVER, ZYG_NOT_UNIQUE, ZYG_UNIQUE, ZYG_UNIQUE_MATCHED = range(4)
+
+
+def genzygosity_limits(tot_seqs_len, subseq_len=25, max_subs=2, mode=0):
+    """(CoreLen, MaxNumSlides, MaxIter) that `genzygosity -l -s -m` asks LocateAllNearMatches with over an index of tot_seqs_len bases
+    (genzygosity.cpp:681-697, :998-1027, :1190); index.zygosity derives the same in the library"""
+    min_core = (5 if tot_seqs_len < 20000000 else 8 if tot_seqs_len < 250000000 else 10) + (4, 2, 0, 6)[mode]
+    return max(min_core, subseq_len // (max_subs + 1)), (4, 6, 8, 3)[mode], (5000, 25000, 50000, 1000)[mode]
+
+
+def genzygosity_csv(index, subseq_len=25, max_subs=2, max_ns=1, max_matches=5000, mode=0, threshold=0.25):
+    """The two files `genzygosity -l -s -n -x -m -z -o -O` writes, as bytes (thresholded, raw): index.zygosity over every entry, then
+    on the host the report of genzygosity.cpp:746-771 -- every (source, target) pair in order as "src",Subseqs,"targ",Matrix in
+    the raw file, and in the thresholded one, with the proportion appended, the pairs of a source with unique windows whose
+    proportion is at least the threshold.  index: a SfxIndex, or anything with zygosity() and entry()."""
+    matrix, subseqs, _ = index.zygosity(subseq_len=subseq_len, max_subs=max_subs, max_ns=max_ns, max_matches=max_matches, mode=mode)[:3]
+    names = [index.entry(i + 1)["name"] for i in range(matrix.shape[1])]
+    thr, raw = [], []
+    for s, src in enumerate(names):
+        n = int(subseqs[s])
+        for t, targ in enumerate(names):
+            m = int(matrix[s, t])
+            if n > 0 and m / n >= threshold:
+                thr.append('"%s",%d,"%s",%d,%1.6f\n' % (src, n, targ, m, m / n))
+            raw.append('"%s",%d,"%s",%d\n' % (src, n, targ, m))
+    return "".join(thr).encode(), "".join(raw).encode()
 
 
 KMER_NOT_KMER, KMER_FIRST_FOREIGN, KMER_DUPLICATE, KMER_FOREIGN_HIT, KMER_HAMMING, KMER_PREFIX, KMER_ACCEPTED = range(1, 8)
@@ -687,6 +731,12 @@ def lib():
     L.k4_kmarkers_last_kernel_ms.argtypes = [vp]
     L.k4_kmarkers_last_kernel_ms.restype = dbl
     L.k4_get_sfx_els.argtypes = [vp, u64, u64, vp]
+    L.k4_all_near_matches_batch.argtypes = [vp, C.POINTER(NearParams), i64, vp, vp, vp, vp, vp, vp, vp, u64]
+    L.k4_all_near_matches_batch_dev.argtypes = [vp, C.POINTER(NearParams), i64, vp, vp, vp, vp, vp, vp, vp, u64, vp]
+    L.k4_zygosity_batch.argtypes = [vp, C.POINTER(ZygosityParams), C.c_int32, C.c_int32, vp, vp, vp, u64, C.POINTER(ZygosityTotals)]
+    L.k4_zygosity_batch_dev.argtypes = [vp, C.POINTER(ZygosityParams), C.c_int32, C.c_int32, vp, vp, vp, u64, C.POINTER(ZygosityTotals), vp]
+    L.k4_zygosity_last_kernel_ms.argtypes = [vp]
+    L.k4_zygosity_last_kernel_ms.restype = dbl
     _lib = L
     return L
 
@@ -1166,6 +1216,49 @@ class SfxIndex:
     def kmarkers_kernel_ms(self):
         """device milliseconds of the last exact_ranges / matches_other_chroms / species_kmers call's launches"""
         return lib().k4_kmarkers_last_kernel_ms(self.h)
+
+    def all_near_matches(self, probes, probe_entries, probe_ofs, max_tot_mm, core_len, core_delta, max_core_slides, max_matches=0,
+                         cur_max_iter=0, n_ident_nodes=1024000, counts=True):
+        """CSfxArray::LocateAllNearMatches (libkit4b/SfxArray.cpp:4820-5091) for a batch of probes (codes) that came from the entries
+        with ids probe_entries at probe_ofs: (rslts int32: -1 or the matches in other entries; counts uint32 n x n_entries by entry
+        id - 1, or None)"""
+        cat, offs, lens = _flatten(probes)
+        n = len(lens)
+        ents = np.ascontiguousarray(probe_entries, dtype=np.uint32)
+        pofs = np.ascontiguousarray(probe_ofs, dtype=np.uint32)
+        if len(ents) != n or len(pofs) != n:
+            raise ValueError("one probe entry and one offset per probe")
+        n_ent = self.info()["n_entries"]
+        rslts = np.zeros(n, dtype=np.int32)
+        cnt = np.zeros((n, n_ent), dtype=np.uint32) if counts else None
+        cat = np.concatenate([cat, np.zeros(16, np.uint8)])
+        p = NearParams(max_tot_mm, core_len, core_delta, max_core_slides, max_matches, cur_max_iter, n_ident_nodes, 0)
+        self._ck(lib().k4_all_near_matches_batch(self.h, C.byref(p), n, cat.ctypes.data, offs.ctypes.data, lens.ctypes.data, ents.ctypes.data,
+                                                 pofs.ctypes.data, rslts.ctypes.data, cnt.ctypes.data if counts else None, n * n_ent))
+        return rslts, cnt
+
+    def zygosity(self, subseq_len=25, max_subs=2, max_ns=1, max_matches=5000, mode=0, src_first=1, src_count=None, status=False):
+        """`genzygosity`'s scan (genzygosity/genzygosity.cpp:1122-1236) over the source entries src_first .. (ordinals, all by default):
+        (matrix uint32 src_count x n_entries, subseqs uint32, totals dict[, status bytes: one ZYG_* per start locus of the sources])"""
+        n_ent = self.info()["n_entries"]
+        if src_count is None:
+            src_count = max(n_ent - src_first + 1, 0)
+        rows = max(src_count, 0)
+        loci = sum(self.entry(src_first + r)["seq_len"] for r in range(rows) if 1 <= src_first + r <= n_ent)
+        matrix, subseqs = np.zeros((rows, n_ent), dtype=np.uint32), np.zeros(rows, dtype=np.uint32)
+        st = np.zeros(max(loci, 1), dtype=np.uint8) if status else None
+        p = ZygosityParams(subseq_len, max_subs, max_ns, max_matches, mode, 0)
+        tot = ZygosityTotals()
+        m_arg = matrix if matrix.size else np.zeros(1, np.uint32)
+        s_arg = subseqs if subseqs.size else np.zeros(1, np.uint32)
+        self._ck(lib().k4_zygosity_batch(self.h, C.byref(p), src_first, src_count, m_arg.ctypes.data, s_arg.ctypes.data,
+                                         st.ctypes.data if status else None, len(st) if status else 0, C.byref(tot)))
+        out = (matrix, subseqs, {f[0]: int(getattr(tot, f[0])) for f in ZygosityTotals._fields_})
+        return out + (st[:loci],) if status else out
+
+    def zygosity_kernel_ms(self):
+        """device milliseconds of the last all_near_matches / zygosity call's launches"""
+        return lib().k4_zygosity_last_kernel_ms(self.h)
 
     def kalign_batch(self, reads, max_subs=5, min_edit_dist=1, max_ns=1, pmode=0, strand=STRAND_BOTH, max_ml=1,
                      pe_mode=0, min_core_len=0, max_num_slides=0):

@@ -124,6 +124,9 @@ struct K4CultState {
 // kmarkers (k4_kmarkers.hip), grow-only: the rank of every entry in the target list, the outputs of the host-pointer entry points
 // (status bytes; first indices and counts; MatchesOtherChroms answers), the four tallies and the long-run flag
 struct K4MarkState { K4DevBuf rank, out, ctl; K4Timer timer; };
+// genzygosity (k4_zygosity.hip), grow-only: the outputs and probe origins of the host-pointer entry points, the scan's internal
+// status bytes and source-entry offsets, the list of probes that wait for the second launch, its dedupe tables, the control block
+struct K4ZygState { K4DevBuf out, status, pre, list, big, ctl; K4Timer timer; uint64_t second = 0; };
 
 struct k4_index {
   int device = 0;
@@ -170,6 +173,7 @@ struct k4_index {
   K4HammState hmm;
   K4CultState cul;
   K4MarkState kmk;
+  K4ZygState zyg;
   // k4_open_async: the arrays are uploaded and the device structures built by this thread; k4_open_wait joins it
   std::thread loader;
   int load_rc = 0;

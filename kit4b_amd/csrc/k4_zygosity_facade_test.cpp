@@ -1,0 +1,85 @@
+// kit4b_amd/csrc/k4_zygosity_facade_test.cpp -- include/k4_sfxarray.hpp's LocateAllNearMatches and ZygosityBatch the way genzygosity
+// calls CSfxArray's (genzygosity/genzygosity.cpp:1193-1206): one call per probe, the caller's counts array and ident-node count.
+// usage: k4_zygosity_facade_test index.sfx calls.txt scan.txt
+// calls.txt, per call: "len digits mm core_len core_delta slides max_matches num_entries entry ofs max_iter nodes rslt" and
+// num_entries counts (the reference's returns)
+// scan.txt: "subseq_len max_subs max_ns max_matches mode n_entries" then n_entries subseqs, n_entries x n_entries matrix cells,
+// the five totals, the loci and one word of that many status digits
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "k4_sfxarray.hpp"
+
+int main(int argc, char** argv) {
+  if (argc < 4) return 1;
+  CSfxArray* pSfx = new CSfxArray;
+  if (pSfx->Open(argv[1]) < 0) {
+    while (pSfx->NumErrMsgs()) fprintf(stderr, "%s\n", pSfx->GetErrMsg());
+    return 2;
+  }
+  if (pSfx->SetTargBlock(1) < 0) return 3;
+  FILE* f = fopen(argv[2], "r");
+  if (!f) return 4;
+  int nCalls = 0, badRslt = 0, badCounts = 0, badProbe = 0, badFill = 0;
+  for (;;) {
+    unsigned len;
+    if (fscanf(f, "%u", &len) != 1) break;
+    std::vector<char> s(len + 2);
+    int mm, coreLen, coreDelta, slides, maxMatches, numEntries, maxIter, nodes, want;
+    unsigned entry, ofs;
+    if (fscanf(f, "%s %d %d %d %d %d %d %u %u %d %d %d", s.data(), &mm, &coreLen, &coreDelta, &slides, &maxMatches, &numEntries, &entry, &ofs, &maxIter,
+               &nodes, &want) != 12)
+      return 5;
+    std::vector<etSeqBase> Probe(len + 8, 0), Keep;
+    for (unsigned j = 0; j < len; j++) Probe[j] = (etSeqBase)(s[j] - '0');
+    Keep = Probe;
+    std::vector<uint32_t> Counts((size_t)numEntries + 2, 0xeeeeeeeeu);
+    const int Rslt = pSfx->LocateAllNearMatches(mm, coreLen, coreDelta, slides, maxMatches, numEntries, Counts.data(), entry, ofs, (int)len, Probe.data(),
+                                                maxIter, nodes, nullptr);
+    bool ok = true;
+    for (int e = 0; e < numEntries; e++) {
+      unsigned c;
+      if (fscanf(f, "%u", &c) != 1) return 5;
+      ok = ok && Counts[(size_t)e] == c;
+    }
+    if (Rslt != want) badRslt++;
+    if (!ok) badCounts++;
+    if (Probe != Keep) badProbe++;
+    if (Counts[(size_t)numEntries] != 0xeeeeeeeeu || Counts[(size_t)numEntries + 1] != 0xeeeeeeeeu) badFill++;
+    nCalls++;
+  }
+  fclose(f);
+  printf("calls %d bad returns %d bad counts %d probes changed %d fill touched %d\n", nCalls, badRslt, badCounts, badProbe, badFill);
+  if (!(f = fopen(argv[3], "r"))) return 4;
+  k4_zygosity_params P;
+  memset(&P, 0, sizeof(P));
+  unsigned nEnt;
+  if (fscanf(f, "%d %d %d %d %d %u", &P.subseq_len, &P.max_subs, &P.max_ns, &P.max_matches, &P.mode, &nEnt) != 6) return 5;
+  std::vector<uint32_t> wantSub(nEnt), wantMat((size_t)nEnt * nEnt);
+  for (unsigned j = 0; j < nEnt; j++)
+    if (fscanf(f, "%u", &wantSub[j]) != 1) return 5;
+  for (size_t j = 0; j < wantMat.size(); j++)
+    if (fscanf(f, "%u", &wantMat[j]) != 1) return 5;
+  unsigned long long w[5], total;
+  if (fscanf(f, "%llu %llu %llu %llu %llu %llu", &w[0], &w[1], &w[2], &w[3], &w[4], &total) != 6) return 5;
+  std::vector<char> want(total + 2);
+  if (fscanf(f, "%s", want.data()) != 1) return 5;
+  fclose(f);
+  std::vector<uint8_t> Status(total + 4, 0xee);
+  std::vector<uint32_t> Sub(nEnt, 0xeeeeeeeeu), Mat((size_t)nEnt * nEnt, 0xeeeeeeeeu);
+  k4_zygosity_totals Tot;
+  const int Rslt = pSfx->ZygosityBatch(P, 1, (int)nEnt, Mat.data(), Sub.data(), Status.data(), total + 4, &Tot);
+  unsigned long long bad = 0;
+  for (unsigned long long k = 0; k < total; k++) bad += Status[k] != (uint8_t)(want[k] - '0');
+  const bool fill = Status[total] == 0xee && Status[total + 3] == 0xee;
+  printf("scan %d bad status %llu matrix %d subseqs %d totals %d fill %d\n", Rslt, bad, Mat == wantMat ? 1 : 0, Sub == wantSub ? 1 : 0,
+         Tot.windows == w[0] && Tot.passed_over == w[1] && Tot.rejected == w[2] && Tot.unique == w[3] && Tot.unique_matched == w[4] ? 1 : 0, fill ? 1 : 0);
+  P.subseq_len = 19;
+  printf("errors %d", pSfx->ZygosityBatch(P, 1, (int)nEnt, Mat.data(), Sub.data(), Status.data(), total + 4, &Tot));
+  etSeqBase Short[8] = {0, 1, 2, 3, 0, 1, 2, 3};
+  const int TooShort = pSfx->LocateAllNearMatches(1, 9, 9, 4, 0, 0, nullptr, 1, 0, 8, Short, 0, 100, nullptr);
+  printf(" %d msgs %d\n", TooShort, pSfx->NumErrMsgs());
+  delete pSfx;
+  return 0;
+}

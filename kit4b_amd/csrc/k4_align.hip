@@ -63,6 +63,9 @@ struct K4Probe {
 // first at base fm (mm = Hamming distance of the whole read, 0xFF when the window was never fetched because the 16-base
 // signature already disagreed).  A later phase with core length cl then knows without any memory access that nothing
 // starts with its offset-0 core (empty, or fm < cl) or that exactly the suffix at pos does, with distance mm.
+// Spare bits: fm is at most the read length (<= 512), so bits 58..61 of a memo word are always zero; every other bit is in use
+// (kind 62..63, fm 48..57, mm 40..47, pos 0..39).  Four bits a word are too few for the read's length, which therefore travels
+// beside the read's id (K4Survivor, k4_align_common.h), not here.
 #define K4_MEMO_NONE 0ull
 K4_DEV uint64_t k4d_memo_pack(int kind, uint64_t pos, int mm, int fm) {
   return ((uint64_t)kind << 62) | ((uint64_t)(fm & 0x3FFF) << 48) | ((uint64_t)(mm & 0xFF) << 40) | (pos & 0xFFFFFFFFFFull);
@@ -338,12 +341,6 @@ K4_DEV int k4d_lcm_fast(const K4AlignArgs& a, const K4Lane<NCH>& ln, int len, in
   return k4d_lcm_result(*p_inst, *p_low, p_nxt, st, rp.mm_delta, rp.max_hits, p_inst, p_low);
 }
 
-// reverse the order of the 32 two-bit groups of a word
-K4_DEV uint64_t k4d_rev2(uint64_t x) {
-  uint64_t y = __brevll(x);
-  return ((y & 0x5555555555555555ull) << 1) | ((y >> 1) & 0x5555555555555555ull);
-}
-
 // etSeqBase bytes -> this lane's LDS column: forward words [0][c], reverse-complement words [1][c], pad words zero.
 // Returns K4_RF_* flags; n_ns = number of N (the fast path cannot express N: such reads go to the general kernel).
 // The four 2-bit codes of a word already masked to 0x03030303 (first base in the low byte), as b0<<6 | b1<<4 | b2<<2 | b3
@@ -461,14 +458,17 @@ K4_DEV uint32_t k4d_pack_read(const uint8_t* __restrict__ src, int len, uint64_t
 }
 
 // One AlignReads phase per launch.  FIRST: lanes take reads j = 0..n_reads-1 and pack them; later steps take the
-// compacted survivors (ids + packed rows) of the previous step.
+// compacted survivors ({id, length} + packed rows) of the previous step.  in_ids: the 4-byte ids of the deferred list (second
+// launch of a split first phase) or the previous step's K4Survivor slots (later steps).  claim: this launch's tile counter.
 template <int EL, int NCH, bool FIRST, typename KT, bool DEFER = false>
 __global__ void __launch_bounds__(K4_BS(NCH), (NCH >= 16 ? K4_STEP_WAVES_LONG : NCH >= 8 ? K4_STEP_WAVES_MID : NCH == 5 ? K4_STEP_WAVES_5 : K4_STEP_WAVES)) k4k_align_step(K4AlignArgs a, int step, const uint32_t* __restrict__ in_ids,
                                                       const uint64_t* __restrict__ in_rows,
-                                                      const uint32_t* __restrict__ in_count, uint32_t* __restrict__ out_ids,
-                                                      uint64_t* __restrict__ out_rows, uint32_t* __restrict__ out_count) {
+                                                      const uint32_t* __restrict__ in_count, K4Survivor* __restrict__ out_ids,
+                                                      uint64_t* __restrict__ out_rows, uint32_t* __restrict__ out_count,
+                                                      uint32_t* __restrict__ claim) {
   extern __shared__ uint64_t lds[];
   constexpr int NW = NCH + 1;
+  constexpr int SW = K4_ROW_STRAND_WORDS(NCH);  // strand words of a survivor row; the memos follow them
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   K4Lane<NCH> ln;
@@ -508,7 +508,6 @@ __global__ void __launch_bounds__(K4_BS(NCH), (NCH >= 16 ? K4_STEP_WAVES_LONG : 
   uint64_t* col = lds + tid;
   uint32_t n_lookup = 0, n_probe = 0, n_cand = 0, n_slow = 0, n_bases = 0, n_done = 0;
   const int64_t count = (FIRST && !(DEFER && in_ids != nullptr)) ? a.n_reads : (int64_t)*in_count;
-  const int64_t stride = (int64_t)gridDim.x * K4_BS(NCH);
   // Survivor slots are reserved K4_CHUNK at a time (one atomic per chunk, not per wave iteration: a single counter
   // word serialises at ~88 atomics/us).  ch_cur / ch_left are wave-uniform: every lane of the wave runs every
   // iteration of this loop, inactive lanes masked, so the copies never diverge.  Unused slots hold K4_NO_READ.
@@ -517,18 +516,36 @@ __global__ void __launch_bounds__(K4_BS(NCH), (NCH >= 16 ? K4_STEP_WAVES_LONG : 
   const bool from_list = !FIRST || (DEFER && in_ids != nullptr);
   const bool may_defer = DEFER && FIRST && in_ids == nullptr && a.defer_ids != nullptr;
   uint32_t dch_cur = 0, dch_left = 0;  // the deferred list's chunk, as ch_cur / ch_left
-  for (int64_t jb = (int64_t)blockIdx.x * K4_BS(NCH) + (tid & ~63); jb < count; jb += stride) {
+  // The input is dealt in tiles of K4_TILE_GROUPS consecutive 64-slot groups, claimed from the launch's counter (lane 0 asks, the
+  // wave hears): the grid is what is resident, a wave that meets cheap reads takes more tiles, and the launch ends within about
+  // one group of its slowest wave.  No wave waits for another: each leaves at its first claim at or past count.  Which wave
+  // takes which read is of no consequence -- everything a read leaves behind is stored under its id.
+  // jb / tile_end are wave-uniform (scalar): the claim is read back with readfirstlane, every lane of the wave is active there.
+  for (int64_t jb = 0, tile_end = 0;; jb += 64) {
+    if (jb >= tile_end) {  // the wave's tile is done (or it has none yet): the next one
+      uint32_t tile = 0;
+      if (lane == 0) tile = atomicAdd(claim, 1u);
+      jb = (int64_t)__builtin_amdgcn_readfirstlane(tile) * (K4_TILE_GROUPS * 64);
+      if (jb >= count) break;
+      tile_end = min(jb + (int64_t)(K4_TILE_GROUPS * 64), count);
+    }
     const int64_t j = jb + lane;
     bool active = j < count;
     int64_t i = 0;
+    int len = 0;
     if (active) {
-      i = from_list ? (int64_t)in_ids[j] : j;
+      if (!FIRST) {
+        const K4Survivor sv = reinterpret_cast<const K4Survivor*>(in_ids)[j];
+        i = (int64_t)sv.id;
+        len = (int)sv.len;
+      } else
+        i = from_list ? (int64_t)in_ids[j] : j;
       if (from_list && (uint32_t)i == K4_NO_READ) active = false;
     }
     bool slow = false, survive = false, deferred = false;
     int ext_from = -1;  // >= 0: every standard phase ran here without a result; the general kernel starts at the optional ones
     if (active) {
-      const int len = (int)a.lens[i];
+      if (FIRST) len = (int)a.lens[i];
       // the read's plan: one LDS load by length (a length outside 1..32*NCH takes the K4_RF_TOOLONG path below and has no use
       // for a plan: it reads record 0), or the same function per lane
       uint4 pr;
@@ -568,22 +585,22 @@ __global__ void __launch_bounds__(K4_BS(NCH), (NCH >= 16 ? K4_STEP_WAVES_LONG : 
         if (((a.mode == 1 && a.kp.pe_mode == 4) || a.best) && !skip) slow = true;  // LocateBestMatches lives in the general kernel
       } else {
         const uint64_t* row = in_rows + (int64_t)j * K4_ROW_WORDS(NCH);
-        {
-          const k4_u64x2_a8 mv = *reinterpret_cast<const k4_u64x2_a8*>(row + 2 * NCH);
-          ln.memo[0] = mv.x; ln.memo[K4_BS(NCH)] = mv.y;
-        }
-        uint64_t rw[2 * NCH];
+        uint64_t rw[K4_ROW_WORDS(NCH)];
 #pragma unroll
-        for (int c = 0; c < NCH; c++) {  // rows are 16-byte aligned: NCH 16-byte loads
+        for (int c = 0; c < K4_ROW_WORDS(NCH) / 2; c++) {  // rows are 16-byte aligned: 16-byte loads
           const k4_u64x2_a8 v = *reinterpret_cast<const k4_u64x2_a8*>(row + 2 * c);
           rw[2 * c] = v.x; rw[2 * c + 1] = v.y;
         }
+        ln.memo[0] = rw[SW]; ln.memo[K4_BS(NCH)] = rw[SW + 1];
 #pragma unroll
-        for (int c = 0; c < NCH; c++) {
-          col[c * K4_BS(NCH)] = rw[c];
-          col[(NW + c) * K4_BS(NCH)] = rw[NCH + c];
-        }
+        for (int c = 0; c < NCH; c++) col[c * K4_BS(NCH)] = rw[c];
         col[NCH * K4_BS(NCH)] = 0;
+        if (K4_LEAN_ROW(NCH))  // the other strand from the words just stored: nothing of it stays in registers
+          k4d_revcomp_words<NCH, K4_BS(NCH)>(col, len, col + NW * K4_BS(NCH));
+        else {
+#pragma unroll
+          for (int c = 0; c < NCH; c++) col[(NW + c) * K4_BS(NCH)] = rw[SW - NCH + c];
+        }
         col[(NW + NCH) * K4_BS(NCH)] = 0;
       }
       if (!skip && ((pr.w & K4_PLAN_NO_CORE) || rp.max_hits < 1 || rp.max_hits > a.max_hits)) slow = true;  // the general kernel reports it
@@ -634,7 +651,7 @@ __global__ void __launch_bounds__(K4_BS(NCH), (NCH >= 16 ? K4_STEP_WAVES_LONG : 
     const uint32_t cnt = (uint32_t)__popcll(m);
     if (cnt) {
       if (cnt > ch_left) {
-        for (uint32_t q = lane; q < ch_left; q += 64) out_ids[ch_cur + q] = K4_NO_READ;  // retire the old chunk's tail
+        for (uint32_t q = lane; q < ch_left; q += 64) out_ids[ch_cur + q] = K4Survivor{K4_NO_READ, 0u};  // retire the old chunk's tail
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(out_count, (uint32_t)K4_CHUNK);
         ch_cur = __shfl(base, 0, 64);
@@ -642,27 +659,25 @@ __global__ void __launch_bounds__(K4_BS(NCH), (NCH >= 16 ? K4_STEP_WAVES_LONG : 
       }
       if (survive) {
         const uint32_t slot = ch_cur + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        out_ids[slot] = (uint32_t)i;
+        out_ids[slot] = K4Survivor{(uint32_t)i, (uint32_t)len};
         uint64_t* row = out_rows + (int64_t)slot * K4_ROW_WORDS(NCH);
+        // word w of the row: the strand words (forward, then -- full form -- reverse complement), the two memos, zero padding
+        auto row_word = [&](int w) -> uint64_t {
+          if (w < SW) return w < NCH ? col[w * K4_BS(NCH)] : col[(NW + w - NCH) * K4_BS(NCH)];
+          return w == SW ? ln.memo[0] : w == SW + 1 ? ln.memo[K4_BS(NCH)] : 0ull;
+        };
 #pragma unroll
-        for (int c = 0; c < NCH; c++) {
+        for (int c = 0; c < K4_ROW_WORDS(NCH) / 2; c++) {
           k4_u64x2_a8 v;
-          const int w0 = 2 * c, w1 = 2 * c + 1;
-          v.x = w0 < NCH ? col[w0 * K4_BS(NCH)] : col[(NW + w0 - NCH) * K4_BS(NCH)];
-          v.y = w1 < NCH ? col[w1 * K4_BS(NCH)] : col[(NW + w1 - NCH) * K4_BS(NCH)];
+          v.x = row_word(2 * c); v.y = row_word(2 * c + 1);
           *reinterpret_cast<k4_u64x2_a8*>(row + 2 * c) = v;
-        }
-        {
-          k4_u64x2_a8 mv;
-          mv.x = ln.memo[0]; mv.y = ln.memo[K4_BS(NCH)];
-          *reinterpret_cast<k4_u64x2_a8*>(row + 2 * NCH) = mv;
         }
       }
       ch_cur += cnt;
       ch_left -= cnt;
     }
   }
-  for (uint32_t q = lane; q < ch_left; q += 64) out_ids[ch_cur + q] = K4_NO_READ;
+  for (uint32_t q = lane; q < ch_left; q += 64) out_ids[ch_cur + q] = K4Survivor{K4_NO_READ, 0u};
   if (FIRST && DEFER)
     for (uint32_t q = lane; q < dch_left; q += 64) a.defer_ids[dch_cur + q] = K4_NO_READ;
   // per-wave tallies -> one atomic per counter per wave (lookups of reads that went slow are recounted there)
@@ -691,6 +706,16 @@ static size_t k4_survivor_slots(size_t cap) {
   return cap + cap / 7 + (size_t)2 * 2048 * 4 * K4_CHUNK + K4_CHUNK;
 }
 
+// words of the widest survivor row among the length classes up to nch: a workspace reserved for long reads serves batches of
+// shorter ones, and the row form is the class's own (K4_LEAN_ROW)
+static size_t k4_row_words_upto(int nch) {
+  size_t m = K4_ROW_WORDS(4);
+  if (nch >= 5) m = std::max<size_t>(m, K4_ROW_WORDS(5));
+  if (nch >= 8) m = std::max<size_t>(m, K4_ROW_WORDS(8));
+  if (nch >= 16) m = std::max<size_t>(m, K4_ROW_WORDS(16));
+  return m;
+}
+
 static int nch_for(int max_len) {
   if (max_len <= 128) return 4;
   if (max_len <= 160) return 5;
@@ -714,19 +739,21 @@ extern "C" int k4_reserve(k4_index* ix, int64_t max_reads, int32_t max_read_len,
     touched = true;
     w.cap_reads = 0;  // (zero until the whole group has grown: K4DevBuf::reserve, k4_pool.h; every *_dev call then refuses the workspace)
     w.cap_len = 0;
-    // Survivors of step t (ids + packed rows) ping-pong between two buffers.  Slots are handed out K4_CHUNK at a time
-    // per wave; a wave abandons the tail of its chunk (at most 63 slots) when the next ballot does not fit, and leaves
-    // one partly used chunk behind when it ends.  Step t+1 walks over step t's slots, holes included, but places only
-    // real survivors again.  So every chunk a wave has moved on from holds at least K4_CHUNK - 63 real entries: a launch
-    // that places s survivors uses at most s * K4_CHUNK / (K4_CHUNK - 63) slots plus one chunk per wave of its grid, which
-    // has at most 2048 * 4 waves.  Step 0 of an index with repeat families is two launches that append to one list (and
-    // place n survivors between them at the most): two partly used chunks per wave, which the bound for one launch does not
-    // cover.  tests/bigbatch.py restates this arithmetic, tests/test_bigbatch_cpu.py holds it against this bound.  The
-    // deferred list of that step (ids[1]) is one launch's.
+    // Survivors of step t (8-byte {id, length} slots + packed rows of K4_ROW_WORDS words) ping-pong between two buffers.
+    // Slots are handed out K4_CHUNK at a time per wave; a wave abandons the tail of its chunk (at most 63 slots) when the
+    // next ballot does not fit, and leaves one partly used chunk behind when it ends.  Step t+1 walks over step t's slots,
+    // holes included, but places only real survivors again.  So every chunk a wave has moved on from holds at least
+    // K4_CHUNK - 63 real entries: a launch that places s survivors uses at most s * K4_CHUNK / (K4_CHUNK - 63) slots plus one
+    // chunk per wave of its grid, which has at most 2048 * 4 waves (k4_resident_blocks caps it there; the resident grid of an
+    // MI355X is half of that or less, and which tiles a wave claims does not enter the argument).  Step 0 of an index with
+    // repeat families is two launches that append to one list (and place n survivors between them at the most): two partly
+    // used chunks per wave, which the bound for one launch does not cover.  tests/bigbatch.py restates this arithmetic for
+    // the largest grid the cap allows, tests/test_bigbatch_cpu.py holds it against this bound.  The deferred list of that
+    // step (4-byte ids in ids[1]) is one launch's.
     const size_t slots = k4_survivor_slots((size_t)cap);
     for (int b = 0; b < 2; b++) {
-      K4_HIP(ix, w.ids[b].reserve(slots * 4));
-      K4_HIP(ix, w.rows[b].reserve(slots * K4_ROW_WORDS(nch) * 8));
+      K4_HIP(ix, w.ids[b].reserve(slots * sizeof(K4Survivor)));
+      K4_HIP(ix, w.rows[b].reserve(slots * k4_row_words_upto(nch) * 8));
     }
     K4_HIP(ix, w.slow_list.reserve((size_t)cap * 4));
     K4_HIP(ix, w.slow_step.reserve((size_t)cap));
@@ -758,10 +785,19 @@ extern "C" int k4_reserve(k4_index* ix, int64_t max_reads, int32_t max_read_len,
   return K4_OK;
 }
 
+// blocks of a step kernel that the device holds at once (0 when the runtime cannot say), capped at the grid the survivor buffers allow
+struct K4StepGrids { int first, first_split, later; };
+static int k4_resident_blocks(const void* kernel, int block, size_t lds) {
+  int dev = 0, cus = 0, per_cu = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, lds) != hipSuccess) return 0;
+  return (int)std::min<int64_t>((int64_t)per_cu * cus, 2048 * (256 / block));
+}
+
 template <int EL, int NCH, typename KT>
 static int launch_steps(k4_index* ix, K4AlignArgs& a, int n_steps, hipStream_t st) {
   K4Workspace& w = ix->ws;
-  uint32_t* const ids[2] = {w.ids[0].as<uint32_t>(), w.ids[1].as<uint32_t>()};
+  K4Survivor* const ids[2] = {w.ids[0].as<K4Survivor>(), w.ids[1].as<K4Survivor>()};
   uint64_t* const rows[2] = {w.rows[0].as<uint64_t>(), w.rows[1].as<uint64_t>()};
   uint32_t* const ctl = w.ctl.as<uint32_t>();
   const size_t lds = (size_t)2 * (NCH + 1) * K4_BS(NCH) * 8 + (size_t)K4_DEDUP_CAP * K4_BS(NCH) * 4 + (size_t)2 * K4_BS(NCH) * 8 + (size_t)2 * K4_LDS_ENTRIES * 8 +
@@ -771,8 +807,19 @@ static int launch_steps(k4_index* ix, K4AlignArgs& a, int n_steps, hipStream_t s
     K4_HIP(ix, hipFuncSetAttribute((const void*)k4k_align_step<EL, NCH, true, KT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     K4_HIP(ix, hipFuncSetAttribute((const void*)k4k_align_step<EL, NCH, false, KT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
-  // grid-stride kernels: enough blocks to fill the chip at the kernel's occupancy, never more than the work
-  const unsigned full = 256 * 8 * (256 / K4_BS(NCH));
+  // The grid is what the device keeps resident of each kernel (its waves claim their work tile by tile), never more than the work
+  // and never more than the 2048 * 4 waves the survivor buffers are sized for (k4_survivor_slots).  Asked once per instantiation:
+  // the GPUs of one process are of one kind.
+  static const K4StepGrids res = [&]() {
+    K4StepGrids g;
+    g.first = k4_resident_blocks((const void*)k4k_align_step<EL, NCH, true, KT, false>, K4_BS(NCH), lds);
+    g.first_split = k4_resident_blocks((const void*)k4k_align_step<EL, NCH, true, KT, true>, K4_BS(NCH), lds);
+    g.later = k4_resident_blocks((const void*)k4k_align_step<EL, NCH, false, KT>, K4_BS(NCH), lds);
+    return g;
+  }();
+  if (res.first < 1 || res.first_split < 1 || res.later < 1) return k4_fail(ix, K4_ERR_INTERNAL, "no resident block count for the step kernels");
+  const int64_t work = (a.n_reads + K4_BS(NCH) - 1) / K4_BS(NCH);
+  const auto grid_of = [&](int resident) { return dim3((unsigned)std::min<int64_t>(work, resident)); };
   const bool timed = ix->timing && ix->ev_used < 4096;
   if (timed) {
     if (ix->ev_used == ix->ev0.size()) {
@@ -786,7 +833,6 @@ static int launch_steps(k4_index* ix, K4AlignArgs& a, int n_steps, hipStream_t s
     }
     K4_HIP(ix, hipEventRecord(ix->ev0[ix->ev_used], st));
   }
-  unsigned grid0 = (unsigned)std::min<int64_t>((a.n_reads + K4_BS(NCH) - 1) / K4_BS(NCH), full);
   // step 0 in two launches: every read, then those it set aside (deep k-mer buckets), listed in the id buffer step 1 will
   // overwrite; both append their survivors to the same list
   // -- on an index with repeat families (share of the suffixes in deep k-mer buckets, measured when the table was built);
@@ -794,20 +840,20 @@ static int launch_steps(k4_index* ix, K4AlignArgs& a, int n_steps, hipStream_t s
   static const int deep_mode = getenv("K4_DEEP_TO_GENERAL") ? atoi(getenv("K4_DEEP_TO_GENERAL")) : 0;  // (experiment)
   a.deep_general = (deep_mode && ix->deep_bucket_frac >= K4_DEFER_MIN_FRAC) ? deep_mode : 0;  // 1: from the first phase on, 2: from the second
   if (ix->deep_bucket_frac >= K4_DEFER_MIN_FRAC && a.deep_general != 1) {
-    a.defer_ids = ids[1];
-    hipLaunchKernelGGL((k4k_align_step<EL, NCH, true, KT, true>), dim3(grid0), dim3(K4_BS(NCH)), lds, st, a, 0, (const uint32_t*)nullptr,
-                       (const uint64_t*)nullptr, (const uint32_t*)nullptr, ids[0], rows[0], ctl + 2);
-    hipLaunchKernelGGL((k4k_align_step<EL, NCH, true, KT, true>), dim3(grid0), dim3(K4_BS(NCH)), lds, st, a, 0, (const uint32_t*)ids[1],
-                       (const uint64_t*)nullptr, (const uint32_t*)(ctl + K4_CTL_DEFER), ids[0], rows[0], ctl + 2);
+    a.defer_ids = reinterpret_cast<uint32_t*>(ids[1]);
+    hipLaunchKernelGGL((k4k_align_step<EL, NCH, true, KT, true>), grid_of(res.first_split), dim3(K4_BS(NCH)), lds, st, a, 0, (const uint32_t*)nullptr,
+                       (const uint64_t*)nullptr, (const uint32_t*)nullptr, ids[0], rows[0], ctl + 2, ctl + K4_CTL_CLAIM);
+    hipLaunchKernelGGL((k4k_align_step<EL, NCH, true, KT, true>), grid_of(res.first_split), dim3(K4_BS(NCH)), lds, st, a, 0, (const uint32_t*)a.defer_ids,
+                       (const uint64_t*)nullptr, (const uint32_t*)(ctl + K4_CTL_DEFER), ids[0], rows[0], ctl + 2, ctl + K4_CTL_CLAIM_DEFER);
   } else {
     a.defer_ids = nullptr;
-    hipLaunchKernelGGL((k4k_align_step<EL, NCH, true, KT, false>), dim3(grid0), dim3(K4_BS(NCH)), lds, st, a, 0, (const uint32_t*)nullptr,
-                       (const uint64_t*)nullptr, (const uint32_t*)nullptr, ids[0], rows[0], ctl + 2);
+    hipLaunchKernelGGL((k4k_align_step<EL, NCH, true, KT, false>), grid_of(res.first), dim3(K4_BS(NCH)), lds, st, a, 0, (const uint32_t*)nullptr,
+                       (const uint64_t*)nullptr, (const uint32_t*)nullptr, ids[0], rows[0], ctl + 2, ctl + K4_CTL_CLAIM);
   }
   for (int t = 1; t < n_steps; t++) {
     const int in = (t - 1) & 1, out = t & 1;
-    hipLaunchKernelGGL((k4k_align_step<EL, NCH, false, KT>), dim3(grid0), dim3(K4_BS(NCH)), lds, st, a, t, ids[in], rows[in],
-                       ctl + 2 + (t - 1), ids[out], rows[out], ctl + 2 + t);
+    hipLaunchKernelGGL((k4k_align_step<EL, NCH, false, KT>), grid_of(res.later), dim3(K4_BS(NCH)), lds, st, a, t, (const uint32_t*)ids[in], rows[in],
+                       ctl + 2 + (t - 1), ids[out], rows[out], ctl + 2 + t, ctl + K4_CTL_CLAIM + t);
   }
   if (timed) K4_HIP(ix, hipEventRecord(ix->ev1[ix->ev_used], st));  // (launch_all records ev2 behind the general kernel and counts the set)
   return K4_OK;
@@ -818,7 +864,7 @@ static int launch_all(k4_index* ix, K4AlignArgs& a, int max_len, int n_steps, hi
   K4Workspace& w = ix->ws;
   const int nch = nch_for(std::min(max_len, K4_MAX_FAST_READ_LEN));
   if (nch > nch_for(w.cap_len)) return k4_fail(ix, K4_ERR_INTERNAL, "workspace not reserved for read length %d", max_len);
-  if (n_steps < 1 || n_steps > K4_CTL_WORDS - 4) return k4_fail(ix, K4_ERR_INTERNAL, "bad phase count %d", n_steps);
+  if (n_steps < 1 || n_steps > K4_MAX_STEPS) return k4_fail(ix, K4_ERR_INTERNAL, "bad phase count %d", n_steps);
   a.slow_list = w.slow_list.as<uint32_t>();
   a.slow_step = w.slow_step.as<uint8_t>();
   a.ctl = w.ctl.as<uint32_t>();

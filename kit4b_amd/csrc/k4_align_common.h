@@ -5,6 +5,7 @@
 #include <string.h>
 #include <algorithm>
 #include "k4_device.h"
+#include "k4_revcomp.h"
 
 #define K4_NEED_SLOW (-100)
 #define K4_DEFER (-101)  // first launch only: the read met a deep k-mer bucket; it is taken again in the launch of its like
@@ -25,7 +26,22 @@
 #endif
 #define K4_CHUNK 512         // survivor slots a wave reserves per atomic
 #define K4_NO_READ 0xFFFFFFFFu  // hole in a survivor list
-#define K4_ROW_WORDS(nch) (2 * (nch) + 2)  // survivor row: forward + reverse-complement words, then the two offset-0 memos
+// Survivor row.  Lean form: the forward words and the two offset-0 memos; the later phase rebuilds the reverse-complement words in
+// the lane's LDS column (k4d_revcomp_words).  Full form: the reverse-complement words travel too.  The form is a constant of the
+// length class (a class whose later-phase kernel would spill more registers for the rebuild keeps the full row); rows are padded
+// to an even number of words, so that every row starts on a 16-byte boundary (the 5-word class: 8 words, one unused).
+#ifndef K4_LEAN_ROW
+#define K4_LEAN_ROW(nch) 1
+#endif
+#define K4_ROW_STRAND_WORDS(nch) (K4_LEAN_ROW(nch) ? (nch) : 2 * (nch))
+#define K4_ROW_WORDS(nch) ((K4_ROW_STRAND_WORDS(nch) + 2 + 1) & ~1)
+// A survivor's id slot is 8 bytes: {read id, read length}.  The length rides here because the memo words have no room for it
+// (k4d_memo_pack, k4_align.hip: kind 2 bits, fm 14 bits of which a length of up to 512 leaves bits 58..61 unused, mm 8 bits, pos
+// 40 bits -- four spare bits a word where ten are needed), and it spares the later phases the gather of lens[id].  A hole is
+// {K4_NO_READ, 0}.  (The deferred list of a split first launch stays a list of 4-byte ids.)
+struct __attribute__((aligned(8))) K4Survivor { uint32_t id, len; };
+#define K4_TILE_GROUPS 4     // 64-slot groups a wave takes per claim (tile = 256 slots: one atomic per 256 reads, ~30 / us on C2)
+#define K4_MAX_STEPS 64      // phases of AlignReads: the escalation 0..TotMM (TotMM <= 63), or fewer plus the final one
 #ifndef K4_PF
 #define K4_PF 4  // k-mer table entries fetched ahead per strand pass
 #endif
@@ -61,7 +77,9 @@
 #define K4_HUGE_WAVES 256
 #define K4_CTL_HUGE 68  // ctl[68] huge count, ctl[69] huge head
 #define K4_CTL_DEFER 70  // ctl[70] slots handed out in the deferred list of the first launch
-#define K4_CTL_WORDS 72  // [0] slow count, [1] slow head, [2+t] survivors of step t
+#define K4_CTL_CLAIM_DEFER 71  // ctl[71] tiles claimed in the second launch of a split first phase (the one over the deferred list)
+#define K4_CTL_CLAIM 72  // ctl[72+t] tiles claimed in the launch of step t (of a split first phase: its first launch)
+#define K4_CTL_WORDS (K4_CTL_CLAIM + K4_MAX_STEPS)  // [0] slow count, [1] slow head, [2+t] survivors of step t
 
 struct K4AlignArgs {
   K4DevIndex ix;

@@ -65,13 +65,14 @@ struct K4Workspace {
   int64_t cap_reads = 0;
   int32_t cap_len = 0;
   int32_t cap_hits = 0;
-  K4DevBuf ids[2];       // survivors of a step: read ids (u32) ...
-  K4DevBuf rows[2];      // ... and their packed rows (u64: forward + reverse-complement words)
+  K4DevBuf ids[2];       // survivors of a step: {read id, read length} (K4Survivor, 8 bytes; ids[1] also the deferred list's u32 ids) ...
+  K4DevBuf rows[2];      // ... and their packed rows (u64, K4_ROW_WORDS a row: forward words and the two offset-0 memos)
   K4DevBuf slow_list;    // read ids (u32) for the general kernel
   K4DevBuf slow_step;    // and the phase ordinal (u8) at which each left the fast path
   K4DevBuf huge_list;    // reads that outgrew the small dedupe tables of the first general pass
   K4DevBuf huge_step;
-  K4DevBuf ctl;          // u32: [0] slow count, [1] slow head, [2+t] survivor count of step t
+  K4DevBuf ctl;          // u32, K4_CTL_WORDS (k4_align_common.h): [0] slow count, [1] slow head, [2+t] survivor count of step t,
+                         // [68] [69] huge count / head, [70] deferred slots, [71] [72+t] tiles claimed in a launch
   K4DevBuf slow_hash;    // u64, per slow lane: open-addressing table of (generation<<32 | TargSeqID)
   uint32_t slow_hash_cap = 0;    // entries per lane (power of two)
   // staging for the host-pointer entry points

@@ -344,7 +344,7 @@ __global__ void __launch_bounds__(64) k4k_blitz_path(K4BlitzArgs a, const uint32
       else x++;
     }
   }
-  for (int d = 32; d > 0; d >>= 1) { m += __shfl_xor(m, d, 64); x += __shfl_xor(x, d, 64); nn += __shfl_xor(nn, d, 64); }
+  m = k4d_wave_sum(m); x = k4d_wave_sum(x); nn = k4d_wave_sum(nn);
   if (lane == 0) {
     o.matches = m; o.mismatches = x; o.n_count = nn;
     const uint64_t at = path_offs[q] + r;
@@ -489,8 +489,7 @@ extern "C" int k4_blitz_paths_batch_dev(k4_index* ix, const k4_blitz_params* p, 
     K4_HIP(ix, hipGetLastError());
   }
   K4_HIP(ix, b.timer.end(st));
-  K4_HIP(ix, hipStreamSynchronize(st));
-  K4_HIP(ix, b.timer.read());
+  K4_TRY(k4s_call_close(ix, st, b.timer));
   if (!fits)
     return k4_fail(ix, K4_ERR_MEM, "blitz paths: %llu paths and %llu blocks found, paths_cap is %llu and blocks_cap %llu", (unsigned long long)n_paths,
                    (unsigned long long)n_blocks, (unsigned long long)paths_cap, (unsigned long long)blocks_cap);
@@ -507,10 +506,10 @@ extern "C" int k4_blitz_paths_batch(k4_index* ix, const k4_blitz_params* p, int6
   if (n < 0 || !node_offs || !path_offs || !needed || (n > 0 && (!seqs || !offs || !lens)) || (node_offs[n] > 0 && !nodes) ||
       (paths_cap > 0 && !paths) || (blocks_cap > 0 && !blocks))
     return k4_fail(ix, K4_ERR_PARAMS, "blitz paths: null argument");
-  K4_HIP(ix, hipSetDevice(ix->device));
   K4SeqStage& s = ix->seq_stage;
   const uint64_t total = node_offs[n];
-  hipStream_t st = ix->stream;
+  hipStream_t st;
+  K4_TRY(k4s_call_open(ix, &st));
   K4_TRY(k4s_stage_seqs(ix, n, seqs, offs, lens, nullptr));
   K4_HIP(ix, s.node_offs.reserve((size_t)(n + 1) * 8));
   K4_HIP(ix, s.nodes.reserve((size_t)std::max<uint64_t>(total, 1) * sizeof(k4_query_node)));
@@ -525,8 +524,7 @@ extern "C" int k4_blitz_paths_batch(k4_index* ix, const k4_blitz_params* p, int6
   K4_HIP(ix, hipMemcpyAsync(path_offs, b.out_offs.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
   if (needed[0]) K4_HIP(ix, hipMemcpyAsync(paths, b.out_paths.p, (size_t)needed[0] * sizeof(k4_blitz_path), hipMemcpyDeviceToHost, st));
   if (needed[1]) K4_HIP(ix, hipMemcpyAsync(blocks, b.out_blocks.p, (size_t)needed[1] * sizeof(k4_blitz_block), hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
-  return K4_OK;
+  return k4s_call_close(ix, st, b.timer);
 }
 
 extern "C" double k4_blitz_last_kernel_ms(const k4_index* ix) { return ix ? ix->blz.timer.ms : 0.0; }

@@ -128,10 +128,6 @@ K4_DEV void k4c_hist_zero(uint32_t* p) {
   else __hip_atomic_store(p, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 K4_DEV uint32_t k4c_saturate(uint64_t v) { return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v; }
-K4_DEV uint64_t k4c_wave_sum(uint64_t v) {
-  for (int d = 32; d > 0; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
-  return v;
-}
 
 // One wave per segment.  hist[2 e] / hist[2 e + 1] = sense / antisense counts of entry e: all zero between segments.
 template <int EL, bool LDSH>
@@ -172,8 +168,8 @@ __global__ void __launch_bounds__(64) k4k_cult_segments(K4CultSegArgs a) {
         if (head == K4C_NONE) head = i;
       }
     }
-    n_f = k4c_wave_sum(n_f);
-    for (int d = 32; d > 0; d >>= 1) head = min(head, (uint64_t)__shfl_xor((unsigned long long)head, d, 64));
+    n_f = k4d_wave_sum(n_f);
+    head = k4d_wave_min(head);
     if (n_f == 0) continue;  // (nothing located; the count pass's answers were zeroed by the host)
     const uint64_t head_psn = k4d_sa_at<EL>(a.ix, head);
     // 2. the antisense side (AntisenseKMerCultsCnts): every occurrence of the prefix's reverse complement, kept when S ACGT bases follow
@@ -188,18 +184,16 @@ __global__ void __launch_bounds__(64) k4k_cult_segments(K4CultSegArgs a) {
       if (lane == 0) cnt = k4q_count<EL>(a.ix, tb, qs, 0u, (int)a.P, 0xFFFFFFFFu, first);
       first = (uint64_t)__shfl((unsigned long long)first, 0, 64);
       cnt = __shfl(cnt, 0, 64);
-      for (uint64_t c0 = 0; c0 < cnt; c0 += 64) {
-        const uint64_t c = c0 + (uint64_t)lane;
-        if (c >= cnt) continue;
-        const uint64_t pos = k4d_sa_at<EL>(a.ix, first + c);
-        if (a.S > 0 && !k4c_all_acgt(a.ix, tb, pos + a.P, a.S)) continue;
+      k4d_run_walk<EL>(a.ix, lane, first, cnt, [&](uint32_t, uint64_t pos, bool active) {
+        if (!active || (a.S > 0 && !k4c_all_acgt(a.ix, tb, pos + a.P, a.S))) return false;
         uint64_t es, ee;
         const int en = k4d_map_entry_slow(a.ix, ent_lds, pos, es, ee);
-        if (en < 0) continue;
+        if (en < 0) return false;
         atomicAdd(&hist[2u * (uint32_t)en + 1u], 1u);
         n_a++;
-      }
-      n_a = k4c_wave_sum(n_a);
+        return false;
+      });
+      n_a = k4d_wave_sum(n_a);
     }
     __threadfence();
     __syncthreads();
@@ -250,6 +244,10 @@ __global__ void __launch_bounds__(64) k4k_cult_segments(K4CultSegArgs a) {
   }
 }
 
+// (K4S_LAUNCH_EL names a kernel by its element size alone)
+template <int EL> constexpr auto k4c_segments_lds = &k4k_cult_segments<EL, true>;
+template <int EL> constexpr auto k4c_segments_global = &k4k_cult_segments<EL, false>;
+
 struct K4CultIsStart {
   const uint8_t* flags;
   __device__ bool operator()(uint32_t i) const { return (flags[i] & 1u) != 0; }
@@ -289,16 +287,12 @@ struct CultRun {
   K4CultState& c;
   hipStream_t st;
   uint32_t P, S, K, W;
-  double ms = 0;
 
   int begin() { return k4_check_hip(ix, c.timer.begin(st), "hipEventRecord"); }
   // the stream waited for, the section's device time added
   int lap() {
     K4_HIP(ix, c.timer.end(st));
-    K4_HIP(ix, hipStreamSynchronize(st));
-    K4_HIP(ix, c.timer.read());
-    ms += c.timer.ms;
-    return K4_OK;
+    return k4s_call_close(ix, st, c.timer);
   }
   int reserve() {
     const size_t w = W;
@@ -322,8 +316,7 @@ struct CultRun {
     a.flags = c.flags.as<uint8_t>(); a.ent = c.ent.as<uint32_t>();
     const size_t n = (size_t)(w1 - w0);
     K4_TRY(begin());
-    if (ix->d.el == 4) hipLaunchKernelGGL(k4k_cult_flags<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k4k_cult_flags<5>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    K4S_LAUNCH_EL(ix, k4k_cult_flags, (unsigned)((n + 255) / 256), 256, st, a);
     K4_HIP(ix, hipGetLastError());
     uint32_t* out = c.starts.as<uint32_t>();
     uint64_t* d_m = c.count.as<uint64_t>();
@@ -337,13 +330,8 @@ struct CultRun {
   void launch(const K4CultSegArgs& a) {
     const bool lds = ix->d.n_entries <= K4C_LDS_ENTRIES;
     const unsigned grid = (unsigned)std::min<uint64_t>(a.n_seg, lds ? K4C_LDS_BLOCKS : K4C_GLOBAL_BLOCKS);
-    if (ix->d.el == 4) {
-      if (lds) hipLaunchKernelGGL((k4k_cult_segments<4, true>), dim3(grid), dim3(64), 0, st, a);
-      else hipLaunchKernelGGL((k4k_cult_segments<4, false>), dim3(grid), dim3(64), 0, st, a);
-    } else {
-      if (lds) hipLaunchKernelGGL((k4k_cult_segments<5, true>), dim3(grid), dim3(64), 0, st, a);
-      else hipLaunchKernelGGL((k4k_cult_segments<5, false>), dim3(grid), dim3(64), 0, st, a);
-    }
+    if (lds) K4S_LAUNCH_EL(ix, k4c_segments_lds, grid, 64, st, a);
+    else K4S_LAUNCH_EL(ix, k4c_segments_global, grid, 64, st, a);
   }
 };
 }  // namespace
@@ -452,13 +440,12 @@ static int cults_run(k4_index* ix, const k4_cults_params* p, int64_t start, int6
   }
   tot->next_sfx_idx = cur;
   tot->done = cur > last ? 1 : 0;
-  c.ms = r.ms;
   return K4_OK;
 }
 
 extern "C" int k4_kmer_cults_batch_dev(k4_index* ix, const k4_cults_params* p, int64_t start_sfx_idx, int64_t end_sfx_idx, const k4_cults_out* d_out,
                                        const k4_cults_caps* caps, k4_cults_totals* totals, void* stream) {
-  if (ix) { ix->cul.timer.reset(); ix->cul.ms = 0; }
+  if (ix) ix->cul.timer.reset();
   const int rc = check_cults_args(ix, p, start_sfx_idx, end_sfx_idx, d_out, caps, totals);
   return rc != K4_OK ? rc : cults_run(ix, p, start_sfx_idx, end_sfx_idx, d_out, caps, totals, (hipStream_t)stream);
 }
@@ -466,30 +453,29 @@ extern "C" int k4_kmer_cults_batch_dev(k4_index* ix, const k4_cults_params* p, i
 // host outputs: the records are staged on the device in room for the caps, and what was written comes back; nothing else is touched
 extern "C" int k4_kmer_cults_batch(k4_index* ix, const k4_cults_params* p, int64_t start_sfx_idx, int64_t end_sfx_idx, const k4_cults_out* out,
                                    const k4_cults_caps* caps, k4_cults_totals* totals) {
-  if (ix) { ix->cul.timer.reset(); ix->cul.ms = 0; }
+  if (ix) ix->cul.timer.reset();
   int rc = check_cults_args(ix, p, start_sfx_idx, end_sfx_idx, out, caps, totals);
   if (rc != K4_OK) return rc;
   K4CultState& c = ix->cul;
   const k4_cults_caps room = cults_room(ix, caps);
   const size_t klen = (size_t)(p->prefix_len + p->suffix_len);
-  K4_HIP(ix, hipSetDevice(ix->device));
-  K4_HIP(ix, hipStreamSynchronize(ix->stream));
+  hipStream_t st;
+  K4_TRY(k4s_call_open(ix, &st));
   K4_HIP(ix, c.out_kmers.reserve((size_t)room.max_kmers * sizeof(k4_cult_kmer) + 16));
   K4_HIP(ix, c.out_bases.reserve((size_t)room.max_kmers * klen + 16));
   K4_HIP(ix, c.out_dist.reserve((size_t)room.max_dist * sizeof(k4_cult_dist) + 16));
   k4_cults_out d;
   d.kmers = c.out_kmers.as<k4_cult_kmer>(); d.bases = c.out_bases.as<uint8_t>(); d.dist = c.out_dist.as<k4_cult_dist>();
-  if ((rc = cults_run(ix, p, start_sfx_idx, end_sfx_idx, &d, caps, totals, ix->stream)) != K4_OK) return rc;
+  if ((rc = cults_run(ix, p, start_sfx_idx, end_sfx_idx, &d, caps, totals, st)) != K4_OK) return rc;
   if (totals->n_kmers) {
-    K4_HIP(ix, hipMemcpyAsync(out->kmers, d.kmers, (size_t)totals->n_kmers * sizeof(k4_cult_kmer), hipMemcpyDeviceToHost, ix->stream));
-    K4_HIP(ix, hipMemcpyAsync(out->bases, d.bases, (size_t)totals->n_kmers * klen, hipMemcpyDeviceToHost, ix->stream));
-    K4_HIP(ix, hipMemcpyAsync(out->dist, d.dist, (size_t)totals->n_dist * sizeof(k4_cult_dist), hipMemcpyDeviceToHost, ix->stream));
+    K4_HIP(ix, hipMemcpyAsync(out->kmers, d.kmers, (size_t)totals->n_kmers * sizeof(k4_cult_kmer), hipMemcpyDeviceToHost, st));
+    K4_HIP(ix, hipMemcpyAsync(out->bases, d.bases, (size_t)totals->n_kmers * klen, hipMemcpyDeviceToHost, st));
+    K4_HIP(ix, hipMemcpyAsync(out->dist, d.dist, (size_t)totals->n_dist * sizeof(k4_cult_dist), hipMemcpyDeviceToHost, st));
   }
-  K4_HIP(ix, hipStreamSynchronize(ix->stream));
-  return K4_OK;
+  return k4s_call_close(ix, st, c.timer);
 }
 
-extern "C" double k4_cults_last_kernel_ms(const k4_index* ix) { return ix ? ix->cul.ms : 0.0; }
+extern "C" double k4_cults_last_kernel_ms(const k4_index* ix) { return ix ? ix->cul.timer.ms : 0.0; }
 
 // SfxOfsToLoci (SfxArray.cpp:49-60) for n elements from `first`
 extern "C" int k4_get_sfx_els(k4_index* ix, uint64_t first, uint64_t n, uint64_t* els) {

@@ -9,7 +9,7 @@
 #include <fstream>
 #include <iterator>
 #include <thread>
-#include "k4_sfxarray.hpp"
+#include "k4_facade_test_util.h"
 
 static const int P = 12, S = 6;
 
@@ -48,7 +48,7 @@ int main(int argc, char** argv) {
   if (argc != 7) return 2;
   const int min_cult = atoi(argv[5]);
   CSfxArray sfx;
-  if (sfx.Open(argv[1]) != 0 || sfx.SetTargBlock(1) < 0) { fprintf(stderr, "open failed\n"); return 1; }
+  if (K4FtOpen(&sfx, argv[1]) != 0) { fprintf(stderr, "open failed\n"); return 1; }
   const bool rest = std::string(argv[4]) != "-";
   const std::vector<uint8_t> want = slurp(argv[2]), want_abort = rest ? slurp(argv[4]) : std::vector<uint8_t>();
   const long long want_located = atoll(argv[3]);

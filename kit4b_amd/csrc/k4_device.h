@@ -1,6 +1,7 @@
 // kit4b_amd/csrc/k4_device.h -- device-side accessors of the HBM index (gfx950 only).
 #pragma once
 #include "k4_internal.h"
+#include "k4_search_arith.h"
 
 #define K4_DEV __device__ __forceinline__
 
@@ -321,16 +322,64 @@ K4_DEV void k4d_runs_layout(int lane, uint64_t first, uint32_t take, uint64_t* g
   g_pre[lane] = x - take;
   if (lane == 63) g_pre[64] = x;
 }
-// candidate g (below the total) is occurrence occ of run item, the last run in 0 .. hi whose candidates start at or before g; any
-// hi at or behind the last run that has a candidate gives the same answer, the entries behind that run holding the total
-K4_DEV void k4d_runs_locate(uint32_t g, uint32_t hi, const uint32_t* g_pre, uint32_t& item, uint32_t& occ) {
-  uint32_t lo = 0;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (g_pre[mid] <= g) lo = mid; else hi = mid - 1;
+// (k4d_runs_locate, k4_search_arith.h, finds the run and the occurrence of candidate g in g_pre)
+
+// ---- what the waves of the search-call families do alike (DESIGN.md "Search-call families: shared scaffold") ----------------------
+// the sum / the minimum of x over the 64 lanes, in every lane
+K4_DEV uint32_t k4d_wave_sum(uint32_t x) {
+  for (int d = 32; d > 0; d >>= 1) x += (uint32_t)__shfl_xor(x, d, 64);
+  return x;
+}
+K4_DEV uint64_t k4d_wave_sum(uint64_t x) {
+  for (int d = 32; d > 0; d >>= 1) x += (uint64_t)__shfl_xor((unsigned long long)x, d, 64);
+  return x;
+}
+K4_DEV uint32_t k4d_wave_min(uint32_t x) {
+  for (int d = 32; d > 0; d >>= 1) x = min(x, (uint32_t)__shfl_xor(x, d, 64));
+  return x;
+}
+K4_DEV uint64_t k4d_wave_min(uint64_t x) {
+  for (int d = 32; d > 0; d >>= 1) x = min(x, (uint64_t)__shfl_xor((unsigned long long)x, d, 64));
+  return x;
+}
+
+// The tail of a tally kernel: each of a lane's N counters summed over its wave, one atomicAdd per wave and counter that has something
+template <int N>
+K4_DEV void k4d_tally_flush(const uint32_t (&c)[N], unsigned long long* tot) {
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    const uint32_t x = k4d_wave_sum(c[k]);
+    if ((threadIdx.x & 63) == 0 && x) atomicAdd(&tot[k], (unsigned long long)x);
   }
-  item = lo;
-  occ = g - g_pre[lo];
+}
+
+// One core per lane, for a wave that holds the cores of one or two strands: lane i < n_items (n_items <= 2 n_core) resolves core
+// i - s n_core of strand s = (i >= n_core) through k4q_count, on the sequence qs_of(s) at offset ofs_of(core); the run's length
+// comes back (0 in the lanes behind n_items), its first suffix-array index in first.  The lanes' answers are then handed round by
+// __shfl, run after run (k4d_run_walk).
+template <int EL, typename QsOf, typename OfsOf>
+K4_DEV uint32_t k4d_cores_to_lanes(const K4DevIndex& ix, K4Tb& tb, int lane, uint32_t n_items, uint32_t n_core, uint32_t core_len, uint32_t max_iter,
+                                   QsOf qs_of, OfsOf ofs_of, uint64_t& first) {
+  first = 0;
+  if ((uint32_t)lane >= n_items) return 0u;
+  const uint32_t s = (uint32_t)lane >= n_core ? 1u : 0u;
+  const K4QSeq qs = qs_of(s);
+  return k4q_count<EL>(ix, tb, qs, ofs_of((uint32_t)lane - s * n_core), (int)core_len, max_iter, first);
+}
+
+// The run [first, first + cnt) of the suffix array walked by the whole wave, 64 suffixes a turn: every lane calls
+// body(i, pos, active) for its occurrence i of the turn -- active = i < cnt, and then pos = the suffix's concatenation offset --
+// and the walk ends behind the first turn in which a lane's body returns true.  Returns whether one did.  The body may hold
+// barriers and shuffles: all 64 lanes run it in every turn.  The turn's first occurrence is i - lane.
+template <int EL, typename Body>
+K4_DEV bool k4d_run_walk(const K4DevIndex& ix, int lane, uint64_t first, uint32_t cnt, Body body) {
+  for (uint32_t c0 = 0; c0 < cnt; c0 += 64) {
+    const uint32_t i = c0 + (uint32_t)lane;
+    const bool active = i < cnt;
+    const uint64_t pos = active ? k4d_sa_at<EL>(ix, first + i) : 0;
+    if (__ballot(body(i, pos, active))) return true;
+  }
+  return false;
 }
 
 // mask of the bases [lo, hi) of a 32-base MSB-first chunk (0 <= lo, hi <= 32)

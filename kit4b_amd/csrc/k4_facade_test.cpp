@@ -4,17 +4,13 @@
 #include <cstdio>
 #include <thread>
 #include <vector>
-#include "k4_sfxarray.hpp"
+#include "k4_facade_test_util.h"
 
 int main(int argc, char** argv) {
   if (argc < 2) return 1;
   CSfxArray* pSfx = new CSfxArray;
-  int Rslt = pSfx->Open(argv[1]);
-  if (Rslt < 0) {
-    while (pSfx->NumErrMsgs()) fprintf(stderr, "%s\n", pSfx->GetErrMsg());
-    return 2;
-  }
-  if (pSfx->SetTargBlock(1) < 0) return 3;
+  int Rslt = K4FtOpen(pSfx, argv[1]);
+  if (Rslt) return Rslt;
   pSfx->SetMaxIter(5000);
   pSfx->InitialiseCoreKMers(8);
   printf("entries %d totlen %llu dataset %s\n", pSfx->GetNumEntries(), (unsigned long long)pSfx->GetTotSeqsLen(),

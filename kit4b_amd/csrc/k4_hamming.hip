@@ -74,27 +74,19 @@ K4_DEV uint32_t k4h_locate(const K4DevIndex& ix, K4Tb& tb, const uint8_t* pb, ui
   qs.q = pb; qs.len = len;
   if (hmin == 0) {  // :4411-4452: IterateExacts on the whole K-mer, sense then antisense
     const int ns = both ? 2 : 1;
-    uint64_t first = 0;
-    uint32_t cnt = 0;
-    if (lane < ns) {
-      qs.s = lane;
-      cnt = k4q_count<EL>(ix, tb, qs, 0u, (int)len, 0xFFFFFFFFu, first);
-    }
+    uint64_t first;
+    const uint32_t cnt = k4d_cores_to_lanes<EL>(
+        ix, tb, lane, (uint32_t)ns, 1u, len, 0xFFFFFFFFu, [&](uint32_t s) { return K4QSeq{pb, len, (int)s}; }, [](uint32_t) { return 0u; }, first);
     for (int s = 0; s < ns; s++) {
-      const uint64_t f = __shfl(first, s, 64);
       const uint32_t c = __shfl(cnt, s, 64);
       const bool filtered = s == 0 ? probe_entry != 0 : (probe_entry != 0 && iib != 0);
       if (c && !filtered) return 0u;
-      for (uint32_t c0 = 0; c0 < c; c0 += 64) {
-        bool ok = false;
-        if (c0 + (uint32_t)lane < c) {
-          const uint64_t pos = k4d_sa_at<EL>(ix, f + c0 + (uint32_t)lane);
-          const int e = k4d_map_entry(ix, pos);
-          // (the antisense run holds no self hit)
-          ok = e >= 0 && !k4h_filtered(ix.ent_id[e], (uint32_t)(pos - ix.ent_start[e]), probe_entry, probe_loci, iib, s == 0);
-        }
-        if (__ballot(ok)) return 0u;
-      }
+      const bool kept = k4d_run_walk<EL>(ix, lane, __shfl(first, s, 64), c, [&](uint32_t, uint64_t pos, bool active) {
+        const int e = active ? k4d_map_entry(ix, pos) : -1;
+        // (the antisense run holds no self hit)
+        return e >= 0 && !k4h_filtered(ix.ent_id[e], (uint32_t)(pos - ix.ent_start[e]), probe_entry, probe_loci, iib, s == 0);
+      });
+      if (kept) return 0u;
     }
   }
   if (hmax == 0) return 1u;
@@ -106,13 +98,11 @@ K4_DEV uint32_t k4h_locate(const K4DevIndex& ix, K4Tb& tb, const uint8_t* pb, ui
     // 1. one segment per lane: first index of its run and the occurrences the reference's walk reaches.  The walk takes at most
     // max_cd of them; on its min_cd-th turn it counts the run once and gives the segment up when what is left, as it counts it
     // (run + 3 - min_cd), exceeds max_cd (:4487-4494)
-    uint64_t first = 0;
-    uint32_t take = 0;
-    if ((uint32_t)lane < n_seg && max_cd > 0) {
-      const uint32_t run = k4q_count<EL>(ix, tb, qs, (uint32_t)lane * core_len, (int)core_len, cap, first);
-      take = min(run, max_cd);
-      if (min_cd >= 2 && min_cd <= max_cd && (uint64_t)run + 1 >= min_cd && (uint64_t)run + 3 > (uint64_t)max_cd + min_cd) take = min_cd - 1;
-    }
+    uint64_t first;
+    const uint32_t run = k4d_cores_to_lanes<EL>(
+        ix, tb, lane, max_cd > 0 ? n_seg : 0u, n_seg, core_len, cap, [&](uint32_t) { return qs; }, [&](uint32_t seg) { return seg * core_len; }, first);
+    uint32_t take = min(run, max_cd);
+    if (min_cd >= 2 && min_cd <= max_cd && (uint64_t)run + 1 >= min_cd && (uint64_t)run + 3 > (uint64_t)max_cd + min_cd) take = min_cd - 1;
     __syncthreads();  // (the previous pass has done with g_first / g_pre)
     k4d_runs_layout(lane, first, take, g_first, g_pre);
     __syncthreads();
@@ -130,9 +120,7 @@ K4_DEV uint32_t k4h_locate(const K4DevIndex& ix, K4Tb& tb, const uint8_t* pb, ui
       // 3. in order: the first candidate at or under hmin ends the stage (nothing in front of it was), else the minimum stands
       const unsigned long long stop = __ballot(mm != K4H_SKIP && mm <= hmin);
       if (stop) return __shfl(mm, __ffsll((long long)stop) - 1, 64);
-      uint32_t m = mm;
-      for (int d = 32; d > 0; d >>= 1) m = min(m, (uint32_t)__shfl_xor(m, d, 64));
-      cur = min(cur, m);
+      cur = min(cur, k4d_wave_min(mm));
     }
     probe_entry = 0;  // :4617: the antisense pass knows no self hit
   }
@@ -148,12 +136,7 @@ __global__ void __launch_bounds__(64) k4k_hammings(K4HammArgs a) {
   const int lane = threadIdx.x;
   const uint64_t kid = a.k0 + blockIdx.x;
   if (kid >= a.k1) return;
-  int64_t lo = 0, hi = a.n_spans - 1;  // the last span whose K-mers start at or before kid
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (a.spans[mid].kbase <= kid) lo = mid; else hi = mid - 1;
-  }
-  const K4HSpan sp = a.spans[lo];
+  const K4HSpan sp = a.spans[k4d_last_le(a.n_spans, kid, [&](int64_t i) { return a.spans[i].kbase; })];  // the span that holds K-mer kid
   const k4_hamming_params p = a.p;
   const uint32_t len = (uint32_t)p.kmer_len, nth = (uint32_t)p.sample_nth;
   const uint32_t ofs = (uint32_t)(kid - sp.kbase) * nth;
@@ -265,7 +248,6 @@ static int hamming_batch(k4_index* ix, const k4_hamming_params* p, bool sfx, boo
   h.timer.reset();
   const bool src = sfx ? n == 0 || (entry_ids && entry_locis) : seqs && (n == 0 || offs);
   if (n < 0 || !hammings || !src || (n > 0 && (!lens || !out_offs))) return k4_fail(ix, K4_ERR_INTERNAL, "Hammings: null argument");
-  K4_HIP(ix, hipSetDevice(ix->device));
   std::vector<K4HSpan> t;
   if ((rc = hamming_spans(ix, p, n, entry_ids, entry_locis, lens, offs, out_offs, hammings_len, t)) != K4_OK) return rc;
   const uint64_t total = t[(size_t)n].kbase;
@@ -273,16 +255,17 @@ static int hamming_batch(k4_index* ix, const k4_hamming_params* p, bool sfx, boo
   K4HammArgs a;
   a.seqs = (const uint8_t*)seqs;  // (null: the sfx form)
   a.out = (uint8_t*)hammings;
-  if (on_host) {
-    st = ix->stream;
-    K4_HIP(ix, hipStreamSynchronize(st));  // (the staging about to be replaced may still be read by the batch before)
+  if (!on_host) {
+    K4_HIP(ix, hipSetDevice(ix->device));
+    K4_HIP(ix, hipStreamSynchronize(st));  // (the span table about to be replaced may still be read by the batch before)
+  } else {
+    K4_TRY(k4s_call_open(ix, &st));
     K4_HIP(ix, h.out.reserve((size_t)hammings_len + 16));
     K4_HIP(ix, hipMemcpyAsync(h.out.p, hammings, (size_t)hammings_len, hipMemcpyHostToDevice, st));
     if (!sfx) K4_TRY(k4s_stage_seqs(ix, n, (const uint8_t*)seqs, offs, lens, nullptr));
     a.seqs = sfx ? nullptr : ix->seq_stage.seqs.as<uint8_t>();
     a.out = h.out.as<uint8_t>();
   }
-  K4_HIP(ix, hipStreamSynchronize(st));  // (a table about to be replaced may still be read by the batch before)
   K4_HIP(ix, h.spans.reserve(t.size() * sizeof(K4HSpan)));
   K4_HIP(ix, hipMemcpyAsync(h.spans.p, t.data(), t.size() * sizeof(K4HSpan), hipMemcpyHostToDevice, st));
   a.ix = ix->d;
@@ -291,18 +274,15 @@ static int hamming_batch(k4_index* ix, const k4_hamming_params* p, bool sfx, boo
   a.p = *p;
   if (a.p.sample_nth <= 0) a.p.sample_nth = 1;
   K4_HIP(ix, h.timer.begin(st));
-  for (uint64_t k0 = 0; k0 < total; k0 += K4H_LAUNCH_KMERS) {
+  k4s_launch_windows(total, K4H_LAUNCH_KMERS, [&](uint64_t k0, uint64_t k1) {
     a.k0 = k0;
-    a.k1 = std::min<uint64_t>(total, k0 + K4H_LAUNCH_KMERS);
-    if (ix->d.el == 4) hipLaunchKernelGGL(k4k_hammings<4>, dim3((unsigned)(a.k1 - a.k0)), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k4k_hammings<5>, dim3((unsigned)(a.k1 - a.k0)), dim3(64), 0, st, a);
-  }
+    a.k1 = k1;
+    K4S_LAUNCH_EL(ix, k4k_hammings, (unsigned)(k1 - k0), 64, st, a);
+  });
   K4_HIP(ix, hipGetLastError());
   K4_HIP(ix, h.timer.end(st));
   if (on_host) K4_HIP(ix, hipMemcpyAsync(hammings, h.out.p, (size_t)hammings_len, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
-  K4_HIP(ix, h.timer.read());
-  return K4_OK;
+  return k4s_call_close(ix, st, h.timer);
 }
 
 extern "C" int k4_locate_sfx_hammings_batch_dev(k4_index* ix, const k4_hamming_params* p, int64_t n, const uint32_t* entry_ids,

@@ -9,7 +9,7 @@
 #include <cstring>
 #include <thread>
 #include <vector>
-#include "k4_sfxarray.hpp"
+#include "k4_facade_test_util.h"
 
 struct Case {
   int form, rhamm, both, klen, nth, iib;
@@ -34,22 +34,14 @@ static int RunCase(CSfxArray* pSfx, const Case& c) {
 int main(int argc, char** argv) {
   if (argc < 3) return 1;
   CSfxArray* pSfx = new CSfxArray;
-  if (pSfx->Open(argv[1]) < 0) {
-    while (pSfx->NumErrMsgs()) fprintf(stderr, "%s\n", pSfx->GetErrMsg());
-    return 2;
-  }
-  if (pSfx->SetTargBlock(1) < 0) return 3;
+  if (const int rc = K4FtOpen(pSfx, argv[1])) return rc;
   FILE* f = fopen(argv[2], "r");
   if (!f) return 4;
   std::vector<Case> Cases;
   for (;;) {
     Case c;
     if (fscanf(f, "%d %d %d %d %d %u %u %d %u %u %u", &c.form, &c.rhamm, &c.both, &c.klen, &c.nth, &c.mn, &c.mx, &c.iib, &c.entry, &c.loci, &c.len) != 11) break;
-    if (c.form == 1) {
-      std::vector<char> s(c.len + 2);
-      if (fscanf(f, "%s", s.data()) != 1) return 5;
-      for (uint32_t j = 0; j < c.len; j++) c.seq.push_back((etSeqBase)(s[j] - '0'));
-    }
+    if (c.form == 1 && !K4FtReadProbe(f, c.len, c.seq)) return 5;
     for (uint32_t k = 0; k < c.len; k++) {
       unsigned v;
       if (fscanf(f, "%u", &v) != 1) return 5;

@@ -89,8 +89,8 @@ struct K4Workspace {
   int32_t* c_out = nullptr; k4_hit* c_hits = nullptr; bool c_small = false;
 };
 
-// The sequence batch of a host-pointer search call on the device (k4s_stage_seqs, k4_stage.h), grow-only: LocateQuerySeqs, blitz's
-// path stage and LocateHammings put their sequences here, the first two also the node table that goes from one to the other
+// The sequence batch of a host-pointer search call on the device (k4s_stage_seqs, k4_stage.h), grow-only: every family whose call
+// takes sequences puts them here, LocateQuerySeqs and blitz's path stage also the node table that goes from one to the other
 struct K4SeqStage { K4DevBuf seqs, offs, lens, node_offs, nodes; };
 // LocateQuerySeqs (k4_query.hip), grow-only: per-query node slices and counts (cap_queries x cap_slice slots; the counts end with
 // the zero the offsets' scan reads), the scan's temporary
@@ -118,8 +118,7 @@ struct K4CultState {
   K4DevBuf flags, ent, starts, count, loc, rep, nnz, loc_pre, rep_pre, dist_pre, hist;
   K4DevBuf out_kmers, out_bases, out_dist;
   K4Scratch<K4DevBuf> scan;
-  K4Timer timer;
-  double ms = 0;  // the sections of the last call, summed
+  K4Timer timer;  // (a section per window pass: the call reports their sum)
 };
 
 // kmarkers (k4_kmarkers.hip), grow-only: the rank of every entry in the target list, the outputs of the host-pointer entry points

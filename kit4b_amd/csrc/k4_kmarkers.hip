@@ -47,31 +47,21 @@ K4_DEV bool k4m_matches_others(const K4DevIndex& ix, K4Tb& tb, const uint8_t* pb
                                int n_strands, const uint8_t* rank) {
   const int lane = threadIdx.x;
   const uint32_t n_items = n_core * (uint32_t)n_strands;
-  K4QSeq qs;
-  qs.q = pb; qs.len = len; qs.s = 0;
-  uint64_t first = 0;
-  uint32_t cnt = 0;
-  if ((uint32_t)lane < n_items) {
-    qs.s = (uint32_t)lane >= n_core ? 1 : 0;
-    cnt = k4q_count<EL>(ix, tb, qs, ((uint32_t)lane % n_core) * core_len, (int)core_len, 0xFFFFFFFFu, first);
-  }
+  uint64_t first;
+  const uint32_t cnt = k4d_cores_to_lanes<EL>(
+      ix, tb, lane, n_items, n_core, core_len, 0xFFFFFFFFu, [&](uint32_t s) { return K4QSeq{pb, len, (int)s}; },
+      [&](uint32_t core) { return core * core_len; }, first);
   for (uint32_t it = 0; it < n_items; it++) {
-    const uint64_t f = __shfl(first, (int)it, 64);
-    const uint32_t c = __shfl(cnt, (int)it, 64);
     const uint32_t ofs = (it % n_core) * core_len;
-    for (uint32_t c0 = 0; c0 < c; c0 += 64) {
-      bool hit = false;
-      if (c0 + (uint32_t)lane < c) {
-        const uint64_t pos = k4d_sa_at<EL>(ix, f + c0 + (uint32_t)lane);
-        const int e = k4d_map_entry(ix, pos);
-        if (e >= 0 && rank[e] == K4M_FOREIGN) {
-          const uint32_t loci = (uint32_t)(pos - ix.ent_start[e]);
-          const uint32_t seq_len = (uint32_t)(ix.ent_end[e] - ix.ent_start[e] + 1);
-          hit = loci >= ofs && loci + len - ofs <= seq_len;  // (32-bit unsigned, as the reference computes it)
-        }
-      }
-      if (__ballot(hit)) return true;
-    }
+    const bool hit = k4d_run_walk<EL>(ix, lane, __shfl(first, (int)it, 64), __shfl(cnt, (int)it, 64), [&](uint32_t, uint64_t pos, bool active) {
+      if (!active) return false;
+      const int e = k4d_map_entry(ix, pos);
+      if (e < 0 || rank[e] != K4M_FOREIGN) return false;
+      const uint32_t loci = (uint32_t)(pos - ix.ent_start[e]);
+      const uint32_t seq_len = (uint32_t)(ix.ent_end[e] - ix.ent_start[e] + 1);
+      return loci >= ofs && loci + len - ofs <= seq_len;  // (32-bit unsigned, as the reference computes it)
+    });
+    if (hit) return true;
   }
   return false;
 }
@@ -81,17 +71,15 @@ K4_DEV bool k4m_matches_others(const K4DevIndex& ix, K4Tb& tb, const uint8_t* pb
 template <int EL>
 K4_DEV uint32_t k4m_prefix_entries(const K4DevIndex& ix, uint64_t first, uint32_t cnt, const uint8_t* rank, uint32_t* seen, uint32_t have, uint32_t want) {
   const int lane = threadIdx.x;
-  for (uint32_t c0 = 0; c0 < cnt && have < want; c0 += 64) {
-    if (c0 + (uint32_t)lane < cnt) {
-      const int e = k4d_map_entry(ix, k4d_sa_at<EL>(ix, first + c0 + (uint32_t)lane));
-      if (e >= 0 && rank[e] == K4M_FOREIGN) atomicOr(&seen[e >> 5], 1u << (e & 31));
-    }
+  if (have >= want) return have;
+  k4d_run_walk<EL>(ix, lane, first, cnt, [&](uint32_t, uint64_t pos, bool active) {
+    const int e = active ? k4d_map_entry(ix, pos) : -1;
+    if (e >= 0 && rank[e] == K4M_FOREIGN) atomicOr(&seen[e >> 5], 1u << (e & 31));
     __syncthreads();
-    uint32_t x = (uint32_t)__popc(seen[lane]);
-    for (int d = 32; d > 0; d >>= 1) x += (uint32_t)__shfl_xor(x, d, 64);
-    have = x;
+    have = k4d_wave_sum((uint32_t)__popc(seen[lane]));
     __syncthreads();
-  }
+    return have >= want;
+  });
   return have;
 }
 
@@ -102,12 +90,8 @@ __global__ void __launch_bounds__(64) k4k_species_kmers(K4MScanArgs a) {
   const int lane = threadIdx.x;
   const uint64_t pid = a.k0 + blockIdx.x;
   if (pid >= a.k1) return;
-  uint32_t lo = 0, hi = a.t.n - 1;  // the last target whose loci start at or before pid
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (a.t.pre[mid] <= pid) lo = mid; else hi = mid - 1;
-  }
-  const uint32_t ti = lo, locus = (uint32_t)(pid - a.t.pre[ti]), K = a.K;
+  const uint32_t ti = k4d_last_le(a.t.n, pid, [&](uint32_t i) { return a.t.pre[i]; });  // the target that holds start locus pid
+  const uint32_t locus = (uint32_t)(pid - a.t.pre[ti]), K = a.K;
   const uint64_t cpos = a.t.start[ti] + locus;
   const uint32_t rem = a.t.len[ti] - locus;
   K4Tb tb;
@@ -127,14 +111,10 @@ __global__ void __launch_bounds__(64) k4k_species_kmers(K4MScanArgs a) {
     return;
   }
   // 2. the runs of the K-mer (lane 0) and of its reverse complement (lane 1)
-  K4QSeq qs;
-  qs.q = pb; qs.len = K; qs.s = 0;
-  uint64_t first = 0;
-  uint32_t cnt = 0;
-  if (lane < 2) {
-    qs.s = lane;
-    cnt = k4q_count<EL>(a.ix, tb, qs, 0u, (int)K, 0xFFFFFFFFu, first);
-  }
+  const auto strand = [&](uint32_t s) { return K4QSeq{pb, K, (int)s}; };
+  const auto whole = [](uint32_t) { return 0u; };
+  uint64_t first;
+  uint32_t cnt = k4d_cores_to_lanes<EL>(a.ix, tb, lane, 2u, 1u, K, 0xFFFFFFFFu, strand, whole, first);
   const uint64_t fs = __shfl(first, 0, 64), fr = __shfl(first, 1, 64);
   const uint32_t cs = __shfl(cnt, 0, 64), cr = __shfl(cnt, 1, 64);
   // 3. :1105-1147.  The first sense hit decides between "foreign first hit" and the flags; a flag at the first hit of either strand
@@ -143,38 +123,34 @@ __global__ void __launch_bounds__(64) k4k_species_kmers(K4MScanArgs a) {
   // sense hit, and at every antisense hit but the first (PrevHitIdx = RcplHitIdx, :1134).
   const uint64_t own = ((uint64_t)ti << 32) | locus;
   uint64_t min_key = ~0ull;
-  bool foreign = false, first_foreign = false;
-  for (uint32_t c0 = 0; c0 < cs; c0 += 64) {
-    const uint32_t i = c0 + (uint32_t)lane;
-    if (i < cs) {
-      const uint64_t pos = k4d_sa_at<EL>(a.ix, fs + i);
-      const int e = k4d_map_entry(a.ix, pos);
-      const uint32_t r = e >= 0 ? a.rank[e] : K4M_FOREIGN;
-      if (r == K4M_FOREIGN) { if (i == 0) first_foreign = true; else foreign = true; }
-      else min_key = min(min_key, ((uint64_t)r << 32) | (uint32_t)(pos - a.ix.ent_start[e]));
-    }
-    if (c0 == 0 && (cs == 0 || __ballot(first_foreign))) break;
-  }
-  if (cs == 0 || __ballot(first_foreign)) {  // (cs == 0 cannot be: the K-mer stands at its own locus)
+  bool foreign = false;
+  const bool first_foreign = k4d_run_walk<EL>(a.ix, lane, fs, cs, [&](uint32_t i, uint64_t pos, bool active) {
+    if (!active) return false;
+    const int e = k4d_map_entry(a.ix, pos);
+    const uint32_t r = e >= 0 ? a.rank[e] : K4M_FOREIGN;
+    if (r != K4M_FOREIGN) min_key = min(min_key, ((uint64_t)r << 32) | (uint32_t)(pos - a.ix.ent_start[e]));
+    else if (i > 0) foreign = true;
+    return r == K4M_FOREIGN && i == 0;  // (the first hit: the walk ends in its first turn)
+  });
+  if (cs == 0 || first_foreign) {  // (cs == 0 cannot be: the K-mer stands at its own locus)
     if (lane == 0) a.status[pid] = K4M_FIRST_FOREIGN;
     return;
   }
   bool rc_first_target = false;
-  for (uint32_t c0 = 0; c0 < cr; c0 += 64) {
-    const uint32_t i = c0 + (uint32_t)lane;
+  k4d_run_walk<EL>(a.ix, lane, fr, cr, [&](uint32_t i, uint64_t pos, bool active) {
     uint32_t r = K4M_FOREIGN;
     uint64_t key = ~0ull;
-    if (i < cr) {
-      const uint64_t pos = k4d_sa_at<EL>(a.ix, fr + i);
+    if (active) {
       const int e = k4d_map_entry(a.ix, pos);
       if (e >= 0) r = a.rank[e];
       if (r != K4M_FOREIGN) key = ((uint64_t)r << 32) | (uint32_t)(pos - a.ix.ent_start[e]);
       else if (i > 0) foreign = true;
     }
-    if (c0 == 0) rc_first_target = __shfl(r, 0, 64) != K4M_FOREIGN;
+    if (i == (uint32_t)lane) rc_first_target = __shfl(r, 0, 64) != K4M_FOREIGN;  // (the first turn)
     if (rc_first_target) min_key = min(min_key, key);
-  }
-  for (int d = 32; d > 0; d >>= 1) min_key = min(min_key, (uint64_t)__shfl_xor((unsigned long long)min_key, d, 64));
+    return false;
+  });
+  min_key = k4d_wave_min(min_key);
   // (a K-mer that is its own reverse complement finds the flag it has just set: SetBaseFlags with one locus twice)
   if ((cr > 0 && fr == fs) || min_key < own) {
     if (lane == 0) a.status[pid] = K4M_DUPLICATE;
@@ -191,11 +167,7 @@ __global__ void __launch_bounds__(64) k4k_species_kmers(K4MScanArgs a) {
   }
   // 5. :1167-1203
   if (a.prefix_len) {
-    first = 0; cnt = 0;
-    if (lane < 2) {
-      qs.s = lane;
-      cnt = k4q_count<EL>(a.ix, tb, qs, 0u, (int)a.prefix_len, 0xFFFFFFFFu, first);
-    }
+    cnt = k4d_cores_to_lanes<EL>(a.ix, tb, lane, 2u, 1u, a.prefix_len, 0xFFFFFFFFu, strand, whole, first);
     uint32_t have = k4m_prefix_entries<EL>(a.ix, __shfl(first, 0, 64), __shfl(cnt, 0, 64), a.rank, seen, 0u, a.min_with_prefix);
     have = k4m_prefix_entries<EL>(a.ix, __shfl(first, 1, 64), __shfl(cnt, 1, 64), a.rank, seen, have, a.min_with_prefix);
     if (have < a.min_with_prefix) {
@@ -226,11 +198,7 @@ __global__ void __launch_bounds__(256) k4k_kmarkers_tally(const uint8_t* status,
       if (b == K4M_ACCEPTED) { c[3]++; break; }
     }
   }
-  for (int k = 0; k < 4; k++) {
-    uint32_t x = c[k];
-    for (int d = 32; d > 0; d >>= 1) x += (uint32_t)__shfl_xor(x, d, 64);
-    if ((threadIdx.x & 63) == 0 && x) atomicAdd(&tot[k], (unsigned long long)x);
-  }
+  k4d_tally_flush(c, tot);
 }
 
 // is an ACGT run of K4M_MAX_RUN bases or more in a target?  Such a run covers a locus that is a multiple of K4M_MAX_RUN / 2; one
@@ -310,8 +278,7 @@ static int exact_ranges_run(k4_index* ix, int64_t n, const uint8_t* d_seqs, cons
   K4MarkState& m = ix->kmk;
   const unsigned grid = (unsigned)std::min<int64_t>((n + 63) / 64, 1 << 16);
   K4_HIP(ix, m.timer.begin(st));
-  if (ix->d.el == 4) hipLaunchKernelGGL(k4k_exact_ranges<4>, dim3(grid), dim3(64), 0, st, ix->d, n, d_seqs, d_offs, d_lens, d_firsts, d_counts);
-  else hipLaunchKernelGGL(k4k_exact_ranges<5>, dim3(grid), dim3(64), 0, st, ix->d, n, d_seqs, d_offs, d_lens, d_firsts, d_counts);
+  K4S_LAUNCH_EL(ix, k4k_exact_ranges, grid, 64, st, ix->d, n, d_seqs, d_offs, d_lens, d_firsts, d_counts);
   K4_HIP(ix, hipGetLastError());
   K4_HIP(ix, m.timer.end(st));
   return K4_OK;
@@ -326,9 +293,7 @@ extern "C" int k4_exact_ranges_batch_dev(k4_index* ix, int64_t n, const void* d_
   K4_HIP(ix, hipSetDevice(ix->device));
   const hipStream_t st = (hipStream_t)stream;
   K4_TRY(exact_ranges_run(ix, n, (const uint8_t*)d_seqs, (const uint64_t*)d_offs, (const uint32_t*)d_lens, (uint64_t*)d_firsts, (uint32_t*)d_counts, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
-  K4_HIP(ix, ix->kmk.timer.read());
-  return K4_OK;
+  return k4s_call_close(ix, st, ix->kmk.timer);
 }
 
 extern "C" int k4_exact_ranges_batch(k4_index* ix, int64_t n, const uint8_t* seqs, const uint64_t* offs, const uint32_t* lens, uint64_t* firsts,
@@ -338,9 +303,8 @@ extern "C" int k4_exact_ranges_batch(k4_index* ix, int64_t n, const uint8_t* seq
   if (n > 0 && !counts) return k4_fail(ix, K4_ERR_PARAMS, "exact ranges: null argument");
   if (n == 0) return K4_OK;
   K4MarkState& m = ix->kmk;
-  K4_HIP(ix, hipSetDevice(ix->device));
-  const hipStream_t st = ix->stream;
-  K4_HIP(ix, hipStreamSynchronize(st));  // (the staging about to be replaced may still be read by the batch before)
+  hipStream_t st;
+  K4_TRY(k4s_call_open(ix, &st));
   K4_TRY(k4s_stage_seqs(ix, n, seqs, offs, lens, nullptr));
   K4_HIP(ix, m.out.reserve((size_t)n * 12 + 16));
   uint64_t* d_firsts = m.out.as<uint64_t>();
@@ -349,9 +313,7 @@ extern "C" int k4_exact_ranges_batch(k4_index* ix, int64_t n, const uint8_t* seq
                           d_counts, st));
   K4_HIP(ix, hipMemcpyAsync(firsts, d_firsts, (size_t)n * 8, hipMemcpyDeviceToHost, st));
   K4_HIP(ix, hipMemcpyAsync(counts, d_counts, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
-  K4_HIP(ix, m.timer.read());
-  return K4_OK;
+  return k4s_call_close(ix, st, m.timer);
 }
 
 extern "C" int k4_matches_other_chroms_batch(k4_index* ix, int32_t n_ids, const uint32_t* ids, int32_t max_tot_mm, int64_t n, const uint8_t* seqs,
@@ -364,26 +326,20 @@ extern "C" int k4_matches_other_chroms_batch(k4_index* ix, int32_t n_ids, const 
     if (lens[i] > K4M_MAX_PROBE) return k4_fail(ix, K4_ERR_PARAMS, "MatchesOtherChroms: probe %lld of %u bases, at most %d", (long long)i, lens[i], K4M_MAX_PROBE);
   if (n == 0) return K4_OK;
   K4MarkState& m = ix->kmk;
-  K4_HIP(ix, hipSetDevice(ix->device));
-  const hipStream_t st = ix->stream;
+  hipStream_t st;
+  K4_TRY(k4s_call_open(ix, &st));
   std::vector<uint8_t> h_rank;
   K4_TRY(kmarkers_rank(ix, n_ids, ids, st, h_rank));
   K4_TRY(k4s_stage_seqs(ix, n, seqs, offs, lens, nullptr));
   K4_HIP(ix, m.out.reserve((size_t)n * 4 + 16));
   const unsigned grid = (unsigned)std::min<int64_t>(n, 1 << 16);
   K4_HIP(ix, m.timer.begin(st));
-  if (ix->d.el == 4)
-    hipLaunchKernelGGL(k4k_matches_others<4>, dim3(grid), dim3(64), 0, st, ix->d, n, ix->seq_stage.seqs.as<uint8_t>(), ix->seq_stage.offs.as<uint64_t>(),
-                       ix->seq_stage.lens.as<uint32_t>(), m.rank.as<uint8_t>(), (uint32_t)max_tot_mm, m.out.as<int32_t>());
-  else
-    hipLaunchKernelGGL(k4k_matches_others<5>, dim3(grid), dim3(64), 0, st, ix->d, n, ix->seq_stage.seqs.as<uint8_t>(), ix->seq_stage.offs.as<uint64_t>(),
-                       ix->seq_stage.lens.as<uint32_t>(), m.rank.as<uint8_t>(), (uint32_t)max_tot_mm, m.out.as<int32_t>());
+  K4S_LAUNCH_EL(ix, k4k_matches_others, grid, 64, st, ix->d, n, ix->seq_stage.seqs.as<uint8_t>(), ix->seq_stage.offs.as<uint64_t>(),
+                ix->seq_stage.lens.as<uint32_t>(), m.rank.as<uint8_t>(), (uint32_t)max_tot_mm, m.out.as<int32_t>());
   K4_HIP(ix, hipGetLastError());
   K4_HIP(ix, m.timer.end(st));
   K4_HIP(ix, hipMemcpyAsync(matches, m.out.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
-  K4_HIP(ix, m.timer.read());
-  return K4_OK;
+  return k4s_call_close(ix, st, m.timer);
 }
 
 // the species scan on a device status array, its arguments checked; *total = the status bytes written
@@ -454,19 +410,17 @@ static int species_run(k4_index* ix, const k4_kmarkers_params* p, int32_t n_targ
   const uint32_t others = ix->d.n_entries - (uint32_t)n_targets;  // :719-720
   a.min_with_prefix = p->min_with_prefix == 0 || (uint32_t)p->min_with_prefix > others ? others : (uint32_t)p->min_with_prefix;
   K4_HIP(ix, m.timer.begin(st));
-  for (uint64_t k0 = 0; k0 < *total; k0 += K4M_LAUNCH_KMERS) {
+  k4s_launch_windows(*total, K4M_LAUNCH_KMERS, [&](uint64_t k0, uint64_t k1) {
     a.k0 = k0;
-    a.k1 = std::min<uint64_t>(*total, k0 + K4M_LAUNCH_KMERS);
-    if (ix->d.el == 4) hipLaunchKernelGGL(k4k_species_kmers<4>, dim3((unsigned)(a.k1 - a.k0)), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k4k_species_kmers<5>, dim3((unsigned)(a.k1 - a.k0)), dim3(64), 0, st, a);
-  }
+    a.k1 = k1;
+    K4S_LAUNCH_EL(ix, k4k_species_kmers, (unsigned)(k1 - k0), 64, st, a);
+  });
   hipLaunchKernelGGL(k4k_kmarkers_tally, dim3((unsigned)std::min<uint64_t>((*total + 255) / 256, 1024)), dim3(256), 0, st, d_status, *total, (int)p->mode, d_ctl);
   K4_HIP(ix, hipGetLastError());
   K4_HIP(ix, m.timer.end(st));
   unsigned long long t4[4] = {0, 0, 0, 0};
   K4_HIP(ix, hipMemcpyAsync(t4, d_ctl, sizeof(t4), hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
-  K4_HIP(ix, m.timer.read());
+  K4_TRY(k4s_call_close(ix, st, m.timer));
   tot->processed = t4[0]; tot->cultivar_specific = t4[1]; tot->hamming_retained = t4[2]; tot->accepted = t4[3];
   return K4_OK;
 }
@@ -480,12 +434,14 @@ extern "C" int k4_species_kmers_batch_dev(k4_index* ix, const k4_kmarkers_params
 // host status array: the bytes of the targets' loci come back, the bytes behind them stay as they were
 extern "C" int k4_species_kmers_batch(k4_index* ix, const k4_kmarkers_params* p, int32_t n_targets, const uint32_t* target_ids, uint8_t* status,
                                       uint64_t status_len, k4_kmarkers_totals* totals) {
+  if (!ix) return K4_ERR_PARAMS;
   uint64_t total = 0;
-  int rc = species_run(ix, p, n_targets, target_ids, status, status_len, true, totals, &total, ix ? ix->stream : nullptr);
+  hipStream_t st;
+  K4_TRY(k4s_call_open(ix, &st));
+  const int rc = species_run(ix, p, n_targets, target_ids, status, status_len, true, totals, &total, st);
   if (rc != K4_OK || total == 0) return rc;
-  K4_HIP(ix, hipMemcpyAsync(status, ix->kmk.out.p, (size_t)total, hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipStreamSynchronize(ix->stream));
-  return K4_OK;
+  K4_HIP(ix, hipMemcpyAsync(status, ix->kmk.out.p, (size_t)total, hipMemcpyDeviceToHost, st));
+  return k4s_call_close(ix, st, ix->kmk.timer);
 }
 
 extern "C" double k4_kmarkers_last_kernel_ms(const k4_index* ix) { return ix ? ix->kmk.timer.ms : 0.0; }

@@ -8,16 +8,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "k4_sfxarray.hpp"
+#include "k4_facade_test_util.h"
 
 int main(int argc, char** argv) {
   if (argc < 4) return 1;
   CSfxArray* pSfx = new CSfxArray;
-  if (pSfx->Open(argv[1]) < 0) {
-    while (pSfx->NumErrMsgs()) fprintf(stderr, "%s\n", pSfx->GetErrMsg());
-    return 2;
-  }
-  if (pSfx->SetTargBlock(1) < 0) return 3;
+  if (const int rc = K4FtOpen(pSfx, argv[1])) return rc;
   FILE* f = fopen(argv[2], "r");
   if (!f) return 4;
   int nProbes = 0, badWalk = 0, badM1 = 0, badMn = 0;
@@ -25,10 +21,8 @@ int main(int argc, char** argv) {
   for (;;) {
     unsigned len, nIds;
     if (fscanf(f, "%u", &len) != 1) break;
-    std::vector<char> s(len + 2);
-    if (fscanf(f, "%s %u", s.data(), &nIds) != 2) return 5;
-    std::vector<etSeqBase> Probe(len + 8, 0);
-    for (unsigned j = 0; j < len; j++) Probe[j] = (etSeqBase)(s[j] - '0');
+    std::vector<etSeqBase> Probe;
+    if (!K4FtReadProbe(f, len, Probe, 8) || fscanf(f, "%u", &nIds) != 1) return 5;
     std::vector<int> Ids(nIds);
     for (unsigned j = 0; j < nIds; j++)
       if (fscanf(f, "%d", &Ids[j]) != 1) return 5;

@@ -165,7 +165,8 @@ struct K4DevBuf {
 
 // The device time of an entry point's last call, owned like a K4DevBuf (`delete ix` destroys the events).  The entry point calls
 // reset() first, so a call that fails or has no work reports 0; it brackets its launches with begin() and end() on their stream
-// and, behind its own synchronise of that stream, calls read().  end() and read() do nothing for a section that never began.
+// and, behind its own synchronise of that stream, calls read(), which adds the section to ms: a call of several sections (the
+// windows of k4_cults.hip) reports their sum.  end() and read() do nothing for a section that never began.
 struct K4Timer {
   hipEvent_t ev[2] = {nullptr, nullptr};  // made by the first begin()
   double ms = 0;
@@ -190,7 +191,7 @@ struct K4Timer {
     float f = 0;
     const hipError_t rc = open ? hipEventElapsedTime(&f, ev[0], ev[1]) : hipSuccess;
     open = false;
-    ms = f;
+    ms += f;
     return rc;
   }
 };

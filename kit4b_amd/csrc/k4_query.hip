@@ -211,7 +211,7 @@ __global__ void __launch_bounds__(64) k4k_query_locate(K4QueryArgs a) {
   const uint32_t nm = s_nm;
   uint32_t kept = 0;
   for (uint32_t j = (uint32_t)lane; j < nm; j += 64) kept += (ws[j].flags & 2u) ? 0u : 1u;
-  for (int d = 32; d > 0; d >>= 1) kept += __shfl_xor(kept, d, 64);
+  kept = k4d_wave_sum(kept);
   if (lane == 0) { a.cnt[qi] = nm; a.cnt[a.n + qi] = kept; }
 }
 
@@ -304,8 +304,7 @@ extern "C" int k4_locate_query_seqs_batch_dev(k4_index* ix, const k4_query_param
   a.cnt = q.cnt.as<uint32_t>();
   if (n > 0) {  // (a batch of no queries has no work to time)
     K4_HIP(ix, q.timer.begin(st));
-    if (ix->d.el == 4) hipLaunchKernelGGL(k4k_query_locate<4>, dim3((unsigned)n), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k4k_query_locate<5>, dim3((unsigned)n), dim3(64), 0, st, a);
+    K4S_LAUNCH_EL(ix, k4k_query_locate, (unsigned)n, 64, st, a);
   }
   // node_offs[0 .. n] from the counts of the nodes kept, cnt[n .. 2 n), and a zero behind them
   K4_HIP(ix, hipMemsetAsync(a.cnt + 2 * n, 0, 4, st));
@@ -329,9 +328,9 @@ extern "C" int k4_locate_query_seqs_batch(k4_index* ix, const k4_query_params* p
   ix->qry.timer.reset();
   if (n < 0 || !node_offs || (n > 0 && (!seqs || !offs || !lens)) || (nodes_cap > 0 && !nodes))
     return k4_fail(ix, K4_ERR_PARAMS, "LocateQuerySeqs: null argument");
-  K4_HIP(ix, hipSetDevice(ix->device));
   K4SeqStage& s = ix->seq_stage;
-  hipStream_t st = ix->stream;
+  hipStream_t st;
+  K4_TRY(k4s_call_open(ix, &st));
   uint32_t max_len = 0;
   K4_TRY(k4s_stage_seqs(ix, n, seqs, offs, lens, &max_len));
   if ((rc = k4_query_reserve(ix, p, n, max_len)) != K4_OK) return rc;  // (so that K4_ERR_MEM below can only mean nodes_cap)
@@ -340,7 +339,7 @@ extern "C" int k4_locate_query_seqs_batch(k4_index* ix, const k4_query_params* p
   rc = k4_locate_query_seqs_batch_dev(ix, p, n, max_len, s.seqs.p, s.offs.p, s.lens.p, s.node_offs.p, s.nodes.p, nodes_cap, st);
   if (rc != K4_OK && rc != K4_ERR_MEM) return rc;
   K4_HIP(ix, hipMemcpyAsync(node_offs, s.node_offs.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
+  K4_TRY(k4s_call_close(ix, st, ix->qry.timer));
   if (rc != K4_OK) return rc;
   if (node_offs[n]) K4_HIP(ix, hipMemcpy(nodes, s.nodes.p, (size_t)node_offs[n] * sizeof(k4_query_node), hipMemcpyDeviceToHost));
   return K4_OK;

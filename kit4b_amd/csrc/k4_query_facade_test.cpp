@@ -9,7 +9,7 @@
 #include <cstring>
 #include <thread>
 #include <vector>
-#include "k4_sfxarray.hpp"
+#include "k4_facade_test_util.h"
 
 struct Case {
   std::vector<etSeqBase> q;
@@ -40,11 +40,7 @@ static int RunCase(CSfxArray* pSfx, const Case& c, uint32_t QueryID, uint32_t Ma
 int main(int argc, char** argv) {
   if (argc < 3) return 1;
   CSfxArray* pSfx = new CSfxArray;
-  if (pSfx->Open(argv[1]) < 0) {
-    while (pSfx->NumErrMsgs()) fprintf(stderr, "%s\n", pSfx->GetErrMsg());
-    return 2;
-  }
-  if (pSfx->SetTargBlock(1) < 0) return 3;
+  if (const int rc = K4FtOpen(pSfx, argv[1])) return rc;
   FILE* f = fopen(argv[2], "r");
   if (!f) return 4;
   std::vector<Case> Cases;
@@ -52,9 +48,7 @@ int main(int argc, char** argv) {
     Case c;
     unsigned len, nn;
     if (fscanf(f, "%u %u %u %u %u %u %u %u %u", &len, &c.p[0], &c.p[1], &c.p[2], &c.p[3], &c.p[4], &c.p[5], &c.p[6], &nn) != 9) break;
-    std::vector<char> s(len + 2);
-    if (fscanf(f, "%s", s.data()) != 1) return 5;
-    for (unsigned j = 0; j < len; j++) c.q.push_back((etSeqBase)(s[j] - '0'));
+    if (!K4FtReadProbe(f, len, c.q)) return 5;
     for (unsigned k = 0; k < nn; k++) {
       std::vector<uint32_t> w(7);
       for (int j = 0; j < 7; j++)

@@ -55,6 +55,30 @@ inline int k4s_stage_seqs(k4_index* ix, int64_t n, const uint8_t* seqs, const ui
   return K4_OK;
 }
 
+// The frame of a host-pointer search call.  The opener: the index's device made current, *st = the index's stream, waited for --
+// the staged batch, the out buffer and the tables the call is about to replace may still be read by the batch before.  Between
+// the two the entry point stages (k4s_stage_seqs), reserves its out buffer, runs what its *_dev form runs and queues the copies
+// down.  The closer: the stream waited for and the timer's open section, if there is one, read.  A *_dev form ends with the closer
+// on its caller's stream.
+inline int k4s_call_open(k4_index* ix, hipStream_t* st) {
+  K4_HIP(ix, hipSetDevice(ix->device));
+  *st = ix->stream;
+  K4_HIP(ix, hipStreamSynchronize(*st));
+  return K4_OK;
+}
+inline int k4s_call_close(k4_index* ix, hipStream_t st, K4Timer& timer) {
+  K4_HIP(ix, hipStreamSynchronize(st));
+  K4_HIP(ix, timer.read());
+  return K4_OK;
+}
+
+// kernel<EL> for the index's 4- or 5-byte suffix elements
+#define K4S_LAUNCH_EL(ix, kernel, grid, block, st, ...)                                                   \
+  do {                                                                                                    \
+    if ((ix)->d.el == 4) hipLaunchKernelGGL(kernel<4>, dim3(grid), dim3(block), 0, st, __VA_ARGS__);      \
+    else hipLaunchKernelGGL(kernel<5>, dim3(grid), dim3(block), 0, st, __VA_ARGS__);                      \
+  } while (0)
+
 // What a stage needs of its record arguments besides the records themselves (SE: d_rr, PE: d_pe): the SE hit slots, the read
 // bytes with their offsets and lengths, the SE second segments.  K4RS_UNITS: the count is in SE reads or PE pairs, not in reads.
 enum : unsigned { K4RS_HITS = 1u, K4RS_READS = 2u, K4RS_SEG2 = 4u, K4RS_UNITS = 8u };

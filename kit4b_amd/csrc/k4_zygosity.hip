@@ -113,48 +113,38 @@ K4_DEV int k4z_near(const K4DevIndex& ix, K4Tb& tb, const K4ZLimits& p, K4ZShare
   const uint32_t n_core = k4z_core_offsets(p, len, sh.ofs, lane);
   __syncthreads();
   // the runs, one per lane
-  uint64_t first = 0;
-  uint32_t cnt = 0;
-  if ((uint32_t)lane < 2 * n_core) {
-    K4QSeq qs;
-    qs.q = sh.pb[(uint32_t)lane >= n_core ? 1 : 0]; qs.len = len; qs.s = 0;
-    cnt = k4q_count<EL>(ix, tb, qs, sh.ofs[(uint32_t)lane % n_core], (int)p.core_len, 0xFFFFFFFFu, first);
-  }
+  uint64_t first;
+  const uint32_t cnt = k4d_cores_to_lanes<EL>(
+      ix, tb, lane, 2 * n_core, n_core, p.core_len, 0xFFFFFFFFu, [&](uint32_t s) { return K4QSeq{sh.pb[s], len, 0}; },
+      [&](uint32_t core) { return sh.ofs[core]; }, first);
   // which path: per pass the runs' sum against the node limit, the longest run against CurMaxIter; ids = what a pass can insert
   uint32_t pass_ids[2];
   for (uint32_t s = 0; s < 2; s++) {
     const bool mine = (uint32_t)lane >= s * n_core && (uint32_t)lane < (s + 1) * n_core;
-    unsigned long long sum = mine ? cnt : 0, cap = mine ? (p.cur_max_iter ? min(cnt, p.cur_max_iter) : cnt) : 0;
-    for (int d = 32; d > 0; d >>= 1) {
-      sum += __shfl_xor(sum, d, 64);
-      cap += __shfl_xor(cap, d, 64);
-    }
+    const uint64_t sum = k4d_wave_sum((uint64_t)(mine ? cnt : 0u));
+    const uint64_t cap = k4d_wave_sum((uint64_t)(mine ? (p.cur_max_iter ? min(cnt, p.cur_max_iter) : cnt) : 0u));
     if (__ballot(mine && p.cur_max_iter && cnt > p.cur_max_iter) || sum >= p.n_ident_nodes) ordered = true;
-    pass_ids[s] = (uint32_t)min(cap, (unsigned long long)p.n_ident_nodes);
+    pass_ids[s] = (uint32_t)min(cap, (uint64_t)p.n_ident_nodes);
   }
   ids = max(pass_ids[0], pass_ids[1]);
   uint32_t total = 0;
   if (!ordered && !rewalk) {
     bool minus_one = false;
     for (uint32_t it = 0; it < 2 * n_core && !minus_one; it++) {
-      const uint64_t f = __shfl(first, (int)it, 64);
-      const uint32_t c = __shfl(cnt, (int)it, 64);
       const uint32_t k = it % n_core, ofs = sh.ofs[k];
       const uint8_t* pbs = sh.pb[it / n_core];
-      for (uint32_t c0 = 0; c0 < c && !minus_one; c0 += 64) {
+      k4d_run_walk<EL>(ix, lane, __shfl(first, (int)it, 64), __shfl(cnt, (int)it, 64), [&](uint32_t, uint64_t pos, bool active) {
         int out = K4Z_SKIP;
-        if (c0 + (uint32_t)lane < c) {
-          const uint64_t pos = k4d_sa_at<EL>(ix, f + c0 + (uint32_t)lane);
-          if (pos >= ofs && pos - ofs + len <= ix.n) {
-            uint32_t dirty;
-            out = k4z_extend(ix, tb, p, pbs, len, sh.ofs, n_core, pos - ofs, probe_id, probe_ofs, dirty);
-            if (~dirty & ((1u << k) - 1u)) out = K4Z_SKIP;  // an earlier core of this pass has met it
-          }
+        if (active && pos >= ofs && pos - ofs + len <= ix.n) {
+          uint32_t dirty;
+          out = k4z_extend(ix, tb, p, pbs, len, sh.ofs, n_core, pos - ofs, probe_id, probe_ofs, dirty);
+          if (~dirty & ((1u << k) - 1u)) out = K4Z_SKIP;  // an earlier core of this pass has met it
         }
         if (out >= 0) sink.count(ix, out);
         total += (uint32_t)__popcll(__ballot(out >= 0));
         minus_one = __ballot(out == K4Z_OWN) != 0 || (p.max_matches > 0 && total > p.max_matches);
-      }
+        return minus_one;
+      });
     }
     if (!minus_one) return (int)total;
     if (!sink.row) return -1;
@@ -185,21 +175,18 @@ K4_DEV int k4z_near(const K4DevIndex& ix, K4Tb& tb, const K4ZLimits& p, K4ZShare
     uint32_t nodes = 0;
     bool zero = false;
     for (uint32_t k = 0; k < n_core && nodes < p.n_ident_nodes; k++) {
-      const uint64_t f = __shfl(first, (int)(s * n_core + k), 64);
       const uint32_t c = __shfl(cnt, (int)(s * n_core + k), 64);
       const uint32_t ofs = sh.ofs[k];
       uint32_t iter = 0;
-      bool copies_known = false, stop = false;
-      for (uint32_t c0 = 0; c0 < c && !stop; c0 += 64) {
+      bool copies_known = false, stop = false, minus_one = false;
+      k4d_run_walk<EL>(ix, lane, __shfl(first, (int)(s * n_core + k), 64), c, [&](uint32_t i0, uint64_t pos, bool active) {
+        const uint32_t c0 = i0 - (uint32_t)lane;
         int out = K4Z_SKIP;
         uint32_t tid = 0;
-        if (c0 + (uint32_t)lane < c) {
-          const uint64_t pos = k4d_sa_at<EL>(ix, f + c0 + (uint32_t)lane);
-          if (pos >= ofs && pos - ofs + len <= ix.n) {
-            uint32_t dirty;
-            tid = (uint32_t)(1 + pos - ofs);
-            out = k4z_extend(ix, tb, p, pbs, len, sh.ofs, n_core, pos - ofs, probe_id, probe_ofs, dirty);
-          }
+        if (active && pos >= ofs && pos - ofs + len <= ix.n) {
+          uint32_t dirty;
+          tid = (uint32_t)(1 + pos - ofs);
+          out = k4z_extend(ix, tb, p, pbs, len, sh.ofs, n_core, pos - ofs, probe_id, probe_ofs, dirty);
         }
         __syncthreads();  // (lane 0 has read the chunk before)
         sh.tid[lane] = tid;
@@ -229,8 +216,10 @@ K4_DEV int k4z_near(const K4DevIndex& ix, K4Tb& tb, const K4ZLimits& p, K4ZShare
         }
         __syncthreads();
         stop = sh.ctl[0] != 0; iter = sh.ctl[2]; nodes = sh.ctl[3]; total = sh.ctl[4]; copies_known = sh.ctl[5] != 0; zero = sh.ctl[6] != 0;
-        if (sh.ctl[1]) return -1;
-      }
+        minus_one = sh.ctl[1] != 0;
+        return stop || minus_one;
+      });
+      if (minus_one) return -1;
     }
   }
   return (int)total;
@@ -323,12 +312,8 @@ struct K4ZScanArgs {
 template <int EL>
 K4_DEV void k4z_one_locus(const K4ZScanArgs& a, K4ZShared& sh, K4Tb& tb, uint64_t pid, bool second) {
   const int lane = threadIdx.x;
-  uint32_t lo = 0, hi = a.src_count - 1;  // the last source entry whose loci start at or before pid
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (a.pre[mid] <= pid) lo = mid; else hi = mid - 1;
-  }
-  const uint32_t r = lo, e = a.src_first + r, locus = (uint32_t)(pid - a.pre[r]), len = a.subseq_len;
+  const uint32_t r = k4d_last_le(a.src_count, pid, [&](uint32_t i) { return a.pre[i]; });  // the source entry that holds start locus pid
+  const uint32_t e = a.src_first + r, locus = (uint32_t)(pid - a.pre[r]), len = a.subseq_len;
   const uint32_t seq_len = (uint32_t)(a.ix.ent_end[e] - a.ix.ent_start[e] + 1);
   if (seq_len < len || locus > seq_len - len) {
     if (lane == 0) a.status[pid] = K4Z_ST_NO_WINDOW;
@@ -347,7 +332,7 @@ K4_DEV void k4z_one_locus(const K4ZScanArgs& a, K4ZShared& sh, K4Tb& tb, uint64_
   }
   const uint32_t words = (a.ix.n_entries + 31) >> 5;
   for (uint32_t w = (uint32_t)lane; w < words; w += 64) sh.seen[w] = 0;
-  for (int d = 32; d > 0; d >>= 1) ns += (uint32_t)__shfl_xor(ns, d, 64);
+  ns = k4d_wave_sum(ns);
   const bool over = __ballot(bad) != 0 || ns > a.max_ns;
   __syncthreads();
   if (over) {
@@ -425,11 +410,7 @@ __global__ void __launch_bounds__(256) k4z_zygosity_tally(const uint8_t* status,
     c[4] += (s & 3u) == 3;
     c[5] += (s & K4Z_ST_ORDERED) != 0;
   }
-  for (int k = 0; k < 6; k++) {
-    uint32_t x = c[k];
-    for (int d = 32; d > 0; d >>= 1) x += (uint32_t)__shfl_xor(x, d, 64);
-    if ((threadIdx.x & 63) == 0 && x) atomicAdd(&tot[k], (unsigned long long)x);
-  }
+  k4d_tally_flush(c, tot);
 }
 
 // ==== host side ======================================================================================================
@@ -459,12 +440,6 @@ static int check_limits(k4_index* ix, const k4_near_params* p, K4ZLimits* l) {
   return K4_OK;
 }
 
-#define K4Z_LAUNCH_EL(kernel, grid, st, ...)                                                      \
-  do {                                                                                            \
-    if (ix->d.el == 4) hipLaunchKernelGGL(kernel<4>, dim3(grid), dim3(64), 0, st, __VA_ARGS__);   \
-    else hipLaunchKernelGGL(kernel<5>, dim3(grid), dim3(64), 0, st, __VA_ARGS__);                 \
-  } while (0)
-
 // the batch on device arrays, its arguments checked; ends with the stream waited for
 static int near_run(k4_index* ix, const K4ZLimits& l, int64_t n, const uint8_t* d_seqs, const uint64_t* d_offs, const uint32_t* d_lens,
                     const uint32_t* d_entries, const uint32_t* d_ofs, int32_t* d_rslt, uint32_t* d_counts, hipStream_t st) {
@@ -476,7 +451,7 @@ static int near_run(k4_index* ix, const K4ZLimits& l, int64_t n, const uint8_t* 
   a.ix = ix->d; a.p = l; a.n = n; a.seqs = d_seqs; a.offs = d_offs; a.lens = d_lens; a.probe_entries = d_entries; a.probe_ofs = d_ofs;
   a.rslt = d_rslt; a.counts = d_counts; a.list = z.list.as<uint32_t>(); a.ctl = z.ctl.as<unsigned long long>(); a.big = nullptr; a.big_slots = 0;
   K4_HIP(ix, z.timer.begin(st));
-  K4Z_LAUNCH_EL(k4z_near_matches, (unsigned)std::min<int64_t>(n, K4Z_LAUNCH), st, a);
+  K4S_LAUNCH_EL(ix, k4z_near_matches, (unsigned)std::min<int64_t>(n, K4Z_LAUNCH), 64, st, a);
   K4_HIP(ix, hipGetLastError());
   unsigned long long c[3] = {0, 0, 0};
   K4_HIP(ix, hipMemcpyAsync(c, z.ctl.p, sizeof(c), hipMemcpyDeviceToHost, st));
@@ -486,13 +461,12 @@ static int near_run(k4_index* ix, const K4ZLimits& l, int64_t n, const uint8_t* 
     unsigned grid = 0;
     K4_TRY(zygosity_big(ix, c[K4Z_CTL_MAX_IDS], c[K4Z_CTL_LISTED], &a.big_slots, &grid));
     a.big = z.big.as<uint32_t>();
-    K4Z_LAUNCH_EL(k4z_near_matches_big, grid, st, a, (uint32_t)c[K4Z_CTL_LISTED]);
+    K4S_LAUNCH_EL(ix, k4z_near_matches_big, grid, 64, st, a, (uint32_t)c[K4Z_CTL_LISTED]);
     K4_HIP(ix, hipGetLastError());
     K4_HIP(ix, hipMemcpyAsync(c, z.ctl.p, sizeof(c), hipMemcpyDeviceToHost, st));
   }
   K4_HIP(ix, z.timer.end(st));
-  K4_HIP(ix, hipStreamSynchronize(st));
-  K4_HIP(ix, z.timer.read());
+  K4_TRY(k4s_call_close(ix, st, z.timer));
   if (c[K4Z_CTL_TABLE]) return k4_fail(ix, K4_ERR_MEM, "LocateAllNearMatches: %llu probes outgrew their dedupe table", c[K4Z_CTL_TABLE]);
   return K4_OK;
 }
@@ -541,9 +515,8 @@ extern "C" int k4_all_near_matches_batch(k4_index* ix, const k4_near_params* p, 
   K4_TRY(near_check_lens(ix, l, n, lens));
   if (n == 0) return K4_OK;
   K4ZygState& z = ix->zyg;
-  K4_HIP(ix, hipSetDevice(ix->device));
-  const hipStream_t st = ix->stream;
-  K4_HIP(ix, hipStreamSynchronize(st));  // (the staging about to be replaced may still be read by the batch before)
+  hipStream_t st;
+  K4_TRY(k4s_call_open(ix, &st));
   K4_TRY(k4s_stage_seqs(ix, n, seqs, offs, lens, nullptr));
   const size_t n_counts = counts ? (size_t)n * ix->d.n_entries : 0;
   K4_HIP(ix, z.out.reserve((size_t)n * 12 + n_counts * 4 + 16));
@@ -557,8 +530,7 @@ extern "C" int k4_all_near_matches_batch(k4_index* ix, const k4_near_params* p, 
                   d_rslt, d_counts, st));
   K4_HIP(ix, hipMemcpyAsync(rslts, d_rslt, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   if (counts) K4_HIP(ix, hipMemcpyAsync(counts, d_counts, n_counts * 4, hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
-  return K4_OK;
+  return k4s_call_close(ix, st, z.timer);
 }
 
 // the front end's derivation (genzygosity.cpp:681-697, :998-1027, :1190) from the scan's parameters and the index
@@ -635,11 +607,11 @@ static int zygosity_run(k4_index* ix, const k4_zygosity_params* p, int32_t src_f
     const uint64_t g1 = std::min<uint64_t>(*total, g0 + (uint64_t)K4Z_GROUP * K4Z_LAUNCH);
     a.g0 = g0;
     a.big = nullptr;
-    for (uint64_t k0 = g0; k0 < g1; k0 += K4Z_LAUNCH) {
-      a.k0 = k0;
-      a.k1 = std::min<uint64_t>(g1, k0 + K4Z_LAUNCH);
-      K4Z_LAUNCH_EL(k4z_zygosity_scan, (unsigned)(a.k1 - a.k0), st, a);
-    }
+    k4s_launch_windows(g1 - g0, K4Z_LAUNCH, [&](uint64_t k0, uint64_t k1) {
+      a.k0 = g0 + k0;
+      a.k1 = g0 + k1;
+      K4S_LAUNCH_EL(ix, k4z_zygosity_scan, (unsigned)(k1 - k0), 64, st, a);
+    });
     K4_HIP(ix, hipGetLastError());
     unsigned long long c[3] = {0, 0, 0};  // the windows of this group that wait for tables in HBM
     K4_HIP(ix, hipMemcpyAsync(c, d_ctl, sizeof(c), hipMemcpyDeviceToHost, st));
@@ -648,7 +620,7 @@ static int zygosity_run(k4_index* ix, const k4_zygosity_params* p, int32_t src_f
       unsigned grid = 0;
       K4_TRY(zygosity_big(ix, c[K4Z_CTL_MAX_IDS], c[K4Z_CTL_LISTED], &a.big_slots, &grid));
       a.big = z.big.as<uint32_t>();
-      K4Z_LAUNCH_EL(k4z_zygosity_scan_big, grid, st, a, (uint32_t)c[K4Z_CTL_LISTED]);
+      K4S_LAUNCH_EL(ix, k4z_zygosity_scan_big, grid, 64, st, a, (uint32_t)c[K4Z_CTL_LISTED]);
       K4_HIP(ix, hipGetLastError());
       z.second += c[K4Z_CTL_LISTED];
       K4_HIP(ix, hipMemsetAsync(d_ctl, 0, 2 * 8, st));
@@ -661,8 +633,7 @@ static int zygosity_run(k4_index* ix, const k4_zygosity_params* p, int32_t src_f
   K4_HIP(ix, z.timer.end(st));
   unsigned long long t16[16] = {0};
   K4_HIP(ix, hipMemcpyAsync(t16, d_ctl, sizeof(t16), hipMemcpyDeviceToHost, st));
-  K4_HIP(ix, hipStreamSynchronize(st));
-  K4_HIP(ix, z.timer.read());
+  K4_TRY(k4s_call_close(ix, st, z.timer));
   if (tables || t16[K4Z_CTL_TABLE]) return k4_fail(ix, K4_ERR_MEM, "genzygosity: a window outgrew its dedupe table");
   const unsigned long long* t = t16 + K4Z_CTL_TOTALS;
   tot->windows = t[0]; tot->passed_over = t[1]; tot->rejected = t[2]; tot->unique = t[3]; tot->unique_matched = t[4]; tot->ordered = t[5];
@@ -680,16 +651,18 @@ extern "C" int k4_zygosity_batch_dev(k4_index* ix, const k4_zygosity_params* p, 
 // host arrays: the matrix and subseqs are written whole; of status the bytes of the source entries' loci, the rest stays
 extern "C" int k4_zygosity_batch(k4_index* ix, const k4_zygosity_params* p, int32_t src_first, int32_t src_count, uint32_t* matrix, uint32_t* subseqs,
                                  uint8_t* status, uint64_t status_len, k4_zygosity_totals* totals) {
+  if (!ix) return K4_ERR_PARAMS;
   uint64_t total = 0;
-  int rc = zygosity_run(ix, p, src_first, src_count, matrix, subseqs, status, status_len, true, totals, &total, ix ? ix->stream : nullptr);
+  hipStream_t st;
+  K4_TRY(k4s_call_open(ix, &st));
+  const int rc = zygosity_run(ix, p, src_first, src_count, matrix, subseqs, status, status_len, true, totals, &total, st);
   if (rc != K4_OK || src_count == 0) return rc;
   K4ZygState& z = ix->zyg;
   const size_t cells = (size_t)src_count * ix->d.n_entries;
-  K4_HIP(ix, hipMemcpyAsync(matrix, z.out.p, cells * 4, hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipMemcpyAsync(subseqs, z.out.as<uint32_t>() + cells, (size_t)src_count * 4, hipMemcpyDeviceToHost, ix->stream));
-  if (status && total) K4_HIP(ix, hipMemcpyAsync(status, z.out.as<uint32_t>() + cells + src_count, (size_t)total, hipMemcpyDeviceToHost, ix->stream));
-  K4_HIP(ix, hipStreamSynchronize(ix->stream));
-  return K4_OK;
+  K4_HIP(ix, hipMemcpyAsync(matrix, z.out.p, cells * 4, hipMemcpyDeviceToHost, st));
+  K4_HIP(ix, hipMemcpyAsync(subseqs, z.out.as<uint32_t>() + cells, (size_t)src_count * 4, hipMemcpyDeviceToHost, st));
+  if (status && total) K4_HIP(ix, hipMemcpyAsync(status, z.out.as<uint32_t>() + cells + src_count, (size_t)total, hipMemcpyDeviceToHost, st));
+  return k4s_call_close(ix, st, z.timer);
 }
 
 extern "C" double k4_zygosity_last_kernel_ms(const k4_index* ix) { return ix ? ix->zyg.timer.ms : 0.0; }

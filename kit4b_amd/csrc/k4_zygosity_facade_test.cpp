@@ -9,16 +9,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "k4_sfxarray.hpp"
+#include "k4_facade_test_util.h"
 
 int main(int argc, char** argv) {
   if (argc < 4) return 1;
   CSfxArray* pSfx = new CSfxArray;
-  if (pSfx->Open(argv[1]) < 0) {
-    while (pSfx->NumErrMsgs()) fprintf(stderr, "%s\n", pSfx->GetErrMsg());
-    return 2;
-  }
-  if (pSfx->SetTargBlock(1) < 0) return 3;
+  if (const int rc = K4FtOpen(pSfx, argv[1])) return rc;
   FILE* f = fopen(argv[2], "r");
   if (!f) return 4;
   int nCalls = 0, badRslt = 0, badCounts = 0, badProbe = 0, badFill = 0;
@@ -32,7 +28,7 @@ int main(int argc, char** argv) {
                &nodes, &want) != 12)
       return 5;
     std::vector<etSeqBase> Probe(len + 8, 0), Keep;
-    for (unsigned j = 0; j < len; j++) Probe[j] = (etSeqBase)(s[j] - '0');
+    K4FtDigits(s.data(), len, Probe.data());
     Keep = Probe;
     std::vector<uint32_t> Counts((size_t)numEntries + 2, 0xeeeeeeeeu);
     const int Rslt = pSfx->LocateAllNearMatches(mm, coreLen, coreDelta, slides, maxMatches, numEntries, Counts.data(), entry, ofs, (int)len, Probe.data(),

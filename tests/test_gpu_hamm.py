@@ -15,6 +15,7 @@ import hamm_craft as hc
 import hamm_ref
 import manytargets as mt
 import query_ref
+import runlen_craft as rc
 from test_hamm_cpu import distribution, load_cases, load_run
 
 pytestmark = pytest.mark.gpu
@@ -279,6 +280,26 @@ def test_five_byte_suffix_elements(built, golden_dir):
     for i, (name, form, what, p, expect) in enumerate(hc.cases()):
         if form == "sfx" and expect:
             assert np.array_equal(x.sfx_hammings([what], hc.K, **_kw(p))[0], g["out_%d" % i]), name
+
+
+def test_a_span_that_crosses_a_launch_window(k4, oracle):
+    """runlen_craft.hamming_window(): one sfx span of 32 768 + 213 K-mers of 20 (rhamm 1, every K-mer, depths 1 / 10) takes two
+    launches.  The same bytes as two calls whose spans meet at K-mer 20 000, neither of which leaves one launch; and the
+    restatement's on the 128 K-mers around K-mer 32 768."""
+    names, chroms = rc.hamming_window()
+    klen, p, n = 20, (1, 0, 1, 1, 10, 0), 33000
+    with rc.host_index(k4, oracle, names, chroms, dataset="hwin") as (x, ref):
+        whole = x.sfx_hammings([(1, 0, n)], klen, **_kw(p))[0]
+        assert x.hamming_kernel_ms() > 0
+        parts = np.full(n, 0xFF, dtype=np.uint8)
+        x.sfx_hammings([(1, 0, 20000 + klen - 1)], klen, out=parts, out_offs=[0], **_kw(p))
+        x.sfx_hammings([(1, 20000, n - 20000)], klen, out=parts, out_offs=[20000], **_kw(p))
+        assert np.array_equal(whole, parts), np.nonzero(whole != parts)[0][:8]
+        assert (whole[:n - klen + 1] != 0xFF).all() and (whole[n - klen + 1:] == 0xFF).all()
+        lo = 32768 - 64
+        want = _restate(ref, [(1, lo, 128 + klen - 1)], klen, p, 128 + klen - 1, [0])[:128]
+        assert np.array_equal(whole[lo:lo + 128], want), (whole[lo:lo + 128].tolist(), want.tolist())
+        assert len(set(want[:64].tolist())) >= 2 and len(set(want[64:].tolist())) >= 2
 
 
 def test_csfxarray_hamming_facade_program(sfx_path, golden_dir, tmp_path):

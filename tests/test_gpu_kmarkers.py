@@ -12,6 +12,7 @@ import pytest
 import cults_craft as cc
 import kmarkers_craft as kc
 import kmarkers_ref as kr
+import runlen_craft as rc
 from test_cults_cpu import big_index
 from test_kmarkers_cpu import load_calls, load_index, probe_list, scan_results
 
@@ -179,6 +180,37 @@ def test_big_targets_past_one_launch(k4, oracle, tmp_path_factory):
         x.close()
     assert np.array_equal(status, np.frombuffer(want, np.uint8)) and [tot[k] for k in TALLIES] == tallies
     assert len(status) == 34000 and tallies[3] > 20 and tallies[1] > tallies[2] > 0
+
+
+@pytest.mark.parametrize("r", rc.RUN_LENGTHS)
+def test_runs_that_end_at_a_turn_of_the_walk(k4, oracle, r):
+    """runlen_craft.kmarkers_runs(r): two 24-mers of exactly r occurrences, the one foreign occurrence at rank 0 of the run (the first
+    lane of the first turn of 64 suffixes) or at rank r - 1 (the last lane of the last turn, which ends before, at or behind a full
+    turn).  Exact ranges, MatchesOtherChroms and the species scan in mode 2 (prefix 12: the prefix pass walks the same runs from the
+    K-mer that shares its prefix with them) against the restatements."""
+    names, chroms, km = rc.kmarkers_runs(r)
+    with rc.host_index(k4, oracle, names, chroms) as (x, ref):
+        probes = [km["first"], km["last"], km["fork"], km["first"][:12], km["last"][:23]]
+        firsts, counts = x.exact_ranges(probes)
+        for p, f, c in zip(probes, firsts, counts):
+            walk = kr.walk_exacts(ref, p.tobytes())
+            assert int(c) == len(walk) and int(f) == (walk[0][0] - 1 if walk else 0), (r, int(f), int(c))
+        assert counts[:4].tolist() == [r, r, 1, r + 1]
+        # one core of 24 (probes of 48 bases, MaxTotMM 1) and cores of 8 (24 bases, MaxTotMM 2), in front of the target's occurrences
+        t = chroms[0].tobytes()
+        long_probes = [chroms[0][at:at + 48] for m in (km["first"], km["last"]) for at in (t.find(m.tobytes()), t.rfind(m.tobytes()))]
+        for ids in ([1], [1, 2], [1, 3]):
+            for mm, ps in ((1, long_probes), (2, probes[:3])):
+                got = x.matches_other_chroms(ids, mm, ps)
+                want = [kr.matches_other_chroms(ref, ids, mm, p.tobytes()) for p in ps]
+                assert got.tolist() == want, (r, ids, mm)
+        assert x.matches_other_chroms([1], 1, long_probes).tolist() == [1 if r > 1 else 0] * 4
+        for mwp in (0, 1):
+            want, tallies, _ = kr.species_kmers(ref, [1], 24, 1, 2, 12, mwp)
+            status, tot = x.species_kmers([1], 24, 1, 2, 12, mwp)
+            assert np.array_equal(status, np.frombuffer(want, np.uint8)) and [tot[k] for k in TALLIES] == tallies, (r, mwp)
+        if r > 1:  # (with one foreign entry asked for: first's occurrences, last's first and later ones, fork)
+            assert {kr.FIRST_FOREIGN, kr.FOREIGN_HIT, kr.DUPLICATE, kr.ACCEPTED} <= set(status.tolist())
 
 
 def test_csfxarray_kmarkers_facade_program(crafted, golden_dir, tmp_path):

@@ -10,6 +10,7 @@ import pytest
 
 import cults_craft as cc
 import query_ref
+import runlen_craft as rc
 import zyg_craft as zc
 import zyg_ref as zr
 from test_cults_cpu import big_index
@@ -261,6 +262,28 @@ def test_big_targets_past_one_launch(k4, oracle, tmp_path_factory):
     for launch in (gst[:16384], gst[16384:32768], gst[32768:]):
         assert (launch == 3).any() and (launch == 1).any()
     assert set(np.unique(gst)) == {0, 1, 2, 3} and gt["windows"] == 2 * (17000 - 24)
+
+
+@pytest.mark.parametrize("r", (63, 64, 65, 129))
+def test_runs_that_end_at_a_turn_of_the_walk(k4, oracle, r):
+    """runlen_craft.zygosity_runs(r): a 25-base probe whose first core of 12 has exactly r occurrences, so the walk of that run
+    ends one short of, at and one past a turn of 64 suffixes.  MaxMatches 0 and r - 1, CurMaxIter off, below r (the ordered walk,
+    cut inside a turn) and above r (the unordered one), with and without substitutions allowed: the returns and the counts rows of
+    the restatement."""
+    names, chroms, probe, ofs = rc.zygosity_runs(r)
+    with rc.host_index(k4, oracle, names, chroms) as (x, ref):
+        assert x.exact_ranges([probe[:12]])[1].tolist() == [r]
+        other = chroms[0][100:125]
+        rslts = set()
+        for mm in (2, 0):
+            for mx in (0, r - 1, r // 2):  # (the last: given up inside a turn)
+                for it in (0, r - 10, r + 10):
+                    want = [zr.near_matches(ref, mm, 12, 12, 2, mx, 4, 1, o, p.tobytes(), it, zr.NODES) for p, o in ((probe, ofs), (other, 100))]
+                    assert zr.needs_ordered_walk(ref, probe.tobytes(), 12, 12, 2, it, zr.NODES) == (it == r - 10)
+                    rs, cnt = x.all_near_matches([probe, other], [1, 1], [ofs, 100], mm, 12, 12, 2, max_matches=mx, cur_max_iter=it)
+                    assert rs.tolist() == [w[0] for w in want] and cnt.tolist() == [w[1] for w in want], (r, mm, mx, it, rs.tolist(), want[0][0])
+                    rslts.add(want[0][0])
+        assert max(rslts) == r - 1 and min(rslts) == -1 and len(rslts) >= 4
 
 
 def test_csfxarray_zygosity_facade_program(crafted, golden_dir, tmp_path):
